@@ -12,6 +12,10 @@ evaluation of every patient of the shard (one theta each).  Weak scaling (defaul
 (medgp_amd/shard.py; 4096 / N patients per rank), so the N = 1, 2, 4 lines are that cohort's own numbers.  Either way the
 cohort is sharded with no data-path collective (patients are independent).  Inputs (patients, theta) are
 resident in HBM before the timed region; outputs stay in HBM.
+
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes the last timed step's results.
+Everything beside the headline -- roofline and per-kernel split of the step, sustained rate, other_configs, CPU baseline -- runs
+with --full only.
 """
 import argparse
 import json
@@ -132,6 +136,34 @@ def pmc_traffic(kernel, P, N):
     return None, dict(prov, status="kernel not in the summary")
 
 
+def step_roofline(prof, prof_all, n_split, N, Q, D, H, P):
+    """Roofline of the dominant kernel of the timed step (`--full`): its algorithmic work (alg_work) over its live HIP-event launch time,
+    the HBM side from the committed PMC passes, and the per-kernel split of a step from `n_split` untimed steps."""
+    # dominant kernel + roofline from the live HIP-event timings
+    tot = {k: v[0] for k, v in prof.items() if v[1] > 0}
+    dom = max(tot, key=tot.get)
+    avg_ms = prof[dom][0] / prof[dom][1]
+    flop, byts, bound = alg_work(dom, N, Q, D, H)
+    if bound == "mfma":
+        achieved = flop * P / (avg_ms * 1e-3) / 1e12
+        roof = {"bound": "mfma", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": achieved / FP64_PEAK_TFLOPS}
+    else:
+        achieved = byts * P / (avg_ms * 1e-3) / 1e9
+        roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS}
+    traffic, traffic_prov = pmc_traffic(dom, P, N)
+    # the HBM side of the same kernel (verdict r5 item 6): measured traffic / launch time against the 8 TB/s spec, and against the
+    # algorithmic bytes (ratio > 1 = re-reads: the left-looking history of k_cholinv)
+    roof.update({"hbm_frac": (traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                 "hbm_achieved_GBs": (traffic / (avg_ms * 1e-3) / 1e9) if traffic else None,
+                 "traffic_ratio": (traffic / (byts * P)) if traffic and byts else None})
+    roof.update({"traffic": traffic, "traffic_provenance": traffic_prov, "kernel": dom, "avg_launch_ms": avg_ms,
+                 "alg_per_patient": {"flop": flop, "bytes": byts},
+                 "kernel_ms_per_step": {k: round(v[0] / n_split, 4) for k, v in prof_all.items() if v[1] > 0},
+                 "kernel_ms_per_step_source": "%d untimed steps behind the timed region, events around every launch; avg_launch_ms: live over the timed region" % n_split})
+    return roof
+
+
 def check_ranks(seen, world, backend):
     """None, or what is wrong with the set of ranks that took part: under nccl (one rank per GPU) the (host, uuid) pairs must be
     pairwise distinct and every rank must have reported."""
@@ -178,6 +210,25 @@ def result_line(value, n_gpus, steps, warmup, ms_per_step, workload, extra, scal
     }
     line.update(extra)
     return line
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, gids, arrays, suffix="", limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: `arrays` (name -> one row per patient: what a caller of the timed path receives) as out_dir/<name><suffix>.npy
+    in float64, beside the patients' global ids (patient_ids<suffix>.npy).  When the rows would exceed `limit` bytes in all, a fixed
+    sample of the patients (seed 0, the same for the same arguments) is written instead, in patient order."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(gids)
+    arrays = dict(arrays, patient_ids=np.asarray(gids))
+    row_bytes = 8 * sum(int(np.prod(np.shape(a)[1:])) for a in arrays.values())
+    rows = np.arange(n)
+    budget = limit - 128 * len(arrays)        # (the .npy header of each file)
+    if row_bytes * n > budget:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=max(1, budget // row_bytes), replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.asarray(a, dtype=np.float64)[rows])
 
 
 def usable_cores():
@@ -682,7 +733,15 @@ def main():
     ap.add_argument("--backend", choices=("auto", "nccl", "gloo"), default="auto",
                     help="process-group backend for N > 1: auto = nccl (RCCL) with one rank per GPU, gloo when ranks share GPUs")
     ap.add_argument("--dump-results", default=None, help="write this rank's (global patient ids, nlml, gradient row sums) to <path>.rank<r>.npz")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (nlml, gradient, status per patient, with the patients' global ids) as "
+                         "DIR/<name>.npy in float64; more than 64 MB: a fixed, seeded sample of the patients")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and per-kernel split of the step, sustained rate, "
+                         "BASELINE configs 2, 3, 5 and the other legs (--no-extra skips them), CPU baseline (--no-cpu-baseline skips it)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # --gpus N is the contract: a line whose n_gpus differs from it must never be printed (verdict r5 item 7).  Under a launcher
     # (torch.distributed.run's environment) N must equal WORLD_SIZE.  Without one and N > 1 this process starts the N ranks ITSELF --
@@ -755,31 +814,38 @@ def main():
             import torch.distributed as dist
             dist.barrier()
 
-    # the warm-up steps run with events around every launch: they say which kernel dominates the step
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    for _ in range(args.warmup):
-        step()
-    ctx.synchronize()
-    torch.cuda.synchronize()
-    prof_w = ctx.profile_read() if args.warmup > 0 else {}
-    ctx.profile_enable(False)
-    if not prof_w:
-        # --warmup 0: the dominant kernel is still MEASURED, by one untimed profiled step -- a default name would bracket the wrong
-        # kernel on look-ahead shapes (few large patients), where k_cholinv is only the retry launch that does nothing
+    if args.full:
+        # the warm-up steps run with events around every launch: they say which kernel dominates the step
         ctx.profile_reset()
         ctx.profile_enable(True)
-        step()
+        for _ in range(args.warmup):
+            step()
         ctx.synchronize()
-        prof_w = ctx.profile_read()
+        torch.cuda.synchronize()
+        prof_w = ctx.profile_read() if args.warmup > 0 else {}
         ctx.profile_enable(False)
-    tot_w = {k: v[0] for k, v in prof_w.items() if v[1] > 0}
-    dom_kernel = max(tot_w, key=tot_w.get)
-    # HIP events on the launch stream, live over the timed region, around the launches of the DOMINANT kernel only (the
-    # roofline leg): events around all seven launches of a step cost 1.6 % of it (scratch/prof_overhead.py).  The other kernels'
-    # per-step times are taken in a short pass behind the timed region (kernel_ms_per_step), with events around every launch.
-    ctx.profile_reset()
-    ctx.profile_enable(True, only=dom_kernel)
+        if not prof_w:
+            # --warmup 0: the dominant kernel is still MEASURED, by one untimed profiled step -- a default name would bracket the wrong
+            # kernel on look-ahead shapes (few large patients), where k_cholinv is only the retry launch that does nothing
+            ctx.profile_reset()
+            ctx.profile_enable(True)
+            step()
+            ctx.synchronize()
+            prof_w = ctx.profile_read()
+            ctx.profile_enable(False)
+        tot_w = {k: v[0] for k, v in prof_w.items() if v[1] > 0}
+        dom_kernel = max(tot_w, key=tot_w.get)
+        # HIP events on the launch stream, live over the timed region, around the launches of the DOMINANT kernel only (the
+        # roofline leg): events around all seven launches of a step cost 1.6 % of it (scratch/prof_overhead.py).  The other kernels'
+        # per-step times are taken in a short pass behind the timed region (kernel_ms_per_step), with events around every launch.
+        ctx.profile_reset()
+        ctx.profile_enable(True, only=dom_kernel)
+    else:
+        # a plain run: no events anywhere, the headline needs none
+        for _ in range(args.warmup):
+            step()
+        ctx.synchronize()
+        torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -789,24 +855,32 @@ def main():
     torch.cuda.synchronize()
     barrier()
     t_local = time.perf_counter() - t0
-    prof = ctx.profile_read()
-    ctx.profile_enable(False)
+    if args.full:
+        prof = ctx.profile_read()
+        ctx.profile_enable(False)
     t = aggregate_time(t_local, world)
-    # per-kernel split of a step (untimed): a few more steps with events around every launch
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    n_split = max(3, min(args.steps, 10))
-    for _ in range(n_split):
-        step()
-    ctx.synchronize()
-    prof_all = ctx.profile_read()
-    ctx.profile_enable(False)
 
+    # the last timed step's results, read before anything else runs on these buffers
     st = stat_d.cpu().numpy()
     nl = nlml_d.cpu().numpy()
+    grad = grad_d.cpu().numpy() if (args.dump_outputs or args.dump_results) else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, gids, {"nlml": nl, "grad": grad, "status": st},
+                     suffix="" if world == 1 else f"_rank{rank}", limit=DUMP_LIMIT_BYTES // world)
     assert np.all(st >= 0) and np.all(np.isfinite(nl)), "evaluation failed inside the timed region"
+    if args.full:
+        # per-kernel split of a step (untimed): a few more steps with events around every launch
+        ctx.profile_reset()
+        ctx.profile_enable(True)
+        n_split = max(3, min(args.steps, 10))
+        for _ in range(n_split):
+            step()
+        ctx.synchronize()
+        prof_all = ctx.profile_read()
+        ctx.profile_enable(False)
+
     if args.dump_results:
-        np.savez(f"{args.dump_results}.rank{rank}.npz", gids=gids, nlml=nl, gsum=grad_d.cpu().numpy().sum(axis=1), status=st)
+        np.savez(f"{args.dump_results}.rank{rank}.npz", gids=gids, nlml=nl, gsum=grad.sum(axis=1), status=st)
     # who actually ran: (rank, device index, device name, uuid, host) of every rank, gathered once outside the timed region
     props = torch.cuda.get_device_properties(local_rank)
     me = {"rank": rank, "device": local_rank, "name": props.name, "uuid": str(getattr(props, "uuid", "")),
@@ -832,28 +906,6 @@ def main():
     if rank == 0:
         total_patients = sum(r["patients"] for r in seen)
         value = total_patients * args.steps / t
-        # dominant kernel + roofline from the live HIP-event timings
-        tot = {k: v[0] for k, v in prof.items() if v[1] > 0}
-        dom = max(tot, key=tot.get)
-        avg_ms = prof[dom][0] / prof[dom][1]
-        flop, byts, bound = alg_work(dom, N, Q, D, H)
-        if bound == "mfma":
-            achieved = flop * P / (avg_ms * 1e-3) / 1e12
-            roof = {"bound": "mfma", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": achieved / FP64_PEAK_TFLOPS}
-        else:
-            achieved = byts * P / (avg_ms * 1e-3) / 1e9
-            roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS}
-        traffic, traffic_prov = pmc_traffic(dom, P, N)
-        # the HBM side of the same kernel (verdict r5 item 6): measured traffic / launch time against the 8 TB/s spec, and against the
-        # algorithmic bytes (ratio > 1 = re-reads: the left-looking history of k_cholinv)
-        roof.update({"hbm_frac": (traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                     "hbm_achieved_GBs": (traffic / (avg_ms * 1e-3) / 1e9) if traffic else None,
-                     "traffic_ratio": (traffic / (byts * P)) if traffic and byts else None})
-        roof.update({"traffic": traffic, "traffic_provenance": traffic_prov, "kernel": dom, "avg_launch_ms": avg_ms,
-                     "alg_per_patient": {"flop": flop, "bytes": byts},
-                     "kernel_ms_per_step": {k: round(v[0] / n_split, 4) for k, v in prof_all.items() if v[1] > 0},
-                     "kernel_ms_per_step_source": "%d untimed steps behind the timed region, events around every launch; avg_launch_ms: live over the timed region" % n_split})
         f_alg = N ** 3 + 6 * N * N + 80 * Q * N * (N + 1) / 2
         rank_ms = [r["ms_per_step"] for r in seen]
         try:   # RCCL's version when the nccl backend carried the barrier / reductions (verdict r5 item 5)
@@ -863,11 +915,12 @@ def main():
         extra = {
             "ranks_seen": seen, "backend": backend, "nccl_version": nccl_version,
             "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms), "mean": sum(rank_ms) / len(rank_ms)},
-            "roofline": roof,
             "end_to_end": {"flop_per_eval": f_alg, "tflops": f_alg * value / world / 1e12,
                            "frac_fp64_peak": f_alg * value / world / 1e12 / FP64_PEAK_TFLOPS},
         }
-        if world == 1 and not args.no_extra and (P, N, D) == (512, 512, 24):
+        if args.full:
+            extra["roofline"] = step_roofline(prof, prof_all, n_split, N, Q, D, H, P)
+        if args.full and world == 1 and not args.no_extra and (P, N, D) == (512, 512, 24):
             # sustained rate: the timed region above is tens of milliseconds; this repeats the same step back to back for >= 2 s
             # (clocks settle under load) -- reported beside the headline, never instead of it
             try:
@@ -884,7 +937,7 @@ def main():
             except Exception as e:   # noqa: BLE001
                 extra["sustained"] = {"error": str(e)[:200]}
             extra["other_configs"] = other_configs(local_rank, args.seed)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             extra["cpu_baseline"] = cpu_baseline(D, N, Q, R, args.seed)
         what = (f"config 4 cohort: {total_patients} patients LPT-sharded over {world} GPU(s) ({P} on rank 0)" if args.scaling == "strong"
                 else f"config 4 shard: {P} patients/GPU")

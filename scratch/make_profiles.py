@@ -1,20 +1,21 @@
-"""Regenerate profiles/<round>_* from the rocprofv3 outputs of scratch/gpurun_prof.sh <tag> (gpurun_out/prof_<tag>_*).
+"""Regenerate profiles/<round>_* from the rocprofv3 outputs of scratch/profile_bench.sh <tag> (prof_out/prof_<tag>_*).
 usage: python scratch/make_profiles.py <tag> [round, default r02].  Records the git commit and the digest of the device
 sources the passes were taken from (bench.py refuses a stale traffic figure)."""
 import csv, glob, collections, json, os, shutil, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 tag = sys.argv[1]
+OUT = 'prof_out'   # scratch/profile_bench.sh writes here
 rnd = sys.argv[2] if len(sys.argv) > 2 else "r03"
-shutil.copy(glob.glob(f'gpurun_out/prof_{tag}_trace/runc/*_kernel_stats.csv')[0], f'profiles/{rnd}_kernel_stats.csv')
-open(f'profiles/{rnd}_bench_line_under_rocprof.json', 'w').write([l for l in open(f'gpurun_out/bench_{tag}_trace.log') if l.startswith('{')][-1])
+shutil.copy(glob.glob(f'{OUT}/prof_{tag}_trace/runc/*_kernel_stats.csv')[0], f'profiles/{rnd}_kernel_stats.csv')
+open(f'profiles/{rnd}_bench_line_under_rocprof.json', 'w').write([l for l in open(f'{OUT}/bench_{tag}_trace.log') if l.startswith('{')][-1])
 try:
-    open(f'profiles/{rnd}_bench_line.json', 'w').write([l for l in open(f'gpurun_out/bench_{tag}_plain.log') if l.startswith('{')][-1])
+    open(f'profiles/{rnd}_bench_line.json', 'w').write([l for l in open(f'{OUT}/bench_{tag}_plain.log') if l.startswith('{')][-1])
 except OSError:
     pass
 # steady-state per-kernel durations from the kernel trace itself: the --stats summary averages the cold launches in (round 2: max
 # 1.65 ms vs min 1.36 ms for k_cholinv), so the warm-up launches of every kernel are dropped here and the median is reported too
-WARM = int(os.environ.get("PROFILE_WARMUP_LAUNCHES", "3"))   # = --warmup of the traced bench command (scratch/gpurun_prof.sh)
-tr = glob.glob(f'gpurun_out/prof_{tag}_trace/runc/*_kernel_trace.csv')
+WARM = int(os.environ.get("PROFILE_WARMUP_LAUNCHES", "3"))   # = --warmup of the traced bench command (scratch/profile_bench.sh)
+tr = glob.glob(f'{OUT}/prof_{tag}_trace/runc/*_kernel_trace.csv')
 if tr:
     per = collections.defaultdict(list)
     for r in csv.DictReader(open(tr[0])):
@@ -28,7 +29,7 @@ if tr:
             f.write(f'"{k}",{len(d)},{len(v) - len(d)},{d[len(d) // 2]},{sum(d) / len(d):.1f},{d[0]},{d[-1]}\n')
 out = {}
 for t in ('fetch', 'write', 'mfma', 'sq'):
-    p = glob.glob(f'gpurun_out/prof_{tag}_{t}/runc/*_counter_collection.csv')[0]
+    p = glob.glob(f'{OUT}/prof_{tag}_{t}/runc/*_counter_collection.csv')[0]
     d = collections.defaultdict(lambda: collections.defaultdict(list))
     for r in csv.DictReader(open(p)):
         k = r['Kernel_Name']
@@ -52,10 +53,10 @@ for k, v in out.items():
             "valu_wave_instructions": v['SQ_INSTS_VALU']['mean_per_launch'],
             "valu_issue_frac_of_1024_simds": v['SQ_INSTS_VALU']['mean_per_launch'] * 4 / (1024 * cyc),
             "wait_any_frac_of_wave_cycles": v['SQ_WAIT_ANY']['mean_per_launch'] / v['SQ_WAVE_CYCLES']['mean_per_launch'] if 'SQ_WAVE_CYCLES' in v else None})
-# round 6: other shapes (scratch/gpurun_prof.sh): steady-state launch time from the kernel trace + FETCH_SIZE / WRITE_SIZE per launch, per kernel
+# round 6: other shapes (scratch/profile_bench.sh): steady-state launch time from the kernel trace + FETCH_SIZE / WRITE_SIZE per launch, per kernel
 shapes = {}
 for name, label in (("screen", "screening_1000xN512_nlml_only"), ("cfg3", "config3_1xN2048")):
-    trs = glob.glob(f'gpurun_out/prof_{tag}_{name}_trace/runc/*_kernel_trace.csv')
+    trs = glob.glob(f'{OUT}/prof_{tag}_{name}_trace/runc/*_kernel_trace.csv')
     if not trs:
         continue
     per = collections.defaultdict(list)
@@ -63,7 +64,7 @@ for name, label in (("screen", "screening_1000xN512_nlml_only"), ("cfg3", "confi
         per[r['Kernel_Name'].split('(')[0].replace('void ', '')].append((int(r['Start_Timestamp']), int(r['End_Timestamp']) - int(r['Start_Timestamp'])))
     cnt = {}
     for t in ('fetch', 'write'):
-        ps = glob.glob(f'gpurun_out/prof_{tag}_{name}_{t}/runc/*_counter_collection.csv')
+        ps = glob.glob(f'{OUT}/prof_{tag}_{name}_{t}/runc/*_counter_collection.csv')
         if not ps:
             continue
         d = collections.defaultdict(list)
@@ -81,7 +82,7 @@ for name, label in (("screen", "screening_1000xN512_nlml_only"), ("cfg3", "confi
             e.update({"fetch_bytes_raw": f, "fetch_bytes_x2_if_wide_loads": 2 * f, "write_bytes": w})
         sh[k] = e
     shapes[label] = sh
-    shutil.copy(glob.glob(f'gpurun_out/prof_{tag}_{name}_trace/runc/*_kernel_stats.csv')[0], f'profiles/{rnd}_kernel_stats_{name}.csv')
+    shutil.copy(glob.glob(f'{OUT}/prof_{tag}_{name}_trace/runc/*_kernel_stats.csv')[0], f'profiles/{rnd}_kernel_stats_{name}.csv')
 if shapes:
     out['_shapes'] = shapes
 import bench

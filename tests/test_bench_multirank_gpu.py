@@ -74,8 +74,9 @@ def test_backend_switch_and_nccl_refuses_shared_gpus(tmp_path):
     """--backend gloo forces the CPU process group; --backend nccl with two ranks on this one-GPU box must FAIL LOUDLY (exit code,
     message) instead of quietly timing two ranks on one device."""
     import torch
-    two, _ = _run(2, ["--patients", "8", "--backend", "gloo"], str(tmp_path / "g"))
+    two, _ = _run(2, ["--patients", "8", "--backend", "gloo", "--full"], str(tmp_path / "g"))
     assert two["backend"] == "gloo"
+    assert two["roofline"]["kernel"] and two["roofline"]["kernel_ms_per_step"]     # --full's profiling path with two ranks
     if torch.cuda.device_count() >= 2:
         pytest.skip("needs a box with fewer GPUs than ranks")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -96,7 +97,7 @@ def test_one_rank_under_torchrun_runs_the_rccl_path(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     dump = str(tmp_path / "tr")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--patients", "16", "--dump-results", dump] + COMMON
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--patients", "16", "--dump-results", dump, "--full"] + COMMON
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -104,6 +105,7 @@ def test_one_rank_under_torchrun_runs_the_rccl_path(tmp_path):
     line = json.loads(lines[0])
     assert line["backend"] == "nccl" and line["n_gpus"] == 1 and len(line["ranks_seen"]) == 1
     assert line["nccl_version"] and line["nccl_version"][0].isdigit()          # RCCL reported its version: it was really initialised
+    assert line["roofline"]["kernel"] and line["roofline"]["kernel_ms_per_step"]  # --full's profiling path under the nccl branch
     assert plain["backend"] == "none" and plain["nccl_version"] is None
     d = np.load(f"{dump}.rank0.npz")
     for g, nl, gs, st in zip(d["gids"], d["nlml"], d["gsum"], d["status"]):
@@ -120,3 +122,24 @@ def test_gpus_flag_must_match_the_launcher(tmp_path):
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert "refusing to print a line" in r.stderr
+
+
+def test_dump_outputs_plain_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's per-patient results as float64 .npy: the same bits with and without --full and equal
+    to --dump-results of the same run.  A plain line carries the headline only; --full adds the roofline and per-kernel split."""
+    plain, res = _run(1, ["--patients", "16", "--dump-outputs", str(tmp_path / "plain")], str(tmp_path / "plain_res"))
+    full, _ = _run(1, ["--patients", "16", "--full", "--dump-outputs", str(tmp_path / "full")], str(tmp_path / "full_res"))
+    assert "roofline" not in plain and "sustained" not in plain and "cpu_baseline" not in plain
+    assert full["roofline"]["kernel"] and full["roofline"]["kernel_ms_per_step"]
+    for line in (plain, full):
+        assert line["steps"] == 2 and line["unit"] == "evals/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert line["ms_per_step"] > 0 and abs(line["value"] - 16 * 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"]
+    out = {}
+    for d in ("plain", "full"):
+        out[d] = {k: np.load(tmp_path / d / f"{k}.npy") for k in ("patient_ids", "nlml", "grad", "status")}
+        assert all(a.dtype == np.float64 and a.shape[0] == 16 for a in out[d].values())
+    for k in out["plain"]:
+        assert np.array_equal(out["plain"][k], out["full"][k]), k
+    gsum = out["plain"]["grad"].sum(axis=1)
+    for i, g in enumerate(out["plain"]["patient_ids"]):
+        assert (out["plain"]["nlml"][i], gsum[i], out["plain"]["status"][i]) == res[int(g)]

@@ -212,6 +212,30 @@ def test_bench_gpus_flag_means_something(capsys):
     assert cmd[-4:] == ["--gpus", "4", "--steps", "3"] and os.path.basename(cmd[-5]) == "bench.py"
 
 
+def test_bench_dump_outputs_float64_and_capped(tmp_path):
+    """bench.dump_outputs (--dump-outputs): every array as float64 .npy beside the patients' global ids; above the cap a fixed sample of
+    whole patient rows (the same on every call), and the files stay within the cap."""
+    bench = _load_bench()
+    rng = np.random.default_rng(1)
+    gids = np.arange(100, 400)
+    arrays = {"nlml": rng.normal(size=300), "grad": rng.normal(size=(300, 50)), "status": np.zeros(300, np.int32)}
+    bench.dump_outputs(str(tmp_path / "all"), gids, arrays)
+    for name in ("nlml", "grad", "status", "patient_ids"):
+        a = np.load(tmp_path / "all" / f"{name}.npy")
+        assert a.dtype == np.float64
+        assert np.array_equal(a, gids if name == "patient_ids" else arrays[name])
+    limit = 40000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), gids, arrays, suffix="_rank1", limit=limit)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= limit
+    ids = np.load(tmp_path / "s1" / "patient_ids_rank1.npy")
+    assert 0 < len(ids) < 300 and np.all(np.diff(ids) > 0)
+    assert np.array_equal(ids, np.load(tmp_path / "s2" / "patient_ids_rank1.npy"))
+    rows = (ids - 100).astype(int)
+    assert np.array_equal(np.load(tmp_path / "s1" / "grad_rank1.npy"), arrays["grad"][rows])
+    assert np.array_equal(np.load(tmp_path / "s1" / "nlml_rank1.npy"), arrays["nlml"][rows])
+
+
 def test_bench_gpus_2_without_a_launcher_never_prints_an_n_gpus_1_line():
     """`python bench.py --gpus 2` with no launcher environment (here: no GPU either, so the ranks fail): whatever happens, no JSON line
     with n_gpus != 2 comes out and the exit status is not 0."""
