@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 3: medgp_reserve_plan, medgp_alloc_stats (round 6) */
+int medgp_abi_version(void);   /* 4: medgp_posterior_batch (3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -218,6 +218,21 @@ int medgp_factor_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const d
  * observation) pairs of a patient, each uploaded as its own slot (a subset of the patient's observations). */
 int medgp_fit_predict_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta,
                             const int32_t *meta2, const float *t2, float *mean, float *var, int32_t *status);
+
+/* Batched posterior with the per-covariate decomposition of the mean.  nbatch patients, patient b = slots[b] with hypers
+ * theta[b*H..), test points offsets[b] .. offsets[b+1) of meta2 / t2 (offsets has nbatch + 1 entries, offsets[0] == 0,
+ * non-decreasing; an empty range is allowed).  For every test point j: mean[j], var[j] as GP_Regression::predict, and
+ * (parts != NULL) parts[j*D + d] = the part of mean[j] carried by the training observations of covariate d, as
+ * GP_Regression::parsed_predict (zero mean function: the D parts of a point sum to its mean; D = 1 for SE / SM).
+ *   ref: core/gp_regression.cpp:216-320 (parsed_predict), :128-214 (predict),
+ *        kernel/c_kernel_LMC_SM.cpp:329-372 (cross Gram), :122-150 (self diagonal)
+ * status[b] as medgp_fit_predict_batch; the points of a patient with status < 0 get NaN mean, var and parts.  One factorisation
+ * per patient, then the points in tiles of 64 per workgroup (forward solve on fp64 MFMA).  A point's outputs do not depend on
+ * the other points of the call, their order, or how the call is cut into launches (work memory per launch:
+ * MEDGP_POSTERIOR_BUDGET_GB, default 2).  meta2 may be NULL for SE / SM.  Like medgp_fit_predict_batch, a call whose
+ * per-entry matrices exceed the memory budget fails with MEDGP_ERR_CAPACITY.  All pointers are HOST memory. */
+int medgp_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                          const int32_t *meta2, const float *t2, float *mean, float *var, float *parts, int32_t *status);
 
 /* Cohort statistics, the step after training: for each of nseries independent sample series
  * (series s = data[off[s] .. off[s] + cnt[s])) the Gaussian kernel density estimate with Silverman's bandwidth evaluated AT the

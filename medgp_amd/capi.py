@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at",
 ]
 
@@ -92,6 +92,7 @@ def load():
     lib.medgp_last_plan.argtypes = [vp, C.c_int, i32p, i32p, i32p]
     lib.medgp_fit_predict.argtypes = [vp, C.c_int, dp, C.c_int, i32p, fp, fp, fp, i32p]
     lib.medgp_fit_predict_batch.argtypes = [vp, C.c_int, i32p, dp, i32p, fp, fp, fp, i32p]
+    lib.medgp_posterior_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, i32p]
     lib.medgp_synchronize.argtypes = [vp]
     lib.medgp_profile_enable.argtypes = [vp, C.c_int]
     lib.medgp_profile_num_kernels.restype = C.c_int
@@ -367,6 +368,50 @@ class Context:
                                                     _ptr(meta2, C.c_int32), _ptr(t2, C.c_float), _ptr(mean, C.c_float),
                                                     _ptr(var, C.c_float), _ptr(st, C.c_int32)))
         return mean, var, st
+
+    def posterior(self, slots, theta, meta2_list, t2_list, parts=True):
+        """medgp_posterior_batch: GP_Regression::predict / parsed_predict for many points of many patients in one call.
+        slots [nbatch], theta [nbatch, H]; t2_list: one array of test times per patient (may be empty), meta2_list: one array of
+        test covariates per patient (None for SE / SM).  Returns ([(mean[m], var[m], parts[m, D] or None) per patient], status)."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        nb = slots.shape[0]
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.size != nb * self.H:
+            raise ValueError(f"theta has {theta.size} values, expected {nb} x {self.H}")
+        theta = theta.reshape(nb, self.H)
+        if len(t2_list) != nb:
+            raise ValueError(f"{len(t2_list)} test-point arrays for {nb} patients")
+        ts = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in t2_list]
+        if meta2_list is None:
+            if self.kernel_index == KERNEL_LMC_SM:
+                raise ValueError("meta2_list is required for the multi-output kernel")
+            ms = [np.zeros(x.shape[0], dtype=np.int32) for x in ts]
+        else:
+            if len(meta2_list) != nb:
+                raise ValueError(f"{len(meta2_list)} covariate arrays for {nb} patients")
+            ms = [np.ascontiguousarray(x, dtype=np.int32).ravel() for x in meta2_list]
+            for b, (m, x) in enumerate(zip(ms, ts)):
+                if m.shape[0] != x.shape[0]:
+                    raise ValueError(f"patient {b}: {m.shape[0]} covariates for {x.shape[0]} test times")
+        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum(cnt)
+        M = int(offsets[-1])
+        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
+        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+        D = self.D if self.kernel_index == KERNEL_LMC_SM else 1
+        mean = np.empty(max(M, 1), dtype=np.float32)
+        var = np.empty(max(M, 1), dtype=np.float32)
+        pr = np.empty((max(M, 1), D), dtype=np.float32) if parts else None
+        st = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_posterior_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
+                                                  offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
+                                                  _ptr(mean, C.c_float), _ptr(var, C.c_float), _ptr(pr, C.c_float), _ptr(st, C.c_int32)))
+        out = []
+        for b in range(nb):
+            a, e = int(offsets[b]), int(offsets[b + 1])
+            out.append((mean[a:e].copy(), var[a:e].copy(), pr[a:e].copy() if parts else None))
+        return out, st
 
     def synchronize(self):
         self._chk(self._lib.medgp_synchronize(self._h))

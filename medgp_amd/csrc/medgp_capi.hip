@@ -11,6 +11,7 @@
 #include "kernels_wgrad.h"
 #include "kernels_io.h"
 #include "kernels_cohort.h"
+#include "kernels_posterior.h"
 
 #include <algorithm>
 #include <chrono>
@@ -24,8 +25,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -174,6 +175,14 @@ struct medgp_ctx {
     int *d_meta2 = nullptr;
     float *d_mean = nullptr, *d_var = nullptr;
     int pred_cap = 0;
+    // medgp_posterior_batch buffers (own blocks, replaced when a call outgrows them; freed by free_all): per-point inputs / outputs of
+    // the call, the tile table, and the work rows of one launch chunk (at most posterior_budget bytes unless one tile needs more)
+    double *d_post_t2 = nullptr, *d_post_work = nullptr;
+    int *d_post_m2 = nullptr;
+    float *d_post_mean = nullptr, *d_post_var = nullptr, *d_post_parts = nullptr;
+    PostTile *d_post_tiles = nullptr;
+    size_t post_cap_pts = 0, post_cap_m2 = 0, post_cap_mean = 0, post_cap_var = 0, post_cap_parts = 0, post_cap_tiles = 0, post_cap_work = 0;   // bytes
+    size_t posterior_budget = (size_t)2 << 30;   // MEDGP_POSTERIOR_BUDGET_GB
     // profiling
     bool profiling = false;
     int profile_only = -1;    // >= 0: only launches of this kernel id are bracketed (medgp_profile_enable(ctx, 2 + id))
@@ -243,6 +252,12 @@ void free_all(medgp_ctx *c) {
     for (void *p : c->retired) (void)hipFree(p);
     c->retired.clear();
     c->retired_bytes = 0;
+    for (void **p : {(void **)&c->d_post_t2, (void **)&c->d_post_work, (void **)&c->d_post_m2, (void **)&c->d_post_mean, (void **)&c->d_post_var,
+                     (void **)&c->d_post_parts, (void **)&c->d_post_tiles}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    c->post_cap_pts = c->post_cap_m2 = c->post_cap_mean = c->post_cap_var = c->post_cap_parts = c->post_cap_tiles = c->post_cap_work = 0;
 }
 
 int num_cov(int kidx, int Q, int D, int R) {
@@ -920,7 +935,7 @@ int run_pipeline(medgp_ctx *c, int nbatch, int max_n, const double *theta_dev, i
 
 extern "C" {
 
-int medgp_abi_version(void) { return 3; }
+int medgp_abi_version(void) { return 4; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -964,6 +979,7 @@ int medgp_create(medgp_ctx **out, int device, int kernel_index, int Q, int D, in
     { const char *e = getenv("MEDGP_SCREEN_LANES"); if (e && atoi(e) >= 1) c->screen_lanes = std::min(2, atoi(e)); }
     { const char *e = getenv("MEDGP_SCREEN_WORK"); if (e && atoll(e) > 0) c->screen_work = atoll(e); }
     { const char *e = getenv("MEDGP_SCREEN_BUDGET_GB"); if (e && atof(e) > 0) c->screen_budget = (size_t)(atof(e) * 1073741824.0); }
+    { const char *e = getenv("MEDGP_POSTERIOR_BUDGET_GB"); if (e && atof(e) > 0) c->posterior_budget = (size_t)(atof(e) * 1073741824.0); }
     for (int i = 0; i < kAuxStreams; i++) {
         (void)hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking);
         (void)hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming);
@@ -1865,6 +1881,136 @@ int medgp_fit_predict_batch(medgp_ctx *c, int nbatch, const int32_t *slots, cons
                             const float *t2, float *mean, float *var, int32_t *status) {
     if (c && nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
     return fit_predict_impl(c, nbatch, slots, theta, 1, meta2, t2, mean, var, status);
+}
+
+namespace {
+// a device block of at least `bytes` in *p (capacity *cap): replaced when too small, after the queued work that may still read it
+int post_buf(medgp_ctx *c, void **p, size_t *cap, size_t bytes) {
+    if (bytes <= *cap && *p) return MEDGP_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (*p) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(*p);
+        *p = nullptr;
+        *cap = 0;
+    }
+    const size_t want = std::max<size_t>(bytes, 256);
+    hipError_t e = hipMalloc(p, want);
+    c->alloc_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    c->alloc_calls++;
+    if (e != hipSuccess) { *p = nullptr; return fail(c, MEDGP_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e)); }
+    *cap = want;
+    return MEDGP_OK;
+}
+
+void launch_posterior(medgp_ctx *c, const MedgpDev &V, int ntiles, const PostTile *tiles, size_t stride, int with_parts, int parts_lds) {
+    const dim3 tg(ntiles), tb(256);
+    const size_t lds = parts_lds ? sizeof(double) * 64 * V.D : 0;
+#define MEDGP_POST(QQ) hipLaunchKernelGGL(k_posterior<QQ>, tg, tb, lds, c->stream, V, tiles, c->d_post_m2, c->d_post_t2, c->d_post_work, stride, \
+                                          with_parts, parts_lds, c->d_post_mean, c->d_post_var, c->d_post_parts)
+    switch (V.Q) {
+    case 1: MEDGP_POST(1); break;
+    case 2: MEDGP_POST(2); break;
+    case 3: MEDGP_POST(3); break;
+    case 4: MEDGP_POST(4); break;
+    case 5: MEDGP_POST(5); break;
+    case 6: MEDGP_POST(6); break;
+    case 7: MEDGP_POST(7); break;
+    case 8: MEDGP_POST(8); break;
+    default: MEDGP_POST(0); break;   // Q > 8: generic component loop
+    }
+#undef MEDGP_POST
+}
+}  // namespace
+
+int medgp_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                          const int32_t *meta2, const float *t2, float *mean, float *var, float *parts, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
+    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
+    if (nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
+    if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
+    for (int b = 0; b < nbatch; b++)
+        if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
+    const int64_t M = offsets[nbatch];
+    if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
+    if (M > 0 && (!t2 || !mean || !var)) return fail(c, MEDGP_ERR_ARG, "t2 / mean / var is NULL");
+    if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
+    const int D = c->D;
+    std::vector<double> ht2(M);
+    std::vector<int> hm2(M, 0);
+    for (int64_t j = 0; j < M; j++) {
+        ht2[j] = (double)t2[j];
+        if (meta2 && c->kidx == MEDGP_KERNEL_LMC_SM) {
+            if (meta2[j] < 0 || meta2[j] >= D) return fail(c, MEDGP_ERR_ARG, "meta2[%lld] = %d outside [0, %d)", (long long)j, meta2[j], D);
+            hm2[j] = meta2[j];
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    int max_n = 0, rc;
+    // the parts, like mean and var, are invariant under a permutation of the training observations: the grouped copy serves
+    if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
+    const bool with_parts = parts != nullptr;
+    const int parts_lds = D <= POST_PARTS_LDS_MAX_D;
+    const size_t Mz = (size_t)std::max<int64_t>(M, 1);
+    if ((rc = post_buf(c, (void **)&c->d_post_t2, &c->post_cap_pts, Mz * sizeof(double)))) return rc;
+    if ((rc = post_buf(c, (void **)&c->d_post_m2, &c->post_cap_m2, Mz * sizeof(int)))) return rc;
+    if ((rc = post_buf(c, (void **)&c->d_post_mean, &c->post_cap_mean, Mz * sizeof(float)))) return rc;
+    if ((rc = post_buf(c, (void **)&c->d_post_var, &c->post_cap_var, Mz * sizeof(float)))) return rc;
+    if (with_parts && (rc = post_buf(c, (void **)&c->d_post_parts, &c->post_cap_parts, Mz * D * sizeof(float)))) return rc;
+    // tile table, per size class (entries of a class share the view's leading dimension, hence the work-row stride), and chunks
+    // of consecutive tiles of one class whose work rows stay within the budget
+    struct Chunk { const SizeClass *k; int t0, nt; size_t stride; };
+    std::vector<PostTile> tiles;
+    std::vector<Chunk> chunks;
+    size_t work_need = 0;
+    for (const SizeClass &k : c->plan.cls) {
+        const int t_begin = (int)tiles.size();
+        for (int i = k.b0; i < k.b0 + k.count; i++) {
+            const int b = c->plan.order[i];
+            for (int64_t p = offsets[b]; p < offsets[b + 1]; p += POST_TW)
+                tiles.push_back({i - k.b0, (int)p, (int)std::min<int64_t>(POST_TW, offsets[b + 1] - p), 0});
+        }
+        const size_t stride = (size_t)k.ld * 64 + ((with_parts && !parts_lds) ? (size_t)D * 64 : 0);   // doubles per tile
+        const int per_chunk = (int)std::max<size_t>(1, c->posterior_budget / (stride * sizeof(double)));
+        for (int t0 = t_begin; t0 < (int)tiles.size(); t0 += per_chunk) {
+            const int nt = std::min(per_chunk, (int)tiles.size() - t0);
+            chunks.push_back({&k, t0, nt, stride});
+            work_need = std::max(work_need, (size_t)nt * stride * sizeof(double));
+        }
+    }
+    if (!tiles.empty()) {
+        if ((rc = post_buf(c, (void **)&c->d_post_tiles, &c->post_cap_tiles, tiles.size() * sizeof(PostTile)))) return rc;
+        if ((rc = post_buf(c, (void **)&c->d_post_work, &c->post_cap_work, work_need))) return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
+    if (M > 0) {
+        HIPCHK(c, hipMemcpyAsync(c->d_post_t2, ht2.data(), sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_post_m2, hm2.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_post_tiles, tiles.data(), sizeof(PostTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
+    }
+    // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
+    if ((rc = run_pipeline(c, nbatch, max_n, c->d_theta, 0, false, 1, nullptr, nullptr, nullptr, true, true))) return rc;
+    if (with_parts && M > 0)
+        for (const SizeClass &k : c->plan.cls) {   // (behind the join of the classes' chains)
+            Launcher l(c, KID_ALPHA);
+            hipLaunchKernelGGL(k_alpha, dim3(k.count), dim3(256), 0, c->stream, class_view(c, c->plan, k));
+        }
+    for (const Chunk &ch : chunks) {   // chunks reuse the work rows in stream order
+        Launcher l(c, KID_POSTERIOR);
+        launch_posterior(c, class_view(c, c->plan, *ch.k), ch.nt, c->d_post_tiles + ch.t0, ch.stride, with_parts ? 1 : 0, parts_lds);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (M > 0) {
+        HIPCHK(c, hipMemcpyAsync(mean, c->d_post_mean, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(var, c->d_post_var, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        if (with_parts) HIPCHK(c, hipMemcpyAsync(parts, c->d_post_parts, sizeof(float) * M * D, hipMemcpyDeviceToHost, c->stream));
+    }
+    std::vector<int> st(nbatch, 0);
+    if (status) HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (status) for (int i = 0; i < nbatch; i++) status[c->plan.order[i]] = st[i];   // internal order -> the caller's
+    return MEDGP_OK;
 }
 
 #ifdef MEDGP_STAMPS
