@@ -975,6 +975,7 @@ int medgp_create(medgp_ctx **out, int device, int kernel_index, int Q, int D, in
     { const char *e = getenv("MEDGP_NO_CLASSES"); c->no_classes = e ? atoi(e) : 0; }
     { const char *e = getenv("MEDGP_WGRAD_DEEP"); c->wgrad_deep = e ? std::max(1, atoi(e)) : -1; }
     { const char *e = getenv("MEDGP_DEBUG_FAIL_ATTEMPTS"); c->dbg_fail = e ? atoi(e) : 0; }
+    { const char *e = getenv("MEDGP_V0"); c->use_v0 = e && e[0] == '1'; }
     { const char *e = getenv("MEDGP_MEM_BUDGET_GB"); if (e && atof(e) > 0) c->mem_budget = (size_t)(atof(e) * 1073741824.0); }
     { const char *e = getenv("MEDGP_SCREEN_LANES"); if (e && atoi(e) >= 1) c->screen_lanes = std::min(2, atoi(e)); }
     { const char *e = getenv("MEDGP_SCREEN_WORK"); if (e && atoll(e) > 0) c->screen_work = atoll(e); }

@@ -8,7 +8,7 @@ pytestmark = pytest.mark.gpu
 
 import medgp_amd
 from medgp_amd import synth
-from posterior_ref import restate
+from posterior_ref import check_posterior, restate
 
 
 def make_ctx(kidx, Q, D, R, pts):
@@ -27,21 +27,11 @@ def grid(seed, D, t, m):
 
 
 def check(kidx, Q, D, R, pt, th, m2, t2, mean, var, parts):
+    """two fp32 ulps of the restatement per element, parts summing to the mean, var >= sigma^2 (posterior_ref.check_posterior)"""
     m, t, y = pt
     multi = kidx == 7
-    rm, rv, rp = restate(kidx, Q, D, R, m if multi else None, t, y, th, m2 if multi else None, t2)
-    if t2.shape[0] == 0:
-        assert mean.shape == (0,) and var.shape == (0,)
-        return
-    ms, vs = np.abs(rm).max(), np.abs(rv).max()
-    np.testing.assert_allclose(mean, rm, rtol=1e-5, atol=1e-6 * max(ms, 1e-3))
-    np.testing.assert_allclose(var, rv, rtol=1e-5, atol=1e-6 * vs)
-    if parts is not None:
-        ps = np.abs(rp).max()
-        assert parts.shape == rp.shape
-        assert np.abs(parts - rp).max() <= 1e-5 * ps
-        # the parts of a point sum to its mean, to float rounding
-        assert np.all(np.abs(parts.astype(np.float64).sum(axis=1) - mean) <= 4e-7 * (D + 1) * (ps + np.abs(mean)))
+    ref = restate(kidx, Q, D, R, m if multi else None, t, y, th, m2 if multi else None, t2)
+    check_posterior(kidx, D, th, m2 if multi else None, ref, mean, var, parts)
 
 
 @pytest.mark.parametrize("D,Q,R,sizes,npts", [
