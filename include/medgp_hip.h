@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 4: medgp_posterior_batch (3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 5: medgp_posterior_joint_batch (4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -241,6 +241,33 @@ int medgp_fit_predict_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, co
  * per-entry matrices exceed the memory budget fails with MEDGP_ERR_CAPACITY.  All pointers are HOST memory. */
 int medgp_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
                           const int32_t *meta2, const float *t2, float *mean, float *var, float *parts, int32_t *status);
+
+/* Joint posterior of every patient's test points: the covariance of the predictive distribution and sample paths from it.
+ * nbatch, slots, theta, offsets, meta2, t2, mean, var, status exactly as medgp_posterior_batch (mean and var are that call's,
+ * bit for bit: the same code path).  With m_b = offsets[b+1] - offsets[b]:
+ *   cov     (may be NULL) patient b's block starts at cov + sum_{a<b} m_a^2: m_b x m_b, row-major,
+ *             C = K** - V^T V + diag(sigma^2_{meta2}),  V = L^-1 K*,
+ *           the predictive covariance of y* (noise included, once: diag(C) is `var`, as GP_Regression::predict adds it,
+ *           ref: core/gp_regression.cpp:128-214); both triangles written, exactly symmetric.
+ *   eps     nsamp standard normals per test point SUPPLIED BY THE CALLER, eps[(offsets[b] + i)*nsamp + s] (the library draws
+ *           nothing: a call depends on its arguments alone)
+ *   samples same layout, float: samples[(offsets[b] + i)*nsamp + s] = mean_i + sum_{j<=i} Lc[i][j] eps[j][s], Lc the lower
+ *           Cholesky factor of C in the caller's order of the points: sample path s of patient b, consistent across times
+ *           and covariates.
+ * nsamp == 0 (eps, samples NULL): covariance only, C is not factored.  cov == NULL: samples only.  Neither: MEDGP_ERR_ARG.
+ * cov_status[b] (may be NULL): 0 ok; -1 the factorisation of C met a pivot <= 0 or NaN (LAPACK's rule; there is no jitter
+ * loop, C >= sigma^2_min I in exact arithmetic): that patient's samples are NaN, its cov is still written; also -1 for a
+ * patient with status[b] < 0, whose outputs are all NaN.  m_b == 0 is allowed.  A patient's outputs do not depend on the other
+ * patients of the call, their order, or how the call is cut into launches.  The reference has no such output (its predict
+ * returns marginals); the definition is the fp64 restatement of tests/posterior_joint_ref.py.
+ * Memory: V of all tiles of a patient (ld x m_b doubles), C (m_b rounded up to 64, squared, doubles) and its float block are
+ * resident together; the call is cut into launches of whole patients within MEDGP_POSTERIOR_BUDGET_GB (default 2), a single
+ * patient beyond it fails with MEDGP_ERR_CAPACITY, as does a call whose per-entry matrices exceed the memory budget.  C is
+ * factored by one workgroup per patient: made for cohorts of patients with up to a few thousand points each.
+ * All pointers are HOST memory. */
+int medgp_posterior_joint_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                                const int32_t *meta2, const float *t2, int nsamp, const double *eps, float *mean, float *var,
+                                float *cov, float *samples, int32_t *status, int32_t *cov_status);
 
 /* Cohort statistics, the step after training: for each of nseries independent sample series
  * (series s = data[off[s] .. off[s] + cnt[s])) the Gaussian kernel density estimate with Silverman's bandwidth evaluated AT the

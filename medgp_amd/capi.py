@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at",
 ]
 
@@ -93,6 +93,7 @@ def load():
     lib.medgp_fit_predict.argtypes = [vp, C.c_int, dp, C.c_int, i32p, fp, fp, fp, i32p]
     lib.medgp_fit_predict_batch.argtypes = [vp, C.c_int, i32p, dp, i32p, fp, fp, fp, i32p]
     lib.medgp_posterior_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, i32p]
+    lib.medgp_posterior_joint_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, fp, fp, fp, fp, i32p, i32p]
     lib.medgp_synchronize.argtypes = [vp]
     lib.medgp_profile_enable.argtypes = [vp, C.c_int]
     lib.medgp_profile_num_kernels.restype = C.c_int
@@ -369,10 +370,8 @@ class Context:
                                                     _ptr(var, C.c_float), _ptr(st, C.c_int32)))
         return mean, var, st
 
-    def posterior(self, slots, theta, meta2_list, t2_list, parts=True):
-        """medgp_posterior_batch: GP_Regression::predict / parsed_predict for many points of many patients in one call.
-        slots [nbatch], theta [nbatch, H]; t2_list: one array of test times per patient (may be empty), meta2_list: one array of
-        test covariates per patient (None for SE / SM).  Returns ([(mean[m], var[m], parts[m, D] or None) per patient], status)."""
+    def _posterior_args(self, slots, theta, meta2_list, t2_list):
+        """the argument checks of posterior / posterior_joint: (slots, theta [nbatch, H], covariate arrays, time arrays)"""
         slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
         nb = slots.shape[0]
         theta = np.ascontiguousarray(theta, dtype=np.float64)
@@ -393,6 +392,14 @@ class Context:
             for b, (m, x) in enumerate(zip(ms, ts)):
                 if m.shape[0] != x.shape[0]:
                     raise ValueError(f"patient {b}: {m.shape[0]} covariates for {x.shape[0]} test times")
+        return slots, theta, ms, ts
+
+    def posterior(self, slots, theta, meta2_list, t2_list, parts=True):
+        """medgp_posterior_batch: GP_Regression::predict / parsed_predict for many points of many patients in one call.
+        slots [nbatch], theta [nbatch, H]; t2_list: one array of test times per patient (may be empty), meta2_list: one array of
+        test covariates per patient (None for SE / SM).  Returns ([(mean[m], var[m], parts[m, D] or None) per patient], status)."""
+        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
+        nb = slots.shape[0]
         cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
         offsets = np.zeros(nb + 1, dtype=np.int64)
         offsets[1:] = np.cumsum(cnt)
@@ -412,6 +419,60 @@ class Context:
             a, e = int(offsets[b]), int(offsets[b + 1])
             out.append((mean[a:e].copy(), var[a:e].copy(), pr[a:e].copy() if parts else None))
         return out, st
+
+    def posterior_joint(self, slots, theta, meta2_list, t2_list, eps_list=None, cov=True):
+        """medgp_posterior_joint_batch: the joint predictive distribution of every patient's test points.  Arguments as
+        posterior(); eps_list: one (m_b, nsamp) array of standard normals per patient (the caller's draws; the same nsamp for
+        all), or None for the covariance only; cov=False: samples only.  Returns ([(mean[m], var[m], cov[m, m] or None,
+        samples[m, nsamp] or None) per patient], status, cov_status): cov = K** - V^T V + diag(sigma^2), whose diagonal is var;
+        samples[:, s] = mean + chol(cov) eps[:, s]."""
+        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
+        nb = slots.shape[0]
+        nsamp = 0
+        es = None
+        if eps_list is None:
+            if not cov:
+                raise ValueError("neither cov nor samples asked for (eps_list is None and cov is False)")
+        else:
+            if len(eps_list) != nb:
+                raise ValueError(f"{len(eps_list)} eps arrays for {nb} patients")
+            es = [np.ascontiguousarray(x, dtype=np.float64) for x in eps_list]
+            for b, (e, x) in enumerate(zip(es, ts)):
+                if e.ndim != 2 or e.shape[0] != x.shape[0]:
+                    raise ValueError(f"patient {b}: eps of shape {e.shape} for {x.shape[0]} test points, expected (m, nsamp)")
+            widths = {e.shape[1] for e in es}
+            if len(widths) != 1:
+                raise ValueError(f"eps arrays of different nsamp: {sorted(widths)}")
+            nsamp = widths.pop()
+            if nsamp < 1:
+                raise ValueError("eps arrays with nsamp = 0: pass eps_list=None for the covariance only")
+        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum(cnt)
+        coff = np.zeros(nb + 1, dtype=np.int64)
+        coff[1:] = np.cumsum(cnt * cnt)
+        M = int(offsets[-1])
+        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
+        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+        mean = np.empty(max(M, 1), dtype=np.float32)
+        var = np.empty(max(M, 1), dtype=np.float32)
+        cv = np.empty(max(int(coff[-1]), 1), dtype=np.float32) if cov else None
+        eps = sm = None
+        if nsamp:
+            eps = np.ascontiguousarray(np.concatenate(es, axis=0) if M else np.zeros((1, nsamp)), dtype=np.float64)
+            sm = np.empty((max(M, 1), nsamp), dtype=np.float32)
+        st = np.empty(nb, dtype=np.int32)
+        cst = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_posterior_joint_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
+                                                        offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
+                                                        int(nsamp), _ptr(eps, C.c_double), _ptr(mean, C.c_float), _ptr(var, C.c_float),
+                                                        _ptr(cv, C.c_float), _ptr(sm, C.c_float), _ptr(st, C.c_int32), _ptr(cst, C.c_int32)))
+        out = []
+        for b in range(nb):
+            a, e, m = int(offsets[b]), int(offsets[b + 1]), int(cnt[b])
+            out.append((mean[a:e].copy(), var[a:e].copy(), cv[int(coff[b]):int(coff[b + 1])].reshape(m, m).copy() if cov else None,
+                        sm[a:e].copy() if nsamp else None))
+        return out, st, cst
 
     def synchronize(self):
         self._chk(self._lib.medgp_synchronize(self._h))

@@ -12,6 +12,7 @@
 #include "kernels_io.h"
 #include "kernels_cohort.h"
 #include "kernels_posterior.h"
+#include "kernels_posterior_joint.h"
 
 #include <algorithm>
 #include <chrono>
@@ -25,8 +26,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -183,6 +184,14 @@ struct medgp_ctx {
     PostTile *d_post_tiles = nullptr;
     size_t post_cap_pts = 0, post_cap_m2 = 0, post_cap_mean = 0, post_cap_var = 0, post_cap_parts = 0, post_cap_tiles = 0, post_cap_work = 0;   // bytes
     size_t posterior_budget = (size_t)2 << 30;   // MEDGP_POSTERIOR_BUDGET_GB
+    // medgp_posterior_joint_batch buffers (same rules): the patient / tile-pair / row-block tables of the call, C and the float
+    // covariance blocks of one launch chunk, the call's eps and samples, cov_status
+    JointPat *d_joint_pats = nullptr;
+    JointTile *d_joint_pairs = nullptr, *d_joint_blks = nullptr;
+    double *d_joint_C = nullptr, *d_joint_eps = nullptr;
+    float *d_joint_cov = nullptr, *d_joint_samp = nullptr;
+    int *d_joint_cstat = nullptr;
+    size_t joint_cap_pats = 0, joint_cap_pairs = 0, joint_cap_blks = 0, joint_cap_C = 0, joint_cap_eps = 0, joint_cap_cov = 0, joint_cap_samp = 0, joint_cap_cstat = 0;   // bytes
     // profiling
     bool profiling = false;
     int profile_only = -1;    // >= 0: only launches of this kernel id are bracketed (medgp_profile_enable(ctx, 2 + id))
@@ -253,11 +262,13 @@ void free_all(medgp_ctx *c) {
     c->retired.clear();
     c->retired_bytes = 0;
     for (void **p : {(void **)&c->d_post_t2, (void **)&c->d_post_work, (void **)&c->d_post_m2, (void **)&c->d_post_mean, (void **)&c->d_post_var,
-                     (void **)&c->d_post_parts, (void **)&c->d_post_tiles}) {
+                     (void **)&c->d_post_parts, (void **)&c->d_post_tiles, (void **)&c->d_joint_pats, (void **)&c->d_joint_pairs, (void **)&c->d_joint_blks,
+                     (void **)&c->d_joint_C, (void **)&c->d_joint_eps, (void **)&c->d_joint_cov, (void **)&c->d_joint_samp, (void **)&c->d_joint_cstat}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
     c->post_cap_pts = c->post_cap_m2 = c->post_cap_mean = c->post_cap_var = c->post_cap_parts = c->post_cap_tiles = c->post_cap_work = 0;
+    c->joint_cap_pats = c->joint_cap_pairs = c->joint_cap_blks = c->joint_cap_C = c->joint_cap_eps = c->joint_cap_cov = c->joint_cap_samp = c->joint_cap_cstat = 0;
 }
 
 int num_cov(int kidx, int Q, int D, int R) {
@@ -935,7 +946,7 @@ int run_pipeline(medgp_ctx *c, int nbatch, int max_n, const double *theta_dev, i
 
 extern "C" {
 
-int medgp_abi_version(void) { return 4; }
+int medgp_abi_version(void) { return 5; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -1922,10 +1933,38 @@ void launch_posterior(medgp_ctx *c, const MedgpDev &V, int ntiles, const PostTil
     }
 #undef MEDGP_POST
 }
-}  // namespace
 
-int medgp_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
-                          const int32_t *meta2, const float *t2, float *mean, float *var, float *parts, int32_t *status) {
+void launch_postcov(medgp_ctx *c, const MedgpDev &V, int npairs, const JointTile *pairs, size_t stride, float *cov) {
+    const dim3 tg(npairs), tb(256);
+#define MEDGP_PCOV(QQ) hipLaunchKernelGGL(k_postcov<QQ>, tg, tb, 0, c->stream, V, c->d_joint_pats, pairs, c->d_post_m2, c->d_post_t2, c->d_post_work, stride, \
+                                          c->d_joint_C, cov)
+    switch (V.Q) {
+    case 1: MEDGP_PCOV(1); break;
+    case 2: MEDGP_PCOV(2); break;
+    case 3: MEDGP_PCOV(3); break;
+    case 4: MEDGP_PCOV(4); break;
+    case 5: MEDGP_PCOV(5); break;
+    case 6: MEDGP_PCOV(6); break;
+    case 7: MEDGP_PCOV(7); break;
+    case 8: MEDGP_PCOV(8); break;
+    default: MEDGP_PCOV(0); break;   // Q > 8: generic component loop
+    }
+#undef MEDGP_PCOV
+}
+
+// the joint outputs of medgp_posterior_joint_batch (null: medgp_posterior_batch)
+struct JointReq {
+    int nsamp;
+    const double *eps;
+    float *cov, *samples;
+    int32_t *cov_status;
+};
+
+// medgp_posterior_batch and medgp_posterior_joint_batch: ONE code path for mean / var (same pipeline run, same k_posterior launches
+// per tile: the bits of a point do not depend on the launch chunk).  A joint call cuts its launch chunks at patient boundaries and
+// runs k_postcov / k_postfactor / k_postdraw behind k_posterior on each chunk, while the chunk's work rows are resident.
+int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                   const int32_t *meta2, const float *t2, float *mean, float *var, float *parts, int32_t *status, const JointReq *jq) {
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
     if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
@@ -1934,10 +1973,19 @@ int medgp_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const 
     for (int b = 0; b < nbatch; b++)
         if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
     const int64_t M = offsets[nbatch];
+    const bool want_cov = jq && jq->cov, want_samp = jq && jq->nsamp > 0;
+    if (jq) {
+        if (jq->nsamp < 0) return fail(c, MEDGP_ERR_ARG, "nsamp = %d", jq->nsamp);
+        if (!want_cov && !want_samp) return fail(c, MEDGP_ERR_ARG, "neither cov nor samples asked for (cov == NULL and nsamp == 0)");
+        if (want_samp && M > 0 && (!jq->eps || !jq->samples)) return fail(c, MEDGP_ERR_ARG, "eps / samples is NULL with nsamp = %d", jq->nsamp);
+        if (want_samp && M * (int64_t)jq->nsamp > (int64_t)INT32_MAX) return fail(c, MEDGP_ERR_ARG, "%lld x %d sample values in one call", (long long)M, jq->nsamp);
+    }
     if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
     if (M > 0 && (!t2 || !mean || !var)) return fail(c, MEDGP_ERR_ARG, "t2 / mean / var is NULL");
     if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
     const int D = c->D;
+    std::vector<size_t> cov_off(want_cov ? nbatch : 0);   // start of patient b's block in cov (floats)
+    if (want_cov) { size_t o = 0; for (int b = 0; b < nbatch; b++) { cov_off[b] = o; const size_t m = (size_t)(offsets[b + 1] - offsets[b]); o += m * m; } }
     std::vector<double> ht2(M);
     std::vector<int> hm2(M, 0);
     for (int64_t j = 0; j < M; j++) {
@@ -1961,22 +2009,61 @@ int medgp_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const 
     if (with_parts && (rc = post_buf(c, (void **)&c->d_post_parts, &c->post_cap_parts, Mz * D * sizeof(float)))) return rc;
     // tile table, per size class (entries of a class share the view's leading dimension, hence the work-row stride), and chunks
     // of consecutive tiles of one class whose work rows stay within the budget
-    struct Chunk { const SizeClass *k; int t0, nt; size_t stride; };
+    // (joint call: chunks of whole patients, with their patients [pat0, pat0 + npat), tile pairs and row blocks)
+    struct Chunk { const SizeClass *k; int t0, nt; size_t stride; int pat0, npat, pair0, npair, blk0, nblk; };
     std::vector<PostTile> tiles;
     std::vector<Chunk> chunks;
-    size_t work_need = 0;
+    std::vector<JointPat> jpats;
+    std::vector<JointTile> jpairs, jblks;
+    size_t work_need = 0, c_need = 0, cov_need = 0;
     for (const SizeClass &k : c->plan.cls) {
         const int t_begin = (int)tiles.size();
+        const size_t stride = (size_t)k.ld * 64 + ((with_parts && !parts_lds) ? (size_t)D * 64 : 0);   // doubles per tile
+        if (jq) {
+            Chunk ch{&k, t_begin, 0, stride, (int)jpats.size(), 0, (int)jpairs.size(), 0, (int)jblks.size(), 0};
+            size_t wbytes = 0, cdbl = 0, cflt = 0;
+            auto close = [&]() {
+                if (ch.npat == 0) return;
+                chunks.push_back(ch);
+                work_need = std::max(work_need, wbytes); c_need = std::max(c_need, cdbl * sizeof(double)); cov_need = std::max(cov_need, cflt * sizeof(float));
+                ch.t0 += ch.nt; ch.nt = 0; ch.pat0 += ch.npat; ch.npat = 0; ch.pair0 += ch.npair; ch.npair = 0; ch.blk0 += ch.nblk; ch.nblk = 0;
+                wbytes = cdbl = cflt = 0;
+            };
+            for (int i = k.b0; i < k.b0 + k.count; i++) {
+                const int b = c->plan.order[i];
+                const int64_t m = offsets[b + 1] - offsets[b];
+                if (m == 0) continue;
+                const int nt = (int)((m + POST_TW - 1) / POST_TW);
+                const size_t mpad = (size_t)nt * 64;
+                // V of all its tiles, C, and its float block of cov
+                const size_t need = (size_t)nt * stride * sizeof(double) + mpad * mpad * sizeof(double) + (want_cov ? (size_t)m * m * sizeof(float) : 0);
+                if (need > c->posterior_budget)
+                    return fail(c, MEDGP_ERR_CAPACITY, "patient %d: the joint posterior of %lld points on %d observations needs %zu MB at once, the budget is %zu MB (MEDGP_POSTERIOR_BUDGET_GB)",
+                                b, (long long)m, c->plan.en[i], need >> 20, c->posterior_budget >> 20);
+                if (wbytes + cdbl * sizeof(double) + cflt * sizeof(float) + need > c->posterior_budget) close();
+                const int pidx = (int)jpats.size();
+                jpats.push_back({i - k.b0, b, (int)offsets[b], (int)m, ch.nt, 0, (long long)cdbl, (long long)cflt});
+                for (int64_t p = offsets[b]; p < offsets[b + 1]; p += POST_TW)
+                    tiles.push_back({i - k.b0, (int)p, (int)std::min<int64_t>(POST_TW, offsets[b + 1] - p), 0});
+                for (int I = 0; I < nt; I++) {
+                    for (int J = 0; J <= I; J++) jpairs.push_back({pidx, I, J, 0});
+                    jblks.push_back({pidx, I, 0, 0});
+                }
+                ch.nt += nt; ch.npat++; ch.npair += nt * (nt + 1) / 2; ch.nblk += nt;
+                wbytes += (size_t)nt * stride * sizeof(double); cdbl += mpad * mpad; if (want_cov) cflt += (size_t)m * m;
+            }
+            close();
+            continue;
+        }
         for (int i = k.b0; i < k.b0 + k.count; i++) {
             const int b = c->plan.order[i];
             for (int64_t p = offsets[b]; p < offsets[b + 1]; p += POST_TW)
                 tiles.push_back({i - k.b0, (int)p, (int)std::min<int64_t>(POST_TW, offsets[b + 1] - p), 0});
         }
-        const size_t stride = (size_t)k.ld * 64 + ((with_parts && !parts_lds) ? (size_t)D * 64 : 0);   // doubles per tile
         const int per_chunk = (int)std::max<size_t>(1, c->posterior_budget / (stride * sizeof(double)));
         for (int t0 = t_begin; t0 < (int)tiles.size(); t0 += per_chunk) {
             const int nt = std::min(per_chunk, (int)tiles.size() - t0);
-            chunks.push_back({&k, t0, nt, stride});
+            chunks.push_back({&k, t0, nt, stride, 0, 0, 0, 0, 0, 0});
             work_need = std::max(work_need, (size_t)nt * stride * sizeof(double));
         }
     }
@@ -1990,6 +2077,26 @@ int medgp_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const 
         HIPCHK(c, hipMemcpyAsync(c->d_post_m2, hm2.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_post_tiles, tiles.data(), sizeof(PostTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
     }
+    if (jq) {
+        if ((rc = post_buf(c, (void **)&c->d_joint_cstat, &c->joint_cap_cstat, sizeof(int) * nbatch))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->d_joint_cstat, 0, sizeof(int) * nbatch, c->stream));
+    }
+    if (jq && !jpats.empty()) {
+        if ((rc = post_buf(c, (void **)&c->d_joint_pats, &c->joint_cap_pats, jpats.size() * sizeof(JointPat)))) return rc;
+        if ((rc = post_buf(c, (void **)&c->d_joint_pairs, &c->joint_cap_pairs, jpairs.size() * sizeof(JointTile)))) return rc;
+        if ((rc = post_buf(c, (void **)&c->d_joint_blks, &c->joint_cap_blks, jblks.size() * sizeof(JointTile)))) return rc;
+        if ((rc = post_buf(c, (void **)&c->d_joint_C, &c->joint_cap_C, c_need))) return rc;
+        if (want_cov && (rc = post_buf(c, (void **)&c->d_joint_cov, &c->joint_cap_cov, cov_need))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_joint_pats, jpats.data(), sizeof(JointPat) * jpats.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_joint_pairs, jpairs.data(), sizeof(JointTile) * jpairs.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_joint_blks, jblks.data(), sizeof(JointTile) * jblks.size(), hipMemcpyHostToDevice, c->stream));
+        if (want_samp) {
+            const size_t ns = (size_t)M * jq->nsamp;
+            if ((rc = post_buf(c, (void **)&c->d_joint_eps, &c->joint_cap_eps, ns * sizeof(double)))) return rc;
+            if ((rc = post_buf(c, (void **)&c->d_joint_samp, &c->joint_cap_samp, ns * sizeof(float)))) return rc;
+            HIPCHK(c, hipMemcpyAsync(c->d_joint_eps, jq->eps, ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        }
+    }
     // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
     if ((rc = run_pipeline(c, nbatch, max_n, c->d_theta, 0, false, 1, nullptr, nullptr, nullptr, true, true))) return rc;
     if (with_parts && M > 0)
@@ -1999,19 +2106,57 @@ int medgp_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const 
         }
     for (const Chunk &ch : chunks) {   // chunks reuse the work rows in stream order
         Launcher l(c, KID_POSTERIOR);
-        launch_posterior(c, class_view(c, c->plan, *ch.k), ch.nt, c->d_post_tiles + ch.t0, ch.stride, with_parts ? 1 : 0, parts_lds);
+        const MedgpDev V = class_view(c, c->plan, *ch.k);
+        launch_posterior(c, V, ch.nt, c->d_post_tiles + ch.t0, ch.stride, with_parts ? 1 : 0, parts_lds);
+        if (!jq) continue;
+        l.finish();
+        {
+            Launcher lc(c, KID_POSTCOV);
+            launch_postcov(c, V, ch.npair, c->d_joint_pairs + ch.pair0, ch.stride, want_cov ? c->d_joint_cov : nullptr);
+        }
+        if (want_samp) {   // (a covariance-only call factors nothing)
+            {
+                Launcher lf(c, KID_POSTFACTOR);
+                hipLaunchKernelGGL(k_postfactor, dim3(ch.npat), dim3(256), 0, c->stream, V, c->d_joint_pats + ch.pat0, c->d_joint_C, c->d_joint_cstat);
+            }
+            Launcher ld(c, KID_POSTDRAW);
+            hipLaunchKernelGGL(k_postdraw, dim3(ch.nblk), dim3(256), 0, c->stream, V, c->d_joint_pats, c->d_joint_blks + ch.blk0, c->d_post_work, ch.stride,
+                               c->d_joint_C, c->d_joint_cstat, c->d_joint_eps, jq->nsamp, c->d_joint_samp);
+        }
+        if (want_cov)   // the chunk's blocks go home before the next chunk reuses the buffer (stream order)
+            for (int i = ch.pat0; i < ch.pat0 + ch.npat; i++) {
+                const JointPat &P = jpats[i];
+                HIPCHK(c, hipMemcpyAsync(jq->cov + cov_off[P.b], c->d_joint_cov + P.voff, sizeof(float) * (size_t)P.m * P.m, hipMemcpyDeviceToHost, c->stream));
+            }
     }
     HIPCHK(c, hipGetLastError());
     if (M > 0) {
         HIPCHK(c, hipMemcpyAsync(mean, c->d_post_mean, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(var, c->d_post_var, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
         if (with_parts) HIPCHK(c, hipMemcpyAsync(parts, c->d_post_parts, sizeof(float) * M * D, hipMemcpyDeviceToHost, c->stream));
+        if (want_samp) HIPCHK(c, hipMemcpyAsync(jq->samples, c->d_joint_samp, sizeof(float) * (size_t)M * jq->nsamp, hipMemcpyDeviceToHost, c->stream));
     }
-    std::vector<int> st(nbatch, 0);
-    if (status) HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    std::vector<int> st(nbatch, 0), cst(nbatch, 0);
+    if (status || jq) HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    if (jq) HIPCHK(c, hipMemcpyAsync(cst.data(), c->d_joint_cstat, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (status) for (int i = 0; i < nbatch; i++) status[c->plan.order[i]] = st[i];   // internal order -> the caller's
+    if (jq && jq->cov_status)   // (caller order on the device; a patient without a factor has no C either)
+        for (int i = 0; i < nbatch; i++) { const int b = c->plan.order[i]; jq->cov_status[b] = (st[i] < 0 || cst[b] < 0) ? -1 : 0; }
     return MEDGP_OK;
+}
+}  // namespace
+
+int medgp_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                          const int32_t *meta2, const float *t2, float *mean, float *var, float *parts, int32_t *status) {
+    return posterior_impl(c, nbatch, slots, theta, offsets, meta2, t2, mean, var, parts, status, nullptr);
+}
+
+int medgp_posterior_joint_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                                const int32_t *meta2, const float *t2, int nsamp, const double *eps, float *mean, float *var,
+                                float *cov, float *samples, int32_t *status, int32_t *cov_status) {
+    const JointReq jq{nsamp, eps, cov, samples, cov_status};
+    return posterior_impl(c, nbatch, slots, theta, offsets, meta2, t2, mean, var, nullptr, status, &jq);
 }
 
 #ifdef MEDGP_STAMPS
