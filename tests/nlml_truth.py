@@ -26,6 +26,9 @@ cos(w t_i), sin(w t_i) (k_prep) and a 64-blocked left-looking factorisation.
 The module also holds the sweep cases shared by tests/test_nlml_truth.py (CPU: budget conditions) and
 tests/test_nlml_budget_gpu.py (GPU: the device held to the budget), and the budget constants measured on the CPU programs.
 """
+import hashlib
+import os
+
 import numpy as np
 
 # fails loudly (never skips): the truth needs a long double with at least the x87 64-bit significand
@@ -313,6 +316,11 @@ DRAWS = {
     "hyp_period_1h_n80_burst": {0: 1},
     "hyp_period_1h_n80_missing": {1: 13},
     "hyp_period_1h_n80_same_time": {0: 1, 1: 1},
+    "large_config5": {0: 2},
+    "large_pass2": {0: 1},
+    "large_q_Q17": {0: 1},
+    "large_q_Q8": {0: 1},
+    "large_slices": {0: 1},
     "lmc_Q1": {3: 1},
     "lmc_Q10": {1: 1, 2: 1, 4: 2},
     "lmc_Q11": {3: 1},
@@ -493,44 +501,175 @@ def shifted(case, off):
     return dict(case, pts=pts, id=f"{case['id']}_off{int(off)}")
 
 
+# ---- the large sweep: N = 512 .. 4096, where the benchmarked kernels spend their time -----------------------------------------------
+# (case id, kidx, Q, D, R, [(n, random_patient mode)]).  Second and later passes of k_cholinv over its block slots, the parked launch
+# of the look-ahead schedule (8 x n = 768), 32 / 45 / 64 look-ahead steps with la_slice_len changing at k = 32 and k = 44, k_wgrad's
+# 2048-column k range.  LARGE_OPTIONAL may be absent from large_cases() (DESIGN.md section 3 says why when it is); nothing else may.
+_LARGE_LMC = [
+    ("large_headline", 5, 24, 8, [(512, m) for m in ("plain", "missing", "shuffled", "plain", "missing", "shuffled", "plain", "plain")]),
+    ("large_pass2", 3, 3, 2, [(513, "plain"), (576, "plain"), (768, "plain"), (1024, "plain")]),
+    ("large_q_Q8", 8, 3, 2, [(640, "plain")]),
+    ("large_q_Q9", 9, 3, 2, [(640, "plain")]),
+    ("large_q_Q16", 16, 3, 2, [(640, "plain")]),
+    ("large_q_Q17", 17, 3, 2, [(640, "plain")]),
+    ("large_config3", 5, 24, 8, [(2048, "plain")]),
+    ("large_slices", 5, 24, 8, [(2880, "plain")]),
+    ("large_config5", 5, 64, 8, [(4096, "plain")]),
+]
+LARGE_OPTIONAL = {"large_config5"}
+LARGE_ABSENT = set()         # optional cases left out: only when none of the first eight draws meets the caps (none is, today)
+LARGE_IDS = [c[0] for c in _LARGE_LMC] + ["large_sm_Q4", "large_se"]
+LARGE_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nlml_truth_large.npz")
+FIXTURE_ABOVE_N = 1024       # the truth of a larger patient takes minutes: it is read from LARGE_FIXTURE, never recomputed by the suite
+FIXTURE_BIT_CHECK = ("large_pass2", 3)      # stored although it is cheap: the CPU test recomputes its truth and demands the stored bits
+
+
+def large_cases():
+    """N = 512 .. 4096 (sweep "large"): the headline shape, second passes of both k_cholinv shapes, the Q > 8 split and the generic
+    route past one pass, the parking size, and the long look-ahead chains; SM (Q = 4) and SE at n = 1024."""
+    from medgp_amd import synth
+    from random_patients import random_patient
+    out = []
+    for ci, (cid, Q, D, R, spec) in enumerate(_LARGE_LMC):
+        if cid in LARGE_ABSENT:
+            continue
+        g = _philox(20261023, ci)
+        pts = [random_patient(g, D, n, mode) for n, mode in spec]
+        th = [synth.theta(4714 + 1000 * _draw(cid, p), 100 * ci + p, 7, Q, D, R) for p in range(len(spec))]
+        out.append(dict(id=cid, sweep="large", kidx=7, Q=Q, D=D, R=R, pts=pts, th=th))
+    for kidx, Q, cid in ((8, 4, "large_sm_Q4"), (0, 1, "large_se")):
+        g = _philox(20261024, kidx)
+        t = np.sort(g.uniform(0.0, 200.0, size=1024)).astype(np.float32)
+        pts = [(None, t, g.standard_normal(1024).astype(np.float32))]
+        th = [synth.theta(4715 + 1000 * _draw(cid, 0), kidx, kidx, Q, 1, 0)]
+        out.append(dict(id=cid, sweep="large", kidx=kidx, Q=Q, D=1, R=0, pts=pts, th=th))
+    return out
+
+
 def all_cases():
-    return variant_cases() + wide_cases() + hyper_cases() + time_cases()
+    return variant_cases() + wide_cases() + hyper_cases() + time_cases() + large_cases()
+
+
+# ---- committed truths of the slow patients (tests/golden/make_nlml_truth_large.py writes them, by hand) ------------------------------
+
+def input_sha256(case, p):
+    """SHA-256 of the exact input bytes of patient p of a case: (kidx, Q, D, R) as int64, meta as int32 (absent for the
+    single-output families), t and y as float32, theta as float64"""
+    m, t, y = case["pts"][p]
+    h = hashlib.sha256()
+    h.update(np.array([case["kidx"], case["Q"], case["D"], case["R"]], np.int64).tobytes())
+    if m is not None:
+        h.update(np.ascontiguousarray(m, np.int32).tobytes())
+    for a, dt in ((t, np.float32), (y, np.float32), (case["th"][p], np.float64)):
+        h.update(np.ascontiguousarray(a, dt).tobytes())
+    return h.hexdigest()
+
+
+def split_hi_lo(x):
+    """long double -> two float64 with hi + lo == x exactly (64-bit significand: 53 + 11 bits)"""
+    x = np.asarray(x, np.longdouble)
+    hi = x.astype(np.float64)
+    lo = (x - hi.astype(np.longdouble)).astype(np.float64)
+    assert np.all(hi.astype(np.longdouble) + lo.astype(np.longdouble) == x)
+    return hi, lo
+
+
+def in_fixture(case, p):
+    """whether truth and program errors of this patient come from LARGE_FIXTURE"""
+    return case["sweep"] == "large" and case["pts"][p][1].shape[0] > FIXTURE_ABOVE_N
+
+
+def fixture_patients():
+    """[(case, p)] of every patient the fixture must hold: the slow ones and the bit-check patient"""
+    return [(c, p) for c in large_cases() for p in range(len(c["pts"])) if in_fixture(c, p) or (c["id"], p) == FIXTURE_BIT_CHECK]
+
+
+_FIXTURE = None
+
+
+def fixture_entry(case, p):
+    """dict(status, truth = (nlml, grad) in long double, en, eg) of a committed patient.  Raises (never skips, never recomputes)
+    when the entry is missing or was made from other input bytes."""
+    global _FIXTURE
+    if _FIXTURE is None:
+        with np.load(LARGE_FIXTURE) as z:
+            _FIXTURE = {k: z[k] for k in z.files}
+    key = f"{case['id']}:{p}"
+    ids = [str(x) for x in _FIXTURE["ids"]]
+    if key not in ids:
+        raise RuntimeError(f"{LARGE_FIXTURE} holds no truth for {key}: run tests/golden/make_nlml_truth_large.py")
+    i = ids.index(key)
+    sha = input_sha256(case, p)
+    if str(_FIXTURE["sha256"][i]) != sha:
+        raise RuntimeError(f"{LARGE_FIXTURE}: {key} was computed from other inputs (stored {_FIXTURE['sha256'][i]}, now {sha}): "
+                           "run tests/golden/make_nlml_truth_large.py")
+    X = np.longdouble
+    tn = X(_FIXTURE["nlml_hi"][i]) + X(_FIXTURE["nlml_lo"][i])
+    tg = _FIXTURE[f"grad_hi_{i}"].astype(X) + _FIXTURE[f"grad_lo_{i}"].astype(X)
+    return dict(status=int(_FIXTURE["status"][i]), truth=(tn, tg), en=[float(x) for x in _FIXTURE["en"][i]],
+                eg=[float(x) for x in _FIXTURE["eg"][i]])
 
 
 _TRUTH = {}
 
 
+def compute_truth(case, p, jitter_rounds=0):
+    m, t, y = case["pts"][p]
+    return nlml_grad(case["kidx"], case["Q"], case["D"], case["R"], m, t, y, case["th"][p], np.longdouble, jitter_rounds)
+
+
 def truth_of(case, p, jitter_rounds=0):
-    """(status, nlml, grad) of patient p of a case in long double, computed once per (case, patient, jitter_rounds) and process"""
+    """(status, nlml, grad) of patient p of a case in long double, computed once per (case, patient, jitter_rounds) and process;
+    read from the committed fixture for the slow patients of the large sweep"""
+    if in_fixture(case, p):                                 # (the input hash is checked on every call, cached or not)
+        e = fixture_entry(case, p)
+        if e["status"] != jitter_rounds:
+            raise RuntimeError(f"{case['id']}:{p}: the fixture holds the truth at jitter_rounds {e['status']}, not {jitter_rounds}")
+        return (e["status"],) + e["truth"]
     key = (case["id"], p, jitter_rounds)
     if key not in _TRUTH:
-        m, t, y = case["pts"][p]
-        _TRUTH[key] = nlml_grad(case["kidx"], case["Q"], case["D"], case["R"], m, t, y, case["th"][p], np.longdouble, jitter_rounds)
+        _TRUTH[key] = compute_truth(case, p, jitter_rounds)
     return _TRUTH[key]
 
 
 _BUDGET = {}
 
 
+def oracle_program(case, p):
+    """program (a): the oracle's dict(status, nlml, grad)"""
+    from oracle import oracle as O
+    m, t, y = case["pts"][p]
+    return O.nlml_grad(case["kidx"], case["Q"], case["D"], case["R"], m, t, y, case["th"][p], nthreads=4)
+
+
+def float64_program(case, p, jitter_rounds, variant="plain"):
+    """programs (b) (variant "plain") and (c) ("device"): the truth code in float64"""
+    m, t, y = case["pts"][p]
+    return nlml_grad(case["kidx"], case["Q"], case["D"], case["R"], m, t, y, case["th"][p], np.float64, jitter_rounds, variant=variant)
+
+
+def compute_programs(case, p, truth=compute_truth):
+    """the truth and the three legitimate fp64 programs on patient p of a case, all computed here (what the fixture generator stores)"""
+    ref = oracle_program(case, p)
+    st = ref["status"]
+    if st < 0:
+        return dict(status=st, truth=None, en=None, eg=None)
+    _, tn, tg = truth(case, p, st)
+    _, bn, bg = float64_program(case, p, st)
+    _, cn, cg = float64_program(case, p, st, "device")
+    e = [error_pair(ref["nlml"], ref["grad"], tn, tg), error_pair(bn, bg, tn, tg), error_pair(cn, cg, tn, tg)]
+    return dict(status=st, truth=(tn, tg), en=[x[0] for x in e], eg=[x[1] for x in e])
+
+
 def programs_of(case, p):
     """the three legitimate fp64 programs on patient p of a case, against the truth at the jitter_rounds the oracle reports:
-    dict(status, truth = (nlml, grad) in long double, en = [E_a, E_b, E_c] (nlml), eg = [...] (gradient)).  Cached per process."""
+    dict(status, truth = (nlml, grad) in long double, en = [E_a, E_b, E_c] (nlml), eg = [...] (gradient)).  Cached per process.
+    The slow patients of the large sweep come from the committed fixture (tests/test_nlml_truth.py re-derives E_a and E_b)."""
+    if in_fixture(case, p):
+        return fixture_entry(case, p)
     key = (case["id"], p)
     if key not in _BUDGET:
-        from oracle import oracle as O
-        k, Q, D, R = case["kidx"], case["Q"], case["D"], case["R"]
-        m, t, y = case["pts"][p]
-        th = case["th"][p]
-        ref = O.nlml_grad(k, Q, D, R, m, t, y, th, nthreads=4)
-        st = ref["status"]
-        if st < 0:
-            _BUDGET[key] = dict(status=st, truth=None, en=None, eg=None)
-        else:
-            _, tn, tg = truth_of(case, p, st)
-            _, bn, bg = nlml_grad(k, Q, D, R, m, t, y, th, np.float64, st)
-            _, cn, cg = nlml_grad(k, Q, D, R, m, t, y, th, np.float64, st, variant="device")
-            e = [error_pair(ref["nlml"], ref["grad"], tn, tg), error_pair(bn, bg, tn, tg), error_pair(cn, cg, tn, tg)]
-            _BUDGET[key] = dict(status=st, truth=(tn, tg), en=[x[0] for x in e], eg=[x[1] for x in e])
+        _BUDGET[key] = compute_programs(case, p, truth_of)
     return _BUDGET[key]
 
 

@@ -1,5 +1,6 @@
 """GPU sweeps that hold medgp_nlml_grad to an fp64 error budget against the long-double truth of tests/nlml_truth.py, on every
-kernel variant the dispatcher can launch, over the hyper ranges a trained model reaches, and with the time axis moved away from 0.
+kernel variant the dispatcher can launch, over the hyper ranges a trained model reaches, with the time axis moved away from 0, and
+at the sizes the benchmarks run at (N = 512 .. 4096: the "large" sweep at the end of the file).
 
 Budget of a case (per patient) = M * max(E_a, E_b, E_c): the errors of three legitimate fp64 programs on the CPU (the oracle, the
 float64 run of the truth code, the same with the device's cosine tables and blocked factorisation), M = nlml_truth.M_NLML /
@@ -21,6 +22,7 @@ VARIANT = T.variant_cases()
 WIDE = T.wide_cases()
 HYPER = T.hyper_cases()
 TIME = T.time_cases()
+LARGE = {c["id"]: c for c in T.large_cases()}
 
 ROUTES = {      # name -> (MEDGP_MULTI_CU, MEDGP_CHOLINV_NW)
     "wg44": ("-1", "44"), "wg84": ("-1", "84"), "la": ("1", None), "auto": (None, None),
@@ -69,19 +71,25 @@ def _run(case, slots=None, profile=True):
 
 def _check(case, out, slots=None, budget_case=None):
     """device results of a call against the budget of budget_case (default: the case itself), patient by patient"""
-    nlml, grad, st, nlml0, st0 = out[:5]
     bc = budget_case or case
     slots = np.arange(len(case["pts"])) if slots is None else np.asarray(slots)
-    for b, s in enumerate(slots):
-        rst, tn, tg, bn, bg = T.budget_of(bc, int(s))
-        assert st[b] == rst and st0[b] == rst, (case["id"], b, st[b], st0[b], rst)
+    _check_refs(case["id"], out, [(bc, int(s)) for s in slots])
+
+
+def _check_refs(label, out, refs):
+    """device results of a call, entry b against the budget of patient refs[b] = (case, patient)"""
+    nlml, grad, st, nlml0, st0 = out[:5]
+    assert len(refs) == len(nlml)
+    for b, (bc, s) in enumerate(refs):
+        rst, tn, tg, bn, bg = T.budget_of(bc, s)
+        assert st[b] == rst and st0[b] == rst, (label, b, st[b], st0[b], rst)
         if rst < 0:
             continue
         en, eg = T.error_pair(nlml[b], grad[b], tn, tg)
-        print(f"{case['id']} entry {b} n={case['pts'][s][1].shape[0]}: nlml {en:.2e} / {bn:.2e}, grad {eg:.2e} / {bg:.2e}")
-        assert en <= bn, (case["id"], b, "nlml", en, bn)
-        assert eg <= bg, (case["id"], b, "grad", eg, bg)
-        assert nlml0[b] == nlml[b], (case["id"], b, "the nlml-only path must return the same bits")
+        print(f"{label} entry {b} n={bc['pts'][s][1].shape[0]}: nlml {en:.2e} / {bn:.2e}, grad {eg:.2e} / {bg:.2e}")
+        assert en <= bn, (label, b, "nlml", en, bn)
+        assert eg <= bg, (label, b, "grad", eg, bg)
+        assert nlml0[b] == nlml[b], (label, b, "the nlml-only path must return the same bits")
 
 
 def _check_route(case, route, plan, prof, ns):
@@ -236,3 +244,124 @@ def test_time_axis_offset_within_unshifted_budget(case, off, monkeypatch):
     sh = T.shifted(case, off)
     out = _run(sh)
     _check(sh, out, budget_case=case)
+
+
+# ---- the large sweep: N = 512 .. 4096 ---------------------------------------------------------------------------------------------------
+# The truths of the patients of n > 1024 are committed (tests/golden/nlml_truth_large.npz, re-derived on the CPU by
+# tests/test_nlml_truth.py); the others are computed on the host when first needed, about 100 s in all.
+
+def test_large_headline_512_entries_default_routing(monkeypatch):
+    """the benchmark's shape: 512 entries of n = 512, D = 24, Q = 5, R = 8 in one call on default routing.  More entries than CUs
+    (asserted), so the dispatcher takes k_cholinv<4,4> (asserted from the plan: route 0), eight row blocks over its four block slots.
+    That two such workgroups share a CU and that k_wgrad runs at its large-launch prefetch depth (PF = 1) cannot be observed through
+    the ABI: both rest on run_pipeline_one's rules for a launch of more entries than CUs (see test_prefetch_depths_bit_identical).
+    Eight distinct patients (plain, missing, shuffled) repeated 64 times: every entry within the budget of its patient, and the
+    repeats of a patient bit-identical."""
+    import torch
+    assert torch.cuda.get_device_properties(0).multi_processor_count < 512
+    case = LARGE["large_headline"]
+    slots = np.tile(np.arange(8), 64)
+    _env(monkeypatch, "auto")
+    out = _run(case, slots)
+    plan, prof = out[5], out[6]
+    assert plan == [(512, 8, 0)], plan
+    assert prof["k_la_step"][1] == 0 and prof["k_wgrad"][1] == 1 and prof["k_lauum"][1] == 0, prof
+    _check(case, out, slots)
+    for b in range(8, 512):
+        assert out[0][b] == out[0][b % 8] and np.array_equal(out[1][b], out[1][b % 8]) and out[3][b] == out[3][b % 8], b
+
+
+@pytest.mark.parametrize("route", ["wg44", "wg84", "la", "auto"])
+def test_large_headline_batch_of_8(route, monkeypatch):
+    """the same eight patients once: at most one patient per CU, on both one-workgroup shapes, the look-ahead route and default routing"""
+    case = LARGE["large_headline"]
+    _env(monkeypatch, route)
+    out = _run(case)
+    _check_route(case, route, out[5], out[6], [512] * 8)
+    assert [c[:2] for c in out[5]] == [(8, 8)], out[5]
+    _check(case, out)
+
+
+SECOND_PASS = ["large_pass2", "large_q_Q8", "large_q_Q9", "large_q_Q16", "large_q_Q17", "large_sm_Q4", "large_se"]
+ROUTE_DEPTH = [("wg44", None), ("wg84", "1"), ("wg84", "2"), ("la", "1"), ("la", "2"), ("auto", None)]
+
+
+@pytest.mark.parametrize("route,deep", ROUTE_DEPTH, ids=lambda x: f"pf{x}" if x in ("1", "2") else (x or "pfauto"))
+@pytest.mark.parametrize("cid", SECOND_PASS)
+def test_large_second_pass_within_budget(cid, route, deep, monkeypatch):
+    """more row blocks than k_cholinv<8,4> has slots: n = 513, 576 (nine blocks: the first block past the eight slots), 768 (a full
+    second pass), 1024 (two full passes of <8,4>, four of <4,4>) in one ragged call; n = 640 (ten blocks) at Q = 8, 9, 16 (one and
+    two launches of assembly and k_wgrad) and Q = 17 (generic pair kernels, no k_wgrad: _check_route); the single-output families SM
+    (Q = 4) and SE at n = 1024.  Both prefetch depths on the wg84 and la legs."""
+    case = LARGE[cid]
+    ns = [p[1].shape[0] for p in case["pts"]]
+    assert [_blocks(n) for n in ns] == {"large_pass2": [9, 9, 12, 16], "large_sm_Q4": [16], "large_se": [16]}.get(cid, [10])
+    _env(monkeypatch, route, deep)
+    out = _run(case)
+    _check_route(case, route, out[5], out[6], ns)
+    assert max(c[1] for c in out[5]) == max(_blocks(n) for n in ns), out[5]
+    _check(case, out)
+
+
+def test_large_parked_launch_within_budget(monkeypatch):
+    """eight equal entries of n = 768 on the look-ahead route: the launch geometry with a parked workgroup (default) and without
+    (MEDGP_LA_PARK=0), BOTH against the truth (test_la_park_switch_bit_identical_where_parking_engages knows only that they agree)"""
+    big = LARGE["large_pass2"]
+    assert big["pts"][2][1].shape[0] == 768
+    case = dict(big, id="large_park", pts=[big["pts"][2]], th=[big["th"][2]])
+    slots = np.zeros(8, np.int64)
+    res = {}
+    for name, park in (("default", None), ("nopark", "0")):
+        _env(monkeypatch, "la", None, park)
+        res[name] = out = _run(case, slots)
+        assert out[5] == [(8, 12, 2)] and out[6]["k_la_step"][1] == 12, (name, out[5], out[6]["k_la_step"])
+        _check_refs(f"large_park_{name}", out, [(big, 2)] * 8)
+        for b in range(1, 8):
+            assert out[0][b] == out[0][0] and np.array_equal(out[1][b], out[1][0]), (name, b)
+    for i in range(3):
+        assert np.array_equal(res["default"][i], res["nopark"][i]), i
+
+
+LONG = [cid for cid in ("large_config3", "large_slices", "large_config5") if cid in LARGE]
+
+
+@pytest.mark.parametrize("route", ["la", "wg84"])
+@pytest.mark.parametrize("cid", LONG)
+def test_large_long_chain_within_budget(cid, route, monkeypatch):
+    """one patient of n = 2048 (32 look-ahead steps), n = 2880 (45: the steps k = 32 and k = 44, where la_slice_len changes, and
+    la_fold off) and, where nlml_truth keeps it, n = 4096 at D = 64 (64), alone in its call: one k_la_step launch per 64-block on
+    the look-ahead route, and the one-workgroup route <8,4> over the same matrix"""
+    case = LARGE[cid]
+    n = case["pts"][0][1].shape[0]
+    nb = _blocks(n)
+    assert len(case["pts"]) == 1 and nb == {"large_config3": 32, "large_slices": 45, "large_config5": 64}[cid]
+    _env(monkeypatch, route)
+    out = _run(case)
+    plan, prof = out[5], out[6]
+    assert plan == [(1, nb, 2 if route == "la" else 1)], plan
+    assert prof["k_la_step"][1] == (nb if route == "la" else 0), prof["k_la_step"]
+    _check_route(case, route, plan, prof, [n])
+    _check(case, out)
+
+
+@pytest.mark.parametrize("no_classes", [False, True], ids=["classes", "no_classes"])
+def test_large_mixed_call_within_budget(no_classes, monkeypatch):
+    """n = 2048 together with the eight n = 512 patients in one call on default routing: two size classes on forked streams, the
+    large patient on the look-ahead route (asserted from the plan).  MEDGP_NO_CLASSES=1 (the documented switch back to one class
+    per call, every entry at the leading dimension of the largest) is held to the same budgets."""
+    small, big = LARGE["large_headline"], LARGE["large_config3"]
+    assert (small["Q"], small["D"], small["R"]) == (big["Q"], big["D"], big["R"])
+    case = dict(small, id="large_mixed", pts=small["pts"] + big["pts"], th=small["th"] + big["th"])
+    refs = [(small, p) for p in range(8)] + [(big, 0)]
+    _env(monkeypatch, "auto")
+    if no_classes:
+        monkeypatch.setenv("MEDGP_NO_CLASSES", "1")
+    out = _run(case)
+    plan, prof = out[5], out[6]
+    assert sum(c[0] for c in plan) == 9, plan
+    if no_classes:
+        assert plan == [(9, 32, 2)], plan
+    else:
+        assert (1, 32, 2) in plan and sum(c[0] for c in plan if c[1] == 8) == 8, plan
+    assert prof["k_la_step"][1] == sum(c[1] for c in plan if c[2] == 2), (plan, prof["k_la_step"])
+    _check_refs(f"large_mixed_{'no_classes' if no_classes else 'classes'}", out, refs)

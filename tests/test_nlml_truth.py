@@ -206,3 +206,89 @@ def test_budget_factor_M_and_caps():
     # <=, not ==: the spreads sit near a power-of-two threshold (57.8 against 64) and another libm for the long-double cosine or
     # another reduction order in the oracle may move them; the constants must cover what is measured
     assert rule(worst_sn) <= T.M_NLML and rule(worst_sg) <= T.M_GRAD
+
+
+# ---- the large sweep (N = 512 .. 4096) and its committed truths ------------------------------------------------------------------------
+
+def test_large_sweep_is_complete():
+    """how much of the large sweep may be left out is a condition: every case of nlml_truth.LARGE_IDS is there, except the optional
+    ones that nlml_truth.LARGE_ABSENT names (DESIGN.md section 3 says why), with the sizes the GPU tests rely on"""
+    assert T.LARGE_ABSENT <= T.LARGE_OPTIONAL == {"large_config5"}
+    cases = {c["id"]: c for c in T.large_cases()}
+    assert set(cases) == set(T.LARGE_IDS) - T.LARGE_ABSENT
+    assert all(c["sweep"] == "large" for c in cases.values())
+    assert set(cases) <= {c["id"] for c in T.all_cases()}
+    ns = {cid: [p[1].shape[0] for p in c["pts"]] for cid, c in cases.items()}
+    assert ns["large_headline"] == [512] * 8 and ns["large_pass2"] == [513, 576, 768, 1024]
+    assert all(ns[f"large_q_Q{Q}"] == [640] and cases[f"large_q_Q{Q}"]["Q"] == Q for Q in (8, 9, 16, 17))
+    assert ns["large_config3"] == [2048] and ns["large_slices"] == [2880] and ns["large_sm_Q4"] == [1024] and ns["large_se"] == [1024]
+    assert (cases["large_headline"]["D"], cases["large_headline"]["Q"], cases["large_headline"]["R"]) == (24, 5, 8)
+    assert (cases["large_config3"]["D"], cases["large_config3"]["Q"], cases["large_config3"]["R"]) == (24, 5, 8)
+    if "large_config5" in cases:
+        assert ns["large_config5"] == [4096] and cases["large_config5"]["D"] == 64
+    hp = cases["large_headline"]["pts"]
+    assert len({T.input_sha256(cases["large_headline"], p) for p in range(8)}) == 8            # eight DISTINCT patients
+    assert any(len(np.unique(m)) < 24 for m, t, y in hp) and any(np.any(np.diff(m) < 0) for m, t, y in hp)      # missing, shuffled
+    # the redraw rule replaces draws, it does not drop patients: every large id in DRAWS names patients that exist
+    for cid, d in T.DRAWS.items():
+        if cid.startswith("large_"):
+            assert cid in cases and all(0 <= p < len(cases[cid]["pts"]) and 0 < k < 8 for p, k in d.items()), (cid, d)
+    want = {f"{c['id']}:{p}" for c in cases.values() for p in range(len(c["pts"])) if c["pts"][p][1].shape[0] > T.FIXTURE_ABOVE_N}
+    want.add("%s:%d" % T.FIXTURE_BIT_CHECK)
+    assert {f"{c['id']}:{p}" for c, p in T.fixture_patients()} == want
+    with np.load(T.LARGE_FIXTURE) as z:
+        assert {str(x) for x in z["ids"]} == want             # and the fixture holds exactly these
+
+
+def test_large_fixture_reproduces():
+    """The committed truths are not trusted blind.  For every committed patient: the input hash matches, and program (a) (the
+    oracle) and program (b) (the truth code in float64), recomputed here, have the stored errors against the stored truth to a factor
+    of 2 (they are deterministic; the factor absorbs libm differences between machines).  A stored truth that was wrong by more than
+    an fp64 rounding error would move both.  The n = 4096, D = 64 patient is left to the hash, status and shape checks: its two
+    programs take 100 s here, which would put the CPU suite's growth over the three minutes it was given (measured: 35 s for the
+    patients of n = 1024, 2048, 2880 together)."""
+    checked = 0
+    for case, p in T.fixture_patients():
+        e = T.fixture_entry(case, p)                          # (raises on a missing entry or another input hash)
+        assert e["status"] == 0, (case["id"], p)
+        tn, tg = e["truth"]
+        assert tg.shape == (T.num_hyp(case["kidx"], case["Q"], case["D"], case["R"]),)
+        assert np.all(np.isfinite(tg.astype(np.float64))) and np.isfinite(float(tn))
+        if case["pts"][p][1].shape[0] > 2880:
+            continue
+        checked += 1
+        a = T.oracle_program(case, p)
+        assert a["status"] == e["status"]
+        _, bn, bg = T.float64_program(case, p, e["status"])
+        for name, i, (en, eg) in (("a", 0, T.error_pair(a["nlml"], a["grad"], tn, tg)), ("b", 1, T.error_pair(bn, bg, tn, tg))):
+            print(f"{case['id']}:{p} program ({name}): nlml {en:.3e} (stored {e['en'][i]:.3e}), gradient {eg:.3e} (stored {e['eg'][i]:.3e})")
+            assert e["en"][i] / 2 <= en <= 2 * e["en"][i], (case["id"], p, name, en, e["en"][i])
+            assert e["eg"][i] / 2 <= eg <= 2 * e["eg"][i], (case["id"], p, name, eg, e["eg"][i])
+    assert checked == 3          # n = 1024, 2048, 2880
+
+
+def test_large_fixture_truth_bits():
+    """the one committed patient that is cheap enough (D = 3, n = 1024): its long-double truth recomputed here equals hi + lo bit for
+    bit, and is the truth the run-time path uses for it"""
+    cid, p = T.FIXTURE_BIT_CHECK
+    case = [c for c in T.large_cases() if c["id"] == cid][0]
+    assert case["pts"][p][1].shape[0] == 1024 and not T.in_fixture(case, p)
+    e = T.fixture_entry(case, p)
+    st, tn, tg = T.truth_of(case, p, e["status"])
+    assert st == e["status"] and tn == e["truth"][0] and np.array_equal(tg, e["truth"][1])
+    assert tn.dtype == np.longdouble and tg.dtype == np.longdouble
+
+
+def test_large_fixture_fails_loudly_on_other_inputs():
+    """a committed truth is bound to the bytes it was computed from: one changed observation and truth_of / programs_of raise"""
+    case = [c for c in T.large_cases() if c["id"] == "large_config3"][0]
+    assert T.in_fixture(case, 0)
+    m, t, y = case["pts"][0]
+    y2 = y.copy()
+    y2[17] = np.nextafter(y2[17], np.float32(9))
+    other = dict(case, pts=[(m, t, y2)])
+    with pytest.raises(RuntimeError, match="other inputs"):
+        T.programs_of(other, 0)
+    other = dict(case, id="large_nowhere")
+    with pytest.raises(RuntimeError, match="holds no truth"):
+        T.truth_of(other, 0)
