@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 5: medgp_posterior_joint_batch (4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 6: medgp_loo_batch (5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -268,6 +268,38 @@ int medgp_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, cons
 int medgp_posterior_joint_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
                                 const int32_t *meta2, const float *t2, int nsamp, const double *eps, float *mean, float *var,
                                 float *cov, float *samples, int32_t *status, int32_t *cov_status);
+
+/* Leave-one-out / leave-group-out predictive distribution of the TRAINING observations: how well the fitted model predicts the
+ * data it was fitted to, without a refit.  The reference has no such output; the definition is the refit restated in
+ * tests/loo_ref.py.  With U = L^-T and alpha = K^-1 y of the one factorisation per patient and, for a held-out index set B,
+ * M = (K^-1)_BB = U_B U_B^T:
+ *   cov(y_B | rest) = M^-1,  mean(y_B | rest) = y_B - M^-1 alpha_B,
+ *   log p(y_B | rest) = -1/2 alpha_B^T M^-1 alpha_B + 1/2 log det M - |B|/2 log 2 pi      (Rasmussen & Williams 5.4.2 for |B| = 1).
+ * nbatch, slots, theta, status as medgp_posterior_batch (one factorisation per patient, no n > 2 guard; status[b] = jitter rounds
+ * or -1).  With n_b the observation count of slots[b], the per-observation arrays are concatenated by patient in call order, in the
+ * caller's observation order.
+ *   group == NULL: every observation is its own group (classic LOO); ngroups is ignored, G_b = n_b.
+ *   group != NULL: group[i] in [-1, ngroups[b]); -1 = never held out (always conditioned on; its mean and var are NaN).  The
+ *     patient's meta as group with ngroups[b] = D is leave-one-covariate-out.  An id outside the range: MEDGP_ERR_ARG before
+ *     any device work.
+ *   mean[i], var[i]: mean and variance of y_i (noise included) given all observations of the patient outside i's group.
+ *   lpd: sum_b G_b entries, patient b's at sum_{a<b} G_a, one per group id (observation order for group == NULL): the joint log
+ *     density of the group's held-out values; 0.0 for an empty group.  total[b]: the sum of the patient's lpd in group-id order
+ *     (the LOO / LGO log pseudo-likelihood).
+ *   group_status: laid out as lpd; 0 ok, -1 when the factorisation of M met a pivot <= 0 or NaN (no jitter loop here, as for
+ *     cov_status; impossible in exact arithmetic): the group's outputs are NaN then.
+ * Any of mean, var, lpd, total, group_status may be NULL, but not all of mean, var, lpd and total.  A patient with
+ * status[b] < 0 gets NaN everywhere and group_status -1.
+ * log 2 pi uses the context's pi (medgp_set_pi): one group holding all n observations gives lpd = -nlml of medgp_nlml_grad
+ * without a prior.  Priors play no part.  After k jitter rounds every quantity is that of the matrix that was factored,
+ * K + k diag(sigma^2).  A group's outputs depend only on the patient, theta and the group's members: not on the labels, the
+ * other groups, the batch-mates (route pinned) or the launch chunks.  The blocks of a launch chunk (2 m'^2 + 2 m' doubles per
+ * group of more than one observation, m' = its size rounded up to 64) stay within MEDGP_POSTERIOR_BUDGET_GB; a single group
+ * beyond it fails with MEDGP_ERR_CAPACITY, as does a call whose per-entry matrices exceed the memory budget.  M is factored by
+ * one workgroup per group.  medgp_get_factor is valid afterwards (the call forms alpha and L^-1).  All pointers are HOST memory. */
+int medgp_loo_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int32_t *group,
+                    const int32_t *ngroups, float *mean, float *var, double *lpd, double *total, int32_t *status,
+                    int32_t *group_status);
 
 /* Cohort statistics, the step after training: for each of nseries independent sample series
  * (series s = data[off[s] .. off[s] + cnt[s])) the Gaussian kernel density estimate with Silverman's bandwidth evaluated AT the

@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at",
 ]
 
@@ -94,6 +94,7 @@ def load():
     lib.medgp_fit_predict_batch.argtypes = [vp, C.c_int, i32p, dp, i32p, fp, fp, fp, i32p]
     lib.medgp_posterior_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, i32p]
     lib.medgp_posterior_joint_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, fp, fp, fp, fp, i32p, i32p]
+    lib.medgp_loo_batch.argtypes = [vp, C.c_int, i32p, dp, i32p, i32p, fp, fp, dp, dp, i32p, i32p]
     lib.medgp_synchronize.argtypes = [vp]
     lib.medgp_profile_enable.argtypes = [vp, C.c_int]
     lib.medgp_profile_num_kernels.restype = C.c_int
@@ -158,6 +159,7 @@ class Context:
         self._h = h
         self.kernel_index, self.Q, self.D, self.R, self.device = kernel_index, Q, D, R, device
         self.H = self._lib.medgp_num_hyp(h)
+        self._slot_n, self._slot_meta = {}, {}   # n and meta of the patient in each slot (loo() lays out its outputs by them)
 
     def _chk(self, rc):
         if rc != 0:
@@ -202,6 +204,11 @@ class Context:
         meta = None if meta is None else np.ascontiguousarray(meta, dtype=np.int32)
         self._chk(self._lib.medgp_set_patient(self._h, int(slot), int(t.shape[0]), _ptr(meta, C.c_int32),
                                               _ptr(t, C.c_float), _ptr(y, C.c_float)))
+        self._remember(int(slot), meta, int(t.shape[0]))
+
+    def _remember(self, slot, meta, n):
+        self._slot_n[slot] = n
+        self._slot_meta[slot] = None if meta is None else np.array(meta, dtype=np.int32)
 
     def set_patients(self, slots, patients):
         """Packed upload: patients = list of (meta, t, y); one H2D transfer, no device wait."""
@@ -216,6 +223,8 @@ class Context:
             meta = np.ascontiguousarray(np.concatenate([np.asarray(p[0], dtype=np.int32) for p in patients]), dtype=np.int32)
         self._chk(self._lib.medgp_set_patients(self._h, len(ns), _ptr(slots, C.c_int32), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
                                                _ptr(meta, C.c_int32), _ptr(t, C.c_float), _ptr(y, C.c_float)))
+        for s, p in zip(slots, patients):
+            self._remember(int(s), p[0], int(np.asarray(p[1]).shape[0]))
 
     def set_prior(self, slot, flag=None, type=None, is_exp=None, p0=None, p1=None):
         if flag is None:
@@ -473,6 +482,79 @@ class Context:
             out.append((mean[a:e].copy(), var[a:e].copy(), cv[int(coff[b]):int(coff[b + 1])].reshape(m, m).copy() if cov else None,
                         sm[a:e].copy() if nsamp else None))
         return out, st, cst
+
+    def _loo_args(self, slots, theta, groups):
+        """the argument checks of loo(): (slots, theta [nbatch, H], observation counts, group ids or None, groups per patient or
+        None); the observation counts and covariates of the patients are those set_patient[s] saw."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        nb = slots.shape[0]
+        if nb < 1:
+            raise ValueError("no patient")
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.size != nb * self.H:
+            raise ValueError(f"theta has {theta.size} values, expected {nb} x {self.H}")
+        theta = theta.reshape(nb, self.H)
+        missing = [int(s) for s in slots if int(s) not in self._slot_n]
+        if missing:
+            raise ValueError(f"slots {missing} hold no patient set through this Context")
+        ns = [self._slot_n[int(s)] for s in slots]
+        if groups is None:
+            return slots, theta, ns, None, None
+        if isinstance(groups, str):
+            if groups != "covariate":
+                raise ValueError(f"groups = {groups!r}: expected a list of int arrays, None or 'covariate'")
+            D = self.D if self.kernel_index == KERNEL_LMC_SM else 1
+            metas = [self._slot_meta[int(s)] for s in slots]
+            gs = [np.zeros(n, dtype=np.int32) if m is None else np.ascontiguousarray(m, dtype=np.int32).ravel() for m, n in zip(metas, ns)]
+            ng = np.full(nb, D, dtype=np.int32)
+        else:
+            if len(groups) != nb:
+                raise ValueError(f"{len(groups)} group arrays for {nb} patients")
+            gs = []
+            for b, x in enumerate(groups):
+                x = np.asarray(x)
+                if x.size and not np.issubdtype(x.dtype, np.integer):
+                    raise ValueError(f"patient {b}: group ids of dtype {x.dtype}, expected integers")
+                gs.append(np.ascontiguousarray(x, dtype=np.int32).ravel())
+            ng = np.array([int(x.max()) + 1 if x.size and x.max() >= 0 else 0 for x in gs], dtype=np.int32)
+        for b, (x, n) in enumerate(zip(gs, ns)):
+            if x.shape[0] != n:
+                raise ValueError(f"patient {b}: {x.shape[0]} group ids for {n} observations")
+            if x.size and (x.min() < -1 or x.max() >= ng[b]):
+                raise ValueError(f"patient {b}: group ids outside [-1, {int(ng[b])})")
+        return slots, theta, ns, gs, ng
+
+    def loo(self, slots, theta, groups=None):
+        """medgp_loo_batch: the leave-one-out / leave-group-out predictive distribution of the patients' own observations.
+        slots [nbatch], theta [nbatch, H]; groups: None (every observation its own group: classic LOO), a list of one int array
+        of group ids per patient (-1: never held out; the number of groups of a patient is its largest id + 1) or "covariate"
+        (each patient's meta: leave-one-covariate-out, D groups).  Returns ([(mean[n], var[n], lpd[G], total) per patient],
+        status, [group_status[G] per patient]): mean / var of y_i given the observations outside i's group, lpd the joint log
+        density of each group's held-out values, total their sum (the log pseudo-likelihood)."""
+        slots, theta, ns, gs, ng = self._loo_args(slots, theta, groups)
+        nb = slots.shape[0]
+        Gs = np.array(ns if gs is None else ng, dtype=np.int64)
+        ooff = np.zeros(nb + 1, dtype=np.int64)
+        ooff[1:] = np.cumsum(ns)
+        goff = np.zeros(nb + 1, dtype=np.int64)
+        goff[1:] = np.cumsum(Gs)
+        NO, NG = int(ooff[-1]), int(goff[-1])
+        grp = None if gs is None else np.ascontiguousarray(np.concatenate(gs) if NO else np.zeros(1), dtype=np.int32)
+        mean = np.empty(max(NO, 1), dtype=np.float32)
+        var = np.empty(max(NO, 1), dtype=np.float32)
+        lpd = np.empty(max(NG, 1), dtype=np.float64)
+        tot = np.empty(nb, dtype=np.float64)
+        st = np.empty(nb, dtype=np.int32)
+        gst = np.empty(max(NG, 1), dtype=np.int32)
+        self._chk(self._lib.medgp_loo_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), _ptr(grp, C.c_int32),
+                                            _ptr(ng, C.c_int32), _ptr(mean, C.c_float), _ptr(var, C.c_float), _ptr(lpd, C.c_double),
+                                            _ptr(tot, C.c_double), _ptr(st, C.c_int32), _ptr(gst, C.c_int32)))
+        out, gstat = [], []
+        for b in range(nb):
+            a, e, ga, ge = int(ooff[b]), int(ooff[b + 1]), int(goff[b]), int(goff[b + 1])
+            out.append((mean[a:e].copy(), var[a:e].copy(), lpd[ga:ge].copy(), float(tot[b])))
+            gstat.append(gst[ga:ge].copy())
+        return out, st, gstat
 
     def synchronize(self):
         self._chk(self._lib.medgp_synchronize(self._h))

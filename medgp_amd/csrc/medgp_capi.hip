@@ -13,6 +13,7 @@
 #include "kernels_cohort.h"
 #include "kernels_posterior.h"
 #include "kernels_posterior_joint.h"
+#include "kernels_loo.h"
 
 #include <algorithm>
 #include <chrono>
@@ -26,8 +27,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -91,6 +92,7 @@ struct Arena {
     char *base = nullptr;
     size_t bytes = 0;    // size of the block
 };
+enum LooBuf { LOO_SINGLES = 0, LOO_ROWS, LOO_GROUPS, LOO_PAIRS, LOO_JOBS, LOO_BLOCKS, LOO_MEAN, LOO_VAR, LOO_LPD, LOO_GSTAT, LOO_BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -192,6 +194,10 @@ struct medgp_ctx {
     float *d_joint_cov = nullptr, *d_joint_samp = nullptr;
     int *d_joint_cstat = nullptr;
     size_t joint_cap_pats = 0, joint_cap_pairs = 0, joint_cap_blks = 0, joint_cap_C = 0, joint_cap_eps = 0, joint_cap_cov = 0, joint_cap_samp = 0, joint_cap_cstat = 0;   // bytes
+    // medgp_loo_batch buffers (same rules): the singleton / index-list / group / tile tables of the call, the blocks of one launch
+    // chunk, the call's outputs
+    void *d_loo[LOO_BUF_COUNT] = {};
+    size_t loo_cap[LOO_BUF_COUNT] = {};   // bytes
     // profiling
     bool profiling = false;
     int profile_only = -1;    // >= 0: only launches of this kernel id are bracketed (medgp_profile_enable(ctx, 2 + id))
@@ -266,6 +272,11 @@ void free_all(medgp_ctx *c) {
                      (void **)&c->d_joint_C, (void **)&c->d_joint_eps, (void **)&c->d_joint_cov, (void **)&c->d_joint_samp, (void **)&c->d_joint_cstat}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
+    }
+    for (int i = 0; i < LOO_BUF_COUNT; i++) {
+        if (c->d_loo[i]) (void)hipFree(c->d_loo[i]);
+        c->d_loo[i] = nullptr;
+        c->loo_cap[i] = 0;
     }
     c->post_cap_pts = c->post_cap_m2 = c->post_cap_mean = c->post_cap_var = c->post_cap_parts = c->post_cap_tiles = c->post_cap_work = 0;
     c->joint_cap_pats = c->joint_cap_pairs = c->joint_cap_blks = c->joint_cap_C = c->joint_cap_eps = c->joint_cap_cov = c->joint_cap_samp = c->joint_cap_cstat = 0;
@@ -946,7 +957,7 @@ int run_pipeline(medgp_ctx *c, int nbatch, int max_n, const double *theta_dev, i
 
 extern "C" {
 
-int medgp_abi_version(void) { return 5; }
+int medgp_abi_version(void) { return 6; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2157,6 +2168,182 @@ int medgp_posterior_joint_batch(medgp_ctx *c, int nbatch, const int32_t *slots, 
                                 float *cov, float *samples, int32_t *status, int32_t *cov_status) {
     const JointReq jq{nsamp, eps, cov, samples, cov_status};
     return posterior_impl(c, nbatch, slots, theta, offsets, meta2, t2, mean, var, nullptr, status, &jq);
+}
+
+// Leave-one-out / leave-group-out predictions of the training observations (kernels_loo.h).  ONE pipeline run in the grouped order
+// (the outputs are permutation-equivariant: the caller's group ids are mapped through h_perm and the results scattered back), then
+// per size class k_loo_diag over its singleton groups and, per launch chunk of larger groups whose blocks fit the posterior budget,
+// k_loo_gram / k_postfactor / k_loo_solve.  Singletons never get a block.  The outputs are filled with NaN on the device first: what no
+// kernel writes (observations never held out, failed patients, failed groups) stays NaN.
+int medgp_loo_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int32_t *group, const int32_t *ngroups,
+                    float *mean, float *var, double *lpd, double *total, int32_t *status, int32_t *group_status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
+    if (!mean && !var && !lpd && !total) return fail(c, MEDGP_ERR_ARG, "none of mean, var, lpd and total asked for");
+    if (group && !ngroups) return fail(c, MEDGP_ERR_ARG, "ngroups is NULL with group ids");
+    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
+    if (nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
+    std::vector<int64_t> ooff(nbatch + 1, 0), goff(nbatch + 1, 0);   // first observation / first group of patient b in the call
+    for (int b = 0; b < nbatch; b++) {
+        const int s = slots[b];
+        if (s < 0 || s >= c->max_slots || c->h_n[s] < 0) return fail(c, MEDGP_ERR_ARG, "slots[%d] = %d is not a resident patient", b, s);
+        if (group && ngroups[b] < 0) return fail(c, MEDGP_ERR_ARG, "ngroups[%d] = %d", b, ngroups[b]);
+        ooff[b + 1] = ooff[b] + c->h_n[s];
+        goff[b + 1] = goff[b] + (group ? ngroups[b] : c->h_n[s]);
+    }
+    const int64_t NO = ooff[nbatch], NG = goff[nbatch];
+    if (NO > (int64_t)INT32_MAX || NG > (int64_t)INT32_MAX) return fail(c, MEDGP_ERR_ARG, "%lld observations in %lld groups in one call", (long long)NO, (long long)NG);
+    if (group)
+        for (int b = 0; b < nbatch; b++)
+            for (int64_t i = ooff[b]; i < ooff[b + 1]; i++)
+                if (group[i] < -1 || group[i] >= ngroups[b])
+                    return fail(c, MEDGP_ERR_ARG, "group[%lld] = %d outside [-1, %d) (patient %d)", (long long)i, group[i], ngroups[b], b);
+    HIPCHK(c, hipSetDevice(c->device));
+    int max_n = 0, rc;
+    if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
+    const bool want_lpd = lpd || total;
+    // tables: per size class its singletons; chunks of larger groups (whole groups, blocks within the budget) with their tile pairs
+    // and solve jobs -- one workgroup per table row, so ragged groups cost no idle workgroups
+    struct Chunk { const SizeClass *k; int g0, ng, pair0, npair, job0, njob; };
+    struct ClassSingles { const SizeClass *k; int s0, ns; };
+    std::vector<LooSingle> singles;
+    std::vector<ClassSingles> csing;
+    std::vector<LooRow> rows;
+    std::vector<JointPat> groups;
+    std::vector<JointTile> pairs, jobs;
+    std::vector<Chunk> chunks;
+    std::vector<int> gsize((size_t)NG, 0), cnt, start, fill;
+    size_t blk_need = 0;
+    for (const SizeClass &k : c->plan.cls) {
+        const int s0 = (int)singles.size();
+        Chunk ch{&k, (int)groups.size(), 0, (int)pairs.size(), 0, (int)jobs.size(), 0};
+        size_t cdbl = 0;
+        auto close = [&]() {
+            if (ch.ng == 0) return;
+            chunks.push_back(ch);
+            blk_need = std::max(blk_need, cdbl * sizeof(double));
+            ch.g0 += ch.ng; ch.ng = 0; ch.pair0 += ch.npair; ch.npair = 0; ch.job0 += ch.njob; ch.njob = 0;
+            cdbl = 0;
+        };
+        for (int i = k.b0; i < k.b0 + k.count; i++) {
+            const int b = c->plan.order[i], slot = slots[b], n = c->plan.en[i], G = (int)(goff[b + 1] - goff[b]);
+            const bool ident = c->h_perm_identity[slot] != 0;
+            const std::vector<int> &perm = c->h_perm[slot];
+            auto gid_of = [&](int r, int *cobs) { *cobs = ident ? r : perm[r]; return group ? group[ooff[b] + *cobs] : *cobs; };
+            cnt.assign(G, 0); start.assign(G, -1); fill.assign(G, 0);
+            int co;
+            for (int r = 0; r < n; r++) { const int gid = gid_of(r, &co); if (gid >= 0) cnt[gid]++; }
+            for (int gid = 0; gid < G; gid++) {
+                gsize[goff[b] + gid] = cnt[gid];
+                if (cnt[gid] < 2) continue;
+                const size_t need = loo_block_doubles(cnt[gid]) * sizeof(double);
+                if (need > c->posterior_budget)
+                    return fail(c, MEDGP_ERR_CAPACITY, "patient %d: group %d of %d observations needs %zu MB at once, the budget is %zu MB (MEDGP_POSTERIOR_BUDGET_GB)",
+                                b, gid, cnt[gid], need >> 20, c->posterior_budget >> 20);
+                if (cdbl * sizeof(double) + need > c->posterior_budget) close();
+                const int gidx = (int)groups.size(), nt = medgp_roundup(cnt[gid], 64) / 64;
+                start[gid] = (int)rows.size();
+                rows.resize(rows.size() + cnt[gid]);
+                groups.push_back({i - k.b0, (int)(goff[b] + gid), start[gid], cnt[gid], 0, 0, (long long)cdbl, 0});
+                for (int I = 0; I < nt; I++)
+                    for (int J = 0; J <= I; J++) pairs.push_back({gidx, I, J, 0});
+                int nj = 0;
+                if (var) for (int I = 0; I < nt; I++, nj++) jobs.push_back({gidx, I, 0, 0});
+                if (mean || want_lpd) { jobs.push_back({gidx, 0, 1, 0}); nj++; }
+                ch.ng++; ch.npair += nt * (nt + 1) / 2; ch.njob += nj;
+                cdbl += loo_block_doubles(cnt[gid]);
+            }
+            for (int r = 0; r < n; r++) {   // (rows ascending: the index list of a group is sorted, stably)
+                const int gid = gid_of(r, &co);
+                if (gid < 0) continue;
+                if (cnt[gid] == 1) singles.push_back({i - k.b0, r, (int)(ooff[b] + co), (int)(goff[b] + gid)});
+                else rows[start[gid] + fill[gid]++] = {r, (int)(ooff[b] + co)};
+            }
+        }
+        close();
+        csing.push_back({&k, s0, (int)singles.size() - s0});
+    }
+    void **D = c->d_loo;
+    size_t *cap = c->loo_cap;
+    const size_t NOz = (size_t)std::max<int64_t>(NO, 1), NGz = (size_t)std::max<int64_t>(NG, 1);
+    if ((rc = post_buf(c, &D[LOO_MEAN], &cap[LOO_MEAN], NOz * sizeof(float)))) return rc;
+    if ((rc = post_buf(c, &D[LOO_VAR], &cap[LOO_VAR], NOz * sizeof(float)))) return rc;
+    if ((rc = post_buf(c, &D[LOO_LPD], &cap[LOO_LPD], NGz * sizeof(double)))) return rc;
+    if ((rc = post_buf(c, &D[LOO_GSTAT], &cap[LOO_GSTAT], NGz * sizeof(int)))) return rc;
+    if ((rc = post_buf(c, &D[LOO_SINGLES], &cap[LOO_SINGLES], singles.size() * sizeof(LooSingle)))) return rc;
+    if ((rc = post_buf(c, &D[LOO_ROWS], &cap[LOO_ROWS], rows.size() * sizeof(LooRow)))) return rc;
+    if ((rc = post_buf(c, &D[LOO_GROUPS], &cap[LOO_GROUPS], groups.size() * sizeof(JointPat)))) return rc;
+    if ((rc = post_buf(c, &D[LOO_PAIRS], &cap[LOO_PAIRS], pairs.size() * sizeof(JointTile)))) return rc;
+    if ((rc = post_buf(c, &D[LOO_JOBS], &cap[LOO_JOBS], jobs.size() * sizeof(JointTile)))) return rc;
+    if ((rc = post_buf(c, &D[LOO_BLOCKS], &cap[LOO_BLOCKS], blk_need))) return rc;
+    float *d_mean = (float *)D[LOO_MEAN], *d_var = (float *)D[LOO_VAR];
+    double *d_lpd = (double *)D[LOO_LPD], *d_blocks = (double *)D[LOO_BLOCKS];
+    int *d_gstat = (int *)D[LOO_GSTAT];
+    const LooSingle *d_singles = (const LooSingle *)D[LOO_SINGLES];
+    const LooRow *d_rows = (const LooRow *)D[LOO_ROWS];
+    const JointPat *d_groups = (const JointPat *)D[LOO_GROUPS];
+    const JointTile *d_pairs = (const JointTile *)D[LOO_PAIRS], *d_jobs = (const JointTile *)D[LOO_JOBS];
+    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_mean, 0xFF, NOz * sizeof(float), c->stream));   // all ones: NaN, float and double
+    HIPCHK(c, hipMemsetAsync(d_var, 0xFF, NOz * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(d_lpd, 0xFF, NGz * sizeof(double), c->stream));
+    HIPCHK(c, hipMemsetAsync(d_gstat, 0, NGz * sizeof(int), c->stream));
+    if (!singles.empty()) HIPCHK(c, hipMemcpyAsync(D[LOO_SINGLES], singles.data(), singles.size() * sizeof(LooSingle), hipMemcpyHostToDevice, c->stream));
+    if (!groups.empty()) {
+        HIPCHK(c, hipMemcpyAsync(D[LOO_ROWS], rows.data(), rows.size() * sizeof(LooRow), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(D[LOO_GROUPS], groups.data(), groups.size() * sizeof(JointPat), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(D[LOO_PAIRS], pairs.data(), pairs.size() * sizeof(JointTile), hipMemcpyHostToDevice, c->stream));
+        if (!jobs.empty()) HIPCHK(c, hipMemcpyAsync(D[LOO_JOBS], jobs.data(), jobs.size() * sizeof(JointTile), hipMemcpyHostToDevice, c->stream));
+    }
+    // factor, U = L^-T and alpha = K^-1 y of every entry: the ONE pipeline run of the call (medgp_get_factor is valid afterwards)
+    if ((rc = run_pipeline(c, nbatch, max_n, c->d_theta, 0, true, 1, nullptr, nullptr, nullptr, false, true))) return rc;
+    const double log2pi = std::log(2.0 * c->pi);
+    for (const ClassSingles &s : csing) {
+        if (s.ns == 0) continue;
+        Launcher l(c, KID_LOO_DIAG);
+        hipLaunchKernelGGL(k_loo_diag, dim3((s.ns + 3) / 4), dim3(256), 0, c->stream, class_view(c, c->plan, *s.k), d_singles + s.s0, s.ns, log2pi,
+                           mean ? d_mean : nullptr, var ? d_var : nullptr, want_lpd ? d_lpd : nullptr);
+    }
+    for (const Chunk &ch : chunks) {   // chunks reuse the blocks in stream order
+        const MedgpDev V = class_view(c, c->plan, *ch.k);
+        {
+            Launcher l(c, KID_LOO_GRAM);
+            hipLaunchKernelGGL(k_loo_gram, dim3(ch.npair), dim3(256), 0, c->stream, V, d_groups, d_pairs + ch.pair0, d_rows, d_blocks);
+        }
+        {
+            Launcher l(c, KID_POSTFACTOR);
+            hipLaunchKernelGGL(k_postfactor, dim3(ch.ng), dim3(256), 0, c->stream, V, d_groups + ch.g0, d_blocks, d_gstat);
+        }
+        if (ch.njob > 0) {
+            Launcher l(c, KID_LOO_SOLVE);
+            hipLaunchKernelGGL(k_loo_solve, dim3(ch.njob), dim3(256), 0, c->stream, V, d_groups, d_jobs + ch.job0, d_rows, d_blocks, d_gstat, log2pi,
+                               mean ? d_mean : nullptr, var ? d_var : nullptr, want_lpd ? d_lpd : nullptr);
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> hl(lpd ? 0 : (want_lpd ? (size_t)NG : 0));
+    double *lp = lpd ? lpd : hl.data();
+    std::vector<int> st(nbatch, 0), gst((size_t)NG, 0);
+    if (mean && NO > 0) HIPCHK(c, hipMemcpyAsync(mean, d_mean, sizeof(float) * NO, hipMemcpyDeviceToHost, c->stream));
+    if (var && NO > 0) HIPCHK(c, hipMemcpyAsync(var, d_var, sizeof(float) * NO, hipMemcpyDeviceToHost, c->stream));
+    if (want_lpd && NG > 0) HIPCHK(c, hipMemcpyAsync(lp, d_lpd, sizeof(double) * NG, hipMemcpyDeviceToHost, c->stream));
+    if (NG > 0) HIPCHK(c, hipMemcpyAsync(gst.data(), d_gstat, sizeof(int) * NG, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < nbatch; i++) {
+        const int b = c->plan.order[i];   // internal order -> the caller's
+        const bool ok = st[i] >= 0;
+        if (status) status[b] = st[i];
+        double sum = 0.0;
+        for (int64_t g = goff[b]; g < goff[b + 1]; g++) {
+            if (group_status) group_status[g] = (!ok || gst[g] < 0) ? -1 : 0;
+            if (!want_lpd) continue;
+            if (ok && gsize[g] == 0) lp[g] = 0.0;   // an empty group
+            sum += lp[g];                            // (group-id order)
+        }
+        if (total) total[b] = ok ? sum : (double)NAN;
+    }
+    return MEDGP_OK;
 }
 
 #ifdef MEDGP_STAMPS
