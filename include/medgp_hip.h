@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 6: medgp_loo_batch (5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 7: medgp_loo_grad (6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -300,6 +300,32 @@ int medgp_posterior_joint_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots
 int medgp_loo_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int32_t *group,
                     const int32_t *ngroups, float *mean, float *var, double *lpd, double *total, int32_t *status,
                     int32_t *group_status);
+
+/* The negative leave-one-out log pseudo-likelihood as a training objective, with its gradient in the hyper-parameters: the second
+ * model-selection criterion of a GP beside the marginal likelihood (Rasmussen & Williams 5.4.2).  The reference has no such output;
+ * the definition is the long-double restatement in tests/loo_grad_truth.py.  With
+ *   P = K^-1,  alpha = P y,  d_i = P_ii,  u_i = alpha_i / d_i,  s_i = (1 + alpha_i^2 / d_i) / d_i,  v = P u,
+ *   log p(y_i | y_-i) = 1/2 log d_i - 1/2 alpha_i^2 / d_i - 1/2 log 2 pi,
+ *   J = - sum_i log p(y_i | y_-i),
+ *   dJ / d theta_h = 1/2 tr(W_loo dK / d theta_h),   W_loo = P diag(s) P - (alpha v^T + v alpha^T)       (from R&W eq. 5.13):
+ * the marginal-likelihood gradient with W_loo in the place of W = K^-1 - alpha alpha^T.
+ * nbatch, slots, theta, status as medgp_loo_batch (one factorisation per patient, no n > 2 guard; status[b] = jitter rounds or -1).
+ *   obj[b] = J plus the prior term exactly as medgp_nlml_grad adds it for that slot; without a prior it is -total[b] of
+ *     medgp_loo_batch(group = NULL).  log 2 pi uses the context's pi (medgp_set_pi).
+ *   grad[b * H ..]: dJ / d theta in theta order, the prior's gradient contribution applied as in medgp_nlml_grad (a clamp prior
+ *     zeroes the component).
+ *   flag_grad: 0 = the objective only (grad may be NULL; P diag(s) P is never formed), 1 = objective and gradient; any other
+ *     bit, or grad == NULL with flag_grad = 1: MEDGP_ERR_ARG before any device work.
+ * After k jitter rounds every quantity is that of the matrix that was factored, K + k diag(sigma^2), and the W -> gradient
+ * mapping is unchanged: the noise gradient is not scaled by 1 + k (as for medgp_nlml_grad).  A patient with status[b] < 0 gets
+ * NaN obj and grad.  All three covariance families; Q <= 16 only: Q > 16 returns MEDGP_ERR_ARG (the generic route of
+ * medgp_nlml_grad keeps the full W in the very buffer that holds P here), and MEDGP_V0 is not honoured by this call.  A call
+ * whose per-entry matrices exceed the memory budget fails with MEDGP_ERR_CAPACITY, as medgp_loo_batch does.  With the route
+ * pinned a patient's obj and grad bits do not depend on its batch-mates or their order: no atomics, every sum in a fixed order.
+ * medgp_get_factor is VALID afterwards: the call forms alpha and L^-1 and leaves both untouched (P overwrites the factor L,
+ * which medgp_get_factor does not read).  All pointers are HOST memory. */
+int medgp_loo_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int flag_grad, double *obj,
+                   double *grad, int32_t *status);
 
 /* Cohort statistics, the step after training: for each of nseries independent sample series
  * (series s = data[off[s] .. off[s] + cnt[s])) the Gaussian kernel density estimate with Silverman's bandwidth evaluated AT the

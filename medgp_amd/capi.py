@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at",
 ]
 
@@ -95,6 +95,7 @@ def load():
     lib.medgp_posterior_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, i32p]
     lib.medgp_posterior_joint_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, fp, fp, fp, fp, i32p, i32p]
     lib.medgp_loo_batch.argtypes = [vp, C.c_int, i32p, dp, i32p, i32p, fp, fp, dp, dp, i32p, i32p]
+    lib.medgp_loo_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, i32p]
     lib.medgp_synchronize.argtypes = [vp]
     lib.medgp_profile_enable.argtypes = [vp, C.c_int]
     lib.medgp_profile_num_kernels.restype = C.c_int
@@ -555,6 +556,20 @@ class Context:
             out.append((mean[a:e].copy(), var[a:e].copy(), lpd[ga:ge].copy(), float(tot[b])))
             gstat.append(gst[ga:ge].copy())
         return out, st, gstat
+
+    def loo_grad(self, slots, theta, flag_grad=True):
+        """medgp_loo_grad: the negative leave-one-out log pseudo-likelihood (plus the prior term, as nlml_grad) and its gradient
+        in theta.  slots [nbatch], theta [nbatch, H].  Returns (obj[nbatch], grad[nbatch, H] or None, status[nbatch])."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(slots.shape[0], self.H)
+        nb = slots.shape[0]
+        flag = int(flag_grad)
+        obj = np.empty(nb)
+        grad = np.empty((nb, self.H)) if flag & 1 else None
+        status = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_loo_grad(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), flag,
+                                           _ptr(obj, C.c_double), _ptr(grad, C.c_double), _ptr(status, C.c_int32)))
+        return obj, grad, status
 
     def synchronize(self):
         self._chk(self._lib.medgp_synchronize(self._h))

@@ -214,7 +214,7 @@ __device__ inline double sym_get(const double *S, int D, int d, int e) { return 
 
 __global__ void __launch_bounds__(256) k_epilogue(MedgpDev L, const double *__restrict__ theta, int flag_grad, int from_slab,
                                                   double *__restrict__ nlml_out, double *__restrict__ grad_out,
-                                                  int *__restrict__ status_out) {
+                                                  int *__restrict__ status_out, int loo_objective = 0) {
     __shared__ double red2[MEDGP_EPI_PARTS][256];   // per-chunk partial sums of the prior log-density
     // LDS copies of S_q (all q) and of A for the Q D R gradients dA_q = S_q A_q (each a D-term dot product whose
     // operands otherwise come from global memory one dependent pair at a time); used when they fit
@@ -424,6 +424,7 @@ __global__ void __launch_bounds__(256) k_epilogue(MedgpDev L, const double *__re
         }
         double logdet = L.scal[b * 4 + 0], quad = L.scal[b * 4 + 1];
         double nlml = quad / 2.0 + logdet + n * log(2. * L.pi) / 2.0;   // ref: c_inference_exact.cpp:149-152
+        if (loo_objective) nlml = L.scal[b * 4 + 2];   // medgp_loo_grad: k_loo_vec left the negative LOO log pseudo-likelihood there
         nlml_out[pos] = nlml - lp;
     }
 }

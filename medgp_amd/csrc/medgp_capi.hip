@@ -14,6 +14,7 @@
 #include "kernels_posterior.h"
 #include "kernels_posterior_joint.h"
 #include "kernels_loo.h"
+#include "kernels_loo_grad.h"
 
 #include <algorithm>
 #include <chrono>
@@ -27,8 +28,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -92,7 +93,7 @@ struct Arena {
     char *base = nullptr;
     size_t bytes = 0;    // size of the block
 };
-enum LooBuf { LOO_SINGLES = 0, LOO_ROWS, LOO_GROUPS, LOO_PAIRS, LOO_JOBS, LOO_BLOCKS, LOO_MEAN, LOO_VAR, LOO_LPD, LOO_GSTAT, LOO_BUF_COUNT };
+enum LooBuf { LOO_SINGLES = 0, LOO_ROWS, LOO_GROUPS, LOO_PAIRS, LOO_JOBS, LOO_BLOCKS, LOO_MEAN, LOO_VAR, LOO_LPD, LOO_GSTAT, LOO_GVEC, LOO_BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -195,7 +196,7 @@ struct medgp_ctx {
     int *d_joint_cstat = nullptr;
     size_t joint_cap_pats = 0, joint_cap_pairs = 0, joint_cap_blks = 0, joint_cap_C = 0, joint_cap_eps = 0, joint_cap_cov = 0, joint_cap_samp = 0, joint_cap_cstat = 0;   // bytes
     // medgp_loo_batch buffers (same rules): the singleton / index-list / group / tile tables of the call, the blocks of one launch
-    // chunk, the call's outputs
+    // chunk, the call's outputs; LOO_GVEC: the per-entry vectors [u | s | v | log p] of medgp_loo_grad
     void *d_loo[LOO_BUF_COUNT] = {};
     size_t loo_cap[LOO_BUF_COUNT] = {};   // bytes
     // profiling
@@ -957,7 +958,7 @@ int run_pipeline(medgp_ctx *c, int nbatch, int max_n, const double *theta_dev, i
 
 extern "C" {
 
-int medgp_abi_version(void) { return 6; }
+int medgp_abi_version(void) { return 7; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2343,6 +2344,81 @@ int medgp_loo_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double
         }
         if (total) total[b] = ok ? sum : (double)NAN;
     }
+    return MEDGP_OK;
+}
+
+// The negative LOO log pseudo-likelihood and its gradient (kernels_loo_grad.h).  ONE pipeline run in the grouped order (as
+// medgp_loo_batch: factor, U = L^-T, alpha), then per size class, in stream order: k_loo_kinv (P = U U^T into the dead Kmat block),
+// k_loo_vec (u, s, log p; then v = P u and J), k_loo_wgrad (W_loo tiles -> slab, wdiag), and the nlml gradient's own k_slabsum and
+// k_epilogue, the latter told to report J (scal[2]) instead of the nlml.  flag_grad = 0 stops after the first pass of k_loo_vec.
+int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int flag_grad, double *obj, double *grad,
+                   int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || !obj) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
+    if (flag_grad && !grad) return fail(c, MEDGP_ERR_ARG, "grad is NULL with flag_grad set");
+    if (c->Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_loo_grad supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds K^-1 here", c->Q);
+    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
+    if (nbatch < 1 || nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
+    HIPCHK(c, hipSetDevice(c->device));
+    int max_n = 0, rc;
+    if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
+    const BatchPlan &P = c->plan;
+    if ((rc = post_buf(c, &c->d_loo[LOO_GVEC], &c->loo_cap[LOO_GVEC], 4 * P.need_vec * sizeof(double)))) return rc;
+    double *gvec = (double *)c->d_loo[LOO_GVEC];
+    const size_t H = c->H;
+    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
+    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * H * nbatch, hipMemcpyHostToDevice, c->stream));
+    // the generic kernels (MEDGP_V0) keep W where P goes: this call always takes the templated ones
+    const bool v0 = c->use_v0;
+    c->use_v0 = false;
+    rc = run_pipeline(c, nbatch, max_n, c->d_theta, 0, true, 1, nullptr, nullptr, nullptr, false, true);
+    c->use_v0 = v0;
+    if (rc) return rc;
+    const double log2pi = std::log(2.0 * c->pi);
+    for (const SizeClass &k : P.cls) {
+        const MedgpDev V = class_view(c, P, k);
+        double *vec = gvec + 4 * k.off_vec;
+        const int nb = k.count, nt64 = k.nbmax;
+        { Launcher l(c, KID_LOO_VEC); hipLaunchKernelGGL(k_loo_vec, dim3(4 * nt64, nb), dim3(256), 0, c->stream, V, vec, 0, log2pi); }
+        if (!flag_grad) {
+            Launcher l(c, KID_LOO_VEC);
+            hipLaunchKernelGGL(k_loo_vec, dim3(1, nb), dim3(256), 0, c->stream, V, vec, 2, log2pi);
+        } else {
+            bool ragged = false;
+            for (int bb = 1; bb < nb; bb++) ragged = ragged || blocks64(P.en[k.b0 + bb]) != blocks64(P.en[k.b0]);
+            const int wg_tiles = tri(nt64), nbp = (ragged && nb < 64) ? (nb | 1) : nb;   // (k_wgrad's grid)
+            const dim3 tg(std::max(8 * ((nb + 7) / 8), nbp) * wg_tiles), tb(WG_THREADS);
+            { Launcher l(c, KID_LOO_KINV); hipLaunchKernelGGL(k_loo_kinv, tg, tb, 0, c->stream, V, nb, wg_tiles, nbp); }
+            { Launcher l(c, KID_LOO_VEC); hipLaunchKernelGGL(k_loo_vec, dim3(4 * nt64, nb), dim3(256), 0, c->stream, V, vec, 1, log2pi); }
+            {
+                Launcher l(c, KID_LOO_WGRAD);
+#define MEDGP_LWG1(QQ) case QQ: hipLaunchKernelGGL((k_loo_wgrad<QQ, 0>), tg, tb, 0, c->stream, V, vec, nb, wg_tiles, nbp); break;
+#define MEDGP_LWG2(QR) case 8 + QR: hipLaunchKernelGGL((k_loo_wgrad<8, 0>), tg, tb, 0, c->stream, V, vec, nb, wg_tiles, nbp); \
+                                    hipLaunchKernelGGL((k_loo_wgrad<QR, 8>), tg, tb, 0, c->stream, V, vec, nb, wg_tiles, nbp); break;
+                switch (V.Q) {
+                MEDGP_LWG1(1) MEDGP_LWG1(2) MEDGP_LWG1(3) MEDGP_LWG1(4) MEDGP_LWG1(5) MEDGP_LWG1(6) MEDGP_LWG1(7) MEDGP_LWG1(8)
+                MEDGP_LWG2(1) MEDGP_LWG2(2) MEDGP_LWG2(3) MEDGP_LWG2(4) MEDGP_LWG2(5) MEDGP_LWG2(6) MEDGP_LWG2(7) MEDGP_LWG2(8)
+                default: break;   // (not reached: Q <= 16 was checked)
+                }
+#undef MEDGP_LWG1
+#undef MEDGP_LWG2
+            }
+            const int nbins3 = 3 * V.Q * tri(V.D);
+            Launcher l(c, KID_EPILOGUE);
+            hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V);
+        }
+        Launcher l(c, KID_EPILOGUE);
+        const int nparts = (2 * nb >= c->num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
+        hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, c->d_theta, flag_grad, 1, c->d_nlml, c->d_grad, c->d_status_out, 1);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(obj, c->d_nlml, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    if (flag_grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * H, hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_retired(c);
     return MEDGP_OK;
 }
 

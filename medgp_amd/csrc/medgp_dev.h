@@ -60,7 +60,7 @@ struct MedgpDev {
                              // column for U) -- medgp_factor[_batch], medgp_get_factor, k_predict, k_wgrad.  tests/test_parity2_gpu.py
                              // (test_exported_factors_have_exact_zero_triangles) holds the exports to it on both routes.
     double *z, *alpha;       // [batch][ldn]
-    double *scal;            // [batch][4]: logdet, quad, -, -
+    double *scal;            // [batch][4]: logdet, quad, negative LOO log pseudo-likelihood (medgp_loo_grad), -
     int *status;             // [batch]
     int *bn;                 // [batch] n of the entry's patient, written by k_prep (one load instead of the bslot -> pn chain)
     double *epi_lp;          // [batch][MEDGP_EPI_PARTS] prior log-density of each part of k_epilogue's hyper range
