@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 7: medgp_loo_grad (6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 8: medgp_forecast_batch (7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -326,6 +326,44 @@ int medgp_loo_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const doub
  * which medgp_get_factor does not read).  All pointers are HOST memory. */
 int medgp_loo_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int flag_grad, double *obj,
                    double *grad, int32_t *status);
+
+/* Rolling-origin forecasts: every test point predicted from a LEADING block of its patient's observations, all from ONE
+ * factorisation per patient -- what the model says at time t from what was known before t.
+ *   ref: core/gp_regression.cpp:128-214 (GP_Regression::predict), main_one_test.cpp:269-300 (the "past" training sets of the
+ *        reference's test program), medgpc/evaluation/evals.py:7-51 (the scores computed from such predictions;
+ *        medgp_amd/forecast.py restates them)
+ * For a lower-triangular L the first p rows of V = L^-1 K* are L[0:p,0:p]^-1 K*[0:p], and L[0:p,0:p] is the factor of the
+ * leading block K[0:p,0:p]: with z = L^-1 y,
+ *   mean_j = sum_{k < p_j} V[k,j] z[k],   var_j = k** - sum_{k < p_j} V[k,j]^2 + sigma^2_{meta2_j}      (kernels_forecast.h).
+ * nbatch, slots, theta, offsets, meta2, t2 and status mean exactly what they mean for medgp_posterior_batch: one factorisation
+ * per patient, no n > 2 guard, status[b] = jitter rounds or -1, meta2 may be NULL for SE / SM, an empty range of points is allowed.
+ *   prefix[j] in [0, n_b] (b = the patient of point j): point j is predicted from the FIRST prefix[j] observations of patient b
+ *     in the caller's observation order, the order given to medgp_set_patient[s].  The library does not look at the time stamps
+ *     to decide what is "earlier": a caller who uploads in time order gets forecasts, any other order gives the prediction from
+ *     that leading subset.  (A patient not uploaded grouped by output is factored on its caller-order copy.)  A value outside
+ *     the range: MEDGP_ERR_ARG before any device work.  prefix == NULL means prefix[j] = n_b: conditioning on all data, like
+ *     medgp_posterior_batch, but in the caller's order.
+ *   mean[j], var[j]: GP_Regression::predict applied to the training set obs[0:prefix[j]], the noise of the test covariate added
+ *     once.  prefix[j] == 0 is the prior: mean exactly 0.0f, var = float(k** + sigma^2).
+ *   y2, lpd: both NULL or both given (else MEDGP_ERR_ARG).  lpd[j] = -1/2 log(2 pi var_j) - 1/2 (y2_j - mean_j)^2 / var_j, formed
+ *     in fp64 from the fp64 mean and variance before those are rounded to float, with the context's pi (medgp_set_pi) as
+ *     medgp_loo_batch.  Summed over a patient's one-step-ahead points it is the prequential log score.
+ * After k jitter rounds every quantity is that of the matrix that was factored, K + k diag(sigma^2), restricted to the prefix
+ * (the rule of the posterior and LOO calls); a refit of the prefix alone might have needed fewer rounds.  The points of a
+ * patient with status[b] < 0 get NaN mean, var and lpd.  There is NO per-covariate decomposition (parts): it needs alpha of
+ * every prefix, which this route does not form.  A call whose per-entry matrices exceed the memory budget fails with
+ * MEDGP_ERR_CAPACITY, like medgp_posterior_batch; the work rows are chunked within MEDGP_POSTERIOR_BUDGET_GB.
+ * A point's outputs depend on the patient, theta, the point and its prefix alone: not on the other points of the call, their
+ * order, the tile a point lands in, the launch chunk, or -- with the route pinned -- the batch-mates.  var is non-increasing
+ * in prefix[j], exactly.
+ * Accuracy (tests/test_forecast_gpu.py, against a refit of every prefix, tests/forecast_ref.py): mean and var within the
+ * project's bar of 2 fp32 ulps of max(|ref|, 1e-3 S); lpd within B max(1, |ref|), B = 50 x the spread of the two fp64
+ * restatements recorded in tests/golden/forecast_lpd_spread.json (2.8e-13, so B = 1.4e-11).  The tests print the worst
+ * observed errors of every case (pytest -s).
+ * All pointers are HOST memory. */
+int medgp_forecast_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                         const int32_t *meta2, const float *t2, const int32_t *prefix, const float *y2,
+                         float *mean, float *var, double *lpd, int32_t *status);
 
 /* Cohort statistics, the step after training: for each of nseries independent sample series
  * (series s = data[off[s] .. off[s] + cnt[s])) the Gaussian kernel density estimate with Silverman's bandwidth evaluated AT the

@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at",
 ]
 
@@ -96,6 +96,7 @@ def load():
     lib.medgp_posterior_joint_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, fp, fp, fp, fp, i32p, i32p]
     lib.medgp_loo_batch.argtypes = [vp, C.c_int, i32p, dp, i32p, i32p, fp, fp, dp, dp, i32p, i32p]
     lib.medgp_loo_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, i32p]
+    lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
     lib.medgp_synchronize.argtypes = [vp]
     lib.medgp_profile_enable.argtypes = [vp, C.c_int]
     lib.medgp_profile_num_kernels.restype = C.c_int
@@ -428,6 +429,48 @@ class Context:
         for b in range(nb):
             a, e = int(offsets[b]), int(offsets[b + 1])
             out.append((mean[a:e].copy(), var[a:e].copy(), pr[a:e].copy() if parts else None))
+        return out, st
+
+    def forecast(self, slots, theta, meta2_list, t2_list, prefix_list=None, y2_list=None):
+        """medgp_forecast_batch: point j of patient b predicted from the FIRST prefix_list[b][j] observations of the patient in the
+        order they were uploaded (rolling-origin forecasts when that is time order; medgp_amd.forecast.rolling_origin builds the
+        points).  slots, theta, meta2_list, t2_list as posterior(); prefix_list: one int array per patient, values in [0, n_b]
+        (None: all of the patient's data); y2_list: the observed values at the points (None: no lpd).
+        Returns ([(mean[m], var[m], lpd[m] or None) per patient], status)."""
+        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
+        nb = slots.shape[0]
+        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum(cnt)
+        M = int(offsets[-1])
+
+        def per_point(lst, dtype, what):
+            if lst is None:
+                return None
+            if len(lst) != nb:
+                raise ValueError(f"{len(lst)} {what} arrays for {nb} patients")
+            arrs = [np.ascontiguousarray(x, dtype=dtype).ravel() for x in lst]
+            for b, (a, x) in enumerate(zip(arrs, ts)):
+                if a.shape[0] != x.shape[0]:
+                    raise ValueError(f"patient {b}: {a.shape[0]} {what} values for {x.shape[0]} test times")
+            return np.ascontiguousarray(np.concatenate(arrs) if M else np.zeros(1), dtype=dtype)
+
+        pf = per_point(prefix_list, np.int32, "prefix")
+        y2 = per_point(y2_list, np.float32, "y2")
+        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
+        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+        mean = np.empty(max(M, 1), dtype=np.float32)
+        var = np.empty(max(M, 1), dtype=np.float32)
+        lpd = np.empty(max(M, 1), dtype=np.float64) if y2 is not None else None
+        st = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_forecast_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
+                                                 offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
+                                                 _ptr(pf, C.c_int32), _ptr(y2, C.c_float), _ptr(mean, C.c_float), _ptr(var, C.c_float),
+                                                 _ptr(lpd, C.c_double), _ptr(st, C.c_int32)))
+        out = []
+        for b in range(nb):
+            a, e = int(offsets[b]), int(offsets[b + 1])
+            out.append((mean[a:e].copy(), var[a:e].copy(), lpd[a:e].copy() if lpd is not None else None))
         return out, st
 
     def posterior_joint(self, slots, theta, meta2_list, t2_list, eps_list=None, cov=True):

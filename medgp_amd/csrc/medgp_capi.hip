@@ -13,6 +13,7 @@
 #include "kernels_cohort.h"
 #include "kernels_posterior.h"
 #include "kernels_posterior_joint.h"
+#include "kernels_forecast.h"
 #include "kernels_loo.h"
 #include "kernels_loo_grad.h"
 
@@ -28,8 +29,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_FORECAST, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_forecast"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -187,6 +188,10 @@ struct medgp_ctx {
     PostTile *d_post_tiles = nullptr;
     size_t post_cap_pts = 0, post_cap_m2 = 0, post_cap_mean = 0, post_cap_var = 0, post_cap_parts = 0, post_cap_tiles = 0, post_cap_work = 0;   // bytes
     size_t posterior_budget = (size_t)2 << 30;   // MEDGP_POSTERIOR_BUDGET_GB
+    // medgp_forecast_batch buffers (same rules; the rest of the call lives in the posterior buffers above): prefix, y2, lpd of the call
+    int *d_fore_prefix = nullptr;
+    double *d_fore_y2 = nullptr, *d_fore_lpd = nullptr;
+    size_t fore_cap_prefix = 0, fore_cap_y2 = 0, fore_cap_lpd = 0;   // bytes
     // medgp_posterior_joint_batch buffers (same rules): the patient / tile-pair / row-block tables of the call, C and the float
     // covariance blocks of one launch chunk, the call's eps and samples, cov_status
     JointPat *d_joint_pats = nullptr;
@@ -270,7 +275,8 @@ void free_all(medgp_ctx *c) {
     c->retired_bytes = 0;
     for (void **p : {(void **)&c->d_post_t2, (void **)&c->d_post_work, (void **)&c->d_post_m2, (void **)&c->d_post_mean, (void **)&c->d_post_var,
                      (void **)&c->d_post_parts, (void **)&c->d_post_tiles, (void **)&c->d_joint_pats, (void **)&c->d_joint_pairs, (void **)&c->d_joint_blks,
-                     (void **)&c->d_joint_C, (void **)&c->d_joint_eps, (void **)&c->d_joint_cov, (void **)&c->d_joint_samp, (void **)&c->d_joint_cstat}) {
+                     (void **)&c->d_joint_C, (void **)&c->d_joint_eps, (void **)&c->d_joint_cov, (void **)&c->d_joint_samp, (void **)&c->d_joint_cstat,
+                     (void **)&c->d_fore_prefix, (void **)&c->d_fore_y2, (void **)&c->d_fore_lpd}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -281,6 +287,7 @@ void free_all(medgp_ctx *c) {
     }
     c->post_cap_pts = c->post_cap_m2 = c->post_cap_mean = c->post_cap_var = c->post_cap_parts = c->post_cap_tiles = c->post_cap_work = 0;
     c->joint_cap_pats = c->joint_cap_pairs = c->joint_cap_blks = c->joint_cap_C = c->joint_cap_eps = c->joint_cap_cov = c->joint_cap_samp = c->joint_cap_cstat = 0;
+    c->fore_cap_prefix = c->fore_cap_y2 = c->fore_cap_lpd = 0;
 }
 
 int num_cov(int kidx, int Q, int D, int R) {
@@ -958,7 +965,7 @@ int run_pipeline(medgp_ctx *c, int nbatch, int max_n, const double *theta_dev, i
 
 extern "C" {
 
-int medgp_abi_version(void) { return 7; }
+int medgp_abi_version(void) { return 8; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2157,6 +2164,145 @@ int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
         for (int i = 0; i < nbatch; i++) { const int b = c->plan.order[i]; jq->cov_status[b] = (st[i] < 0 || cst[b] < 0) ? -1 : 0; }
     return MEDGP_OK;
 }
+
+void launch_forecast(medgp_ctx *c, const MedgpDev &V, int ntiles, const ForeTile *tiles, size_t stride, bool with_lpd, double log2pi) {
+    const dim3 tg(ntiles), tb(256);
+#define MEDGP_FORE(QQ) hipLaunchKernelGGL(k_forecast<QQ>, tg, tb, 0, c->stream, V, tiles, c->d_post_m2, c->d_post_t2, c->d_fore_prefix, \
+                                          with_lpd ? c->d_fore_y2 : nullptr, c->d_post_work, stride, log2pi, c->d_post_mean, c->d_post_var, c->d_fore_lpd)
+    switch (V.Q) {
+    case 1: MEDGP_FORE(1); break;
+    case 2: MEDGP_FORE(2); break;
+    case 3: MEDGP_FORE(3); break;
+    case 4: MEDGP_FORE(4); break;
+    case 5: MEDGP_FORE(5); break;
+    case 6: MEDGP_FORE(6); break;
+    case 7: MEDGP_FORE(7); break;
+    case 8: MEDGP_FORE(8); break;
+    default: MEDGP_FORE(0); break;   // Q > 8: generic component loop
+    }
+#undef MEDGP_FORE
+}
+
+// medgp_forecast_batch (kernels_forecast.h): the posterior call's pipeline run on the CALLER-order copies, then k_forecast over tiles
+// of points sorted by prefix inside each patient (a tile's panel count follows its largest prefix).  The device sees the points in
+// the sorted order; the outputs are scattered back on the host.  A point's bits do not depend on its tile, so the sort is invisible.
+int forecast_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets, const int32_t *meta2,
+                  const float *t2, const int32_t *prefix, const float *y2, float *mean, float *var, double *lpd, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
+    if ((y2 == nullptr) != (lpd == nullptr)) return fail(c, MEDGP_ERR_ARG, "y2 and lpd must both be given or both be NULL");
+    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
+    if (nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
+    if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
+    for (int b = 0; b < nbatch; b++)
+        if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
+    const int64_t M = offsets[nbatch];
+    if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
+    if (M > 0 && (!t2 || !mean || !var)) return fail(c, MEDGP_ERR_ARG, "t2 / mean / var is NULL");
+    if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
+    for (int b = 0; b < nbatch; b++) {
+        const int s = slots[b];
+        if (s < 0 || s >= c->max_slots || c->h_n[s] < 0) return fail(c, MEDGP_ERR_ARG, "slots[%d] = %d is not a resident patient", b, s);
+    }
+    const int D = c->D;
+    // the device order of the points: inside each patient stably sorted by prefix (src[k] = the caller's index of device point k)
+    std::vector<int64_t> src(M);
+    std::vector<int> hpf(M);
+    for (int b = 0; b < nbatch; b++) {
+        const int n = c->h_n[slots[b]];
+        for (int64_t j = offsets[b]; j < offsets[b + 1]; j++) {
+            if (prefix && (prefix[j] < 0 || prefix[j] > n))
+                return fail(c, MEDGP_ERR_ARG, "prefix[%lld] = %d outside [0, %d] (patient %d)", (long long)j, prefix[j], n, b);
+            src[j] = j;
+        }
+        if (prefix)
+            std::stable_sort(src.begin() + offsets[b], src.begin() + offsets[b + 1], [&](int64_t a, int64_t z) { return prefix[a] < prefix[z]; });
+        for (int64_t k = offsets[b]; k < offsets[b + 1]; k++) hpf[k] = prefix ? prefix[src[k]] : n;
+    }
+    std::vector<double> ht2(M), hy2(y2 ? M : 0);
+    std::vector<int> hm2(M, 0);
+    for (int64_t k = 0; k < M; k++) {
+        const int64_t j = src[k];
+        ht2[k] = (double)t2[j];
+        if (y2) hy2[k] = (double)y2[j];
+        if (meta2 && c->kidx == MEDGP_KERNEL_LMC_SM) {
+            if (meta2[j] < 0 || meta2[j] >= D) return fail(c, MEDGP_ERR_ARG, "meta2[%lld] = %d outside [0, %d)", (long long)j, meta2[j], D);
+            hm2[k] = meta2[j];
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    int max_n = 0, rc;
+    // "the first p observations" is the caller's order: a patient not uploaded grouped by output is factored on its caller-order copy
+    if ((rc = set_batch(c, nbatch, slots, &max_n, true, true))) return rc;
+    const size_t Mz = (size_t)std::max<int64_t>(M, 1);
+    if ((rc = post_buf(c, (void **)&c->d_post_t2, &c->post_cap_pts, Mz * sizeof(double)))) return rc;
+    if ((rc = post_buf(c, (void **)&c->d_post_m2, &c->post_cap_m2, Mz * sizeof(int)))) return rc;
+    if ((rc = post_buf(c, (void **)&c->d_post_mean, &c->post_cap_mean, Mz * sizeof(float)))) return rc;
+    if ((rc = post_buf(c, (void **)&c->d_post_var, &c->post_cap_var, Mz * sizeof(float)))) return rc;
+    if ((rc = post_buf(c, (void **)&c->d_fore_prefix, &c->fore_cap_prefix, Mz * sizeof(int)))) return rc;
+    if (y2 && (rc = post_buf(c, (void **)&c->d_fore_y2, &c->fore_cap_y2, Mz * sizeof(double)))) return rc;
+    if (y2 && (rc = post_buf(c, (void **)&c->d_fore_lpd, &c->fore_cap_lpd, Mz * sizeof(double)))) return rc;
+    // tile table per size class and launch chunks within the budget, as the posterior call's
+    struct Chunk { const SizeClass *k; int t0, nt; size_t stride; };
+    std::vector<ForeTile> tiles;
+    std::vector<Chunk> chunks;
+    size_t work_need = 0;
+    for (const SizeClass &k : c->plan.cls) {
+        const int t_begin = (int)tiles.size();
+        const size_t stride = (size_t)k.ld * 64;   // doubles per tile
+        for (int i = k.b0; i < k.b0 + k.count; i++) {
+            const int b = c->plan.order[i];
+            for (int64_t p = offsets[b]; p < offsets[b + 1]; p += POST_TW) {
+                const int cnt = (int)std::min<int64_t>(POST_TW, offsets[b + 1] - p);
+                tiles.push_back({i - k.b0, (int)p, cnt, hpf[p + cnt - 1]});   // (sorted: the tile's last point has its largest prefix)
+            }
+        }
+        const int per_chunk = (int)std::max<size_t>(1, c->posterior_budget / (stride * sizeof(double)));
+        for (int t0 = t_begin; t0 < (int)tiles.size(); t0 += per_chunk) {
+            const int nt = std::min(per_chunk, (int)tiles.size() - t0);
+            chunks.push_back({&k, t0, nt, stride});
+            work_need = std::max(work_need, (size_t)nt * stride * sizeof(double));
+        }
+    }
+    static_assert(sizeof(ForeTile) == sizeof(PostTile), "the forecast tiles travel in the posterior call's tile buffer");
+    if (!tiles.empty()) {
+        if ((rc = post_buf(c, (void **)&c->d_post_tiles, &c->post_cap_tiles, tiles.size() * sizeof(ForeTile)))) return rc;
+        if ((rc = post_buf(c, (void **)&c->d_post_work, &c->post_cap_work, work_need))) return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
+    if (M > 0) {
+        HIPCHK(c, hipMemcpyAsync(c->d_post_t2, ht2.data(), sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_post_m2, hm2.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_fore_prefix, hpf.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
+        if (y2) HIPCHK(c, hipMemcpyAsync(c->d_fore_y2, hy2.data(), sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_post_tiles, tiles.data(), sizeof(ForeTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
+    }
+    // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
+    if ((rc = run_pipeline(c, nbatch, max_n, c->d_theta, 0, false, 1, nullptr, nullptr, nullptr, true, true))) return rc;
+    const double log2pi = std::log(2.0 * c->pi);
+    for (const Chunk &ch : chunks) {   // chunks reuse the work rows in stream order
+        Launcher l(c, KID_FORECAST);
+        launch_forecast(c, class_view(c, c->plan, *ch.k), ch.nt, (const ForeTile *)c->d_post_tiles + ch.t0, ch.stride, y2 != nullptr, log2pi);
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<float> hmean(M), hvar(M);
+    std::vector<double> hlpd(y2 ? M : 0);
+    if (M > 0) {
+        HIPCHK(c, hipMemcpyAsync(hmean.data(), c->d_post_mean, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(hvar.data(), c->d_post_var, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        if (y2) HIPCHK(c, hipMemcpyAsync(hlpd.data(), c->d_fore_lpd, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+    }
+    std::vector<int> st(nbatch, 0);
+    if (status) HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int64_t k = 0; k < M; k++) {   // sorted order -> the caller's
+        mean[src[k]] = hmean[k];
+        var[src[k]] = hvar[k];
+        if (y2) lpd[src[k]] = hlpd[k];
+    }
+    if (status) for (int i = 0; i < nbatch; i++) status[c->plan.order[i]] = st[i];   // internal order -> the caller's
+    return MEDGP_OK;
+}
 }  // namespace
 
 int medgp_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
@@ -2169,6 +2315,12 @@ int medgp_posterior_joint_batch(medgp_ctx *c, int nbatch, const int32_t *slots, 
                                 float *cov, float *samples, int32_t *status, int32_t *cov_status) {
     const JointReq jq{nsamp, eps, cov, samples, cov_status};
     return posterior_impl(c, nbatch, slots, theta, offsets, meta2, t2, mean, var, nullptr, status, &jq);
+}
+
+int medgp_forecast_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                         const int32_t *meta2, const float *t2, const int32_t *prefix, const float *y2,
+                         float *mean, float *var, double *lpd, int32_t *status) {
+    return forecast_impl(c, nbatch, slots, theta, offsets, meta2, t2, prefix, y2, mean, var, lpd, status);
 }
 
 // Leave-one-out / leave-group-out predictions of the training observations (kernels_loo.h).  ONE pipeline run in the grouped order
