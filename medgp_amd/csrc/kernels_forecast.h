@@ -10,13 +10,7 @@
 #include "medgp_dev.h"
 #include "kernels_cholinv.h"     // v4d
 #include "kernels_assemble.h"    // exp_neg
-#include "kernels_posterior.h"   // POST_TW, POST_KC, POST_LS
-
-// one workgroup of k_forecast: entry e of the class view, points [p0, p0 + cnt) of the call in the call's SORTED order
-// (cnt <= POST_TW), pmax = the largest prefix among them
-struct ForeTile {
-    int e, p0, cnt, pmax;
-};
+#include "kernels_posterior.h"   // POST_TW, POST_KC, POST_LS; ForeTile (inference_tables.h)
 
 // ------------------------------------------------------------------------------------------
 // k_posterior (kernels_posterior.h: same workgroup shape, MFMA operand layout, left-looking panel loop, K* forms) with

@@ -16,26 +16,7 @@
 #pragma once
 #include "kernels_posterior_joint.h"
 
-// one singleton group
-struct LooSingle {
-    int e;     // entry of the class view
-    int r;     // its row of the entry (internal order)
-    int out;   // its observation of the call (mean / var, the caller's order)
-    int g;     // its group of the call (lpd)
-};
-// one member of a larger group: the index list of a group is rows[p0 .. p0 + m), r ascending
-struct LooRow {
-    int r, out;
-};
-// A larger group is a JointPat: e = entry of the class view, b = its group of the call (lpd / group_status row), p0 = first of its
-// rows in the index list, m = its size, coff = offset (doubles) of its block in the chunk's buffer:
-//   [mpad x mpad] M -> R | [mpad x mpad] R^-1 (k_loo_solve's panels) | [mpad] w | [mpad] R^-T w,     mpad = m rounded up to 64.
-// A workgroup of k_loo_gram is a JointTile (pat, I, J), I >= J; of k_loo_solve (pat, I = column tile, J = 0) or (pat, 0, J = 1: the
-// vector solves).
-__host__ __device__ inline size_t loo_block_doubles(int m) {
-    const size_t mpad = (size_t)medgp_roundup(m, 64);
-    return 2 * mpad * mpad + 2 * mpad;
-}
+// LooSingle, LooRow, the JointPat / JointTile of a larger group and loo_block_doubles: inference_tables.h
 
 // ------------------------------------------------------------------------------------------
 // Singletons: row i of U is contiguous from its diagonal on; lane l takes the columns l, l + 64, ... of the row's 64-aligned

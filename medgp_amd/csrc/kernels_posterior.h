@@ -7,16 +7,11 @@
 #include "medgp_dev.h"
 #include "kernels_cholinv.h"   // v4d
 #include "kernels_assemble.h"  // exp_neg
+#include "inference_tables.h"  // POST_TW (test points per tile = one workgroup), PostTile
 
-#define POST_TW 64    // test points per tile (one workgroup)
 #define POST_KC 32    // rows of V staged in LDS per step of the off-diagonal product
 #define POST_LS 66    // LDS row stride (doubles) of the staged V rows and of the 64 x 64 block buffer
 #define POST_PARTS_LDS_MAX_D 32   // up to this D the per-covariate accumulators of a tile live in LDS, beyond it in the work rows
-
-// one workgroup of k_posterior: entry e of the class view, test points [p0, p0 + cnt) of the call (cnt <= POST_TW)
-struct PostTile {
-    int e, p0, cnt, pad;
-};
 
 // ------------------------------------------------------------------------------------------
 // alpha = K^-1 y = L^-T z by blocked back substitution over the 64-wide panels, last panel first:

@@ -18,20 +18,7 @@
 #define PJ_KC 32   // k-rows staged in LDS per step of the products
 #define PJ_BS 34   // LDS row stride (doubles) of the staged rows of L in k_postfactor
 
-// one patient of a joint call
-struct JointPat {
-    int e;             // entry of the class view
-    int b;             // caller index (cov_status row)
-    int p0, m;         // its test points [p0, p0 + m) of the call
-    int tile0;         // first of its tiles in the launch chunk (work rows)
-    int pad;
-    long long coff;    // offset (doubles) of its C (mpad x mpad, mpad = m rounded up to 64) in the chunk's C buffer
-    long long voff;    // offset (floats) of its m x m block in the chunk's cov buffer
-};
-// one workgroup of k_postcov: tile pair (I, J), I >= J, of patient pat; of k_postdraw: row block I (J unused)
-struct JointTile {
-    int pat, I, J, pad;
-};
+// JointPat (one patient of a joint call) and JointTile (one workgroup of k_postcov / k_postdraw): inference_tables.h
 
 // ------------------------------------------------------------------------------------------
 // C_IJ = K**_IJ - V_I^T V_J (+ sigma^2 on the diagonal; identity on rows / columns [m, mpad)).  acc = V_I^T V_J over the

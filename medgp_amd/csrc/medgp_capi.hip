@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -94,7 +95,17 @@ struct Arena {
     char *base = nullptr;
     size_t bytes = 0;    // size of the block
 };
-enum LooBuf { LOO_SINGLES = 0, LOO_ROWS, LOO_GROUPS, LOO_PAIRS, LOO_JOBS, LOO_BLOCKS, LOO_MEAN, LOO_VAR, LOO_LPD, LOO_GSTAT, LOO_GVEC, LOO_BUF_COUNT };
+// The device buffers of the inference entry points (medgp_fit_predict*, medgp_posterior*_batch, medgp_forecast_batch, medgp_loo_*): own
+// blocks, replaced when a call outgrows them (buf_ensure), freed by free_all.  The calls block and run in stream order, so buffers of
+// one role are shared between them:
+//   per-point inputs / outputs of the call, the tile table, the work rows of one launch chunk (at most posterior_budget bytes unless
+//   one tile needs more; medgp_fit_predict*: the k* rows); the forecast's prefix and y2; lpd (forecast: per point, LOO: per group);
+//   joint posterior: the patient / tile-pair / row-block tables of the call, C and the float covariance blocks of one launch chunk, the
+//   call's eps and samples, cov_status -- LOO: its group / tile-pair / job tables, the blocks of one launch chunk, group_status;
+//   LOO: the singleton table and the index lists; BUF_GVEC: the per-entry vectors [u | s | v | log p] of medgp_loo_grad
+struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
+enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -175,35 +186,8 @@ struct medgp_ctx {
     char *h_bounce = nullptr;        // pinned bounce buffer for the large device-to-host exports (factor matrices)
     size_t bounce_cap = 0;
     int *d_one_slot = nullptr;       // single-entry slot table for the caller-order re-factorisation of medgp_get_factor
-    // predict scratch
-    double *d_t2 = nullptr, *d_ks = nullptr;
-    int *d_meta2 = nullptr;
-    float *d_mean = nullptr, *d_var = nullptr;
-    int pred_cap = 0;
-    // medgp_posterior_batch buffers (own blocks, replaced when a call outgrows them; freed by free_all): per-point inputs / outputs of
-    // the call, the tile table, and the work rows of one launch chunk (at most posterior_budget bytes unless one tile needs more)
-    double *d_post_t2 = nullptr, *d_post_work = nullptr;
-    int *d_post_m2 = nullptr;
-    float *d_post_mean = nullptr, *d_post_var = nullptr, *d_post_parts = nullptr;
-    PostTile *d_post_tiles = nullptr;
-    size_t post_cap_pts = 0, post_cap_m2 = 0, post_cap_mean = 0, post_cap_var = 0, post_cap_parts = 0, post_cap_tiles = 0, post_cap_work = 0;   // bytes
+    DevBuf buf[BUF_COUNT];          // the inference entry points' buffers (enum BufId)
     size_t posterior_budget = (size_t)2 << 30;   // MEDGP_POSTERIOR_BUDGET_GB
-    // medgp_forecast_batch buffers (same rules; the rest of the call lives in the posterior buffers above): prefix, y2, lpd of the call
-    int *d_fore_prefix = nullptr;
-    double *d_fore_y2 = nullptr, *d_fore_lpd = nullptr;
-    size_t fore_cap_prefix = 0, fore_cap_y2 = 0, fore_cap_lpd = 0;   // bytes
-    // medgp_posterior_joint_batch buffers (same rules): the patient / tile-pair / row-block tables of the call, C and the float
-    // covariance blocks of one launch chunk, the call's eps and samples, cov_status
-    JointPat *d_joint_pats = nullptr;
-    JointTile *d_joint_pairs = nullptr, *d_joint_blks = nullptr;
-    double *d_joint_C = nullptr, *d_joint_eps = nullptr;
-    float *d_joint_cov = nullptr, *d_joint_samp = nullptr;
-    int *d_joint_cstat = nullptr;
-    size_t joint_cap_pats = 0, joint_cap_pairs = 0, joint_cap_blks = 0, joint_cap_C = 0, joint_cap_eps = 0, joint_cap_cov = 0, joint_cap_samp = 0, joint_cap_cstat = 0;   // bytes
-    // medgp_loo_batch buffers (same rules): the singleton / index-list / group / tile tables of the call, the blocks of one launch
-    // chunk, the call's outputs; LOO_GVEC: the per-entry vectors [u | s | v | log p] of medgp_loo_grad
-    void *d_loo[LOO_BUF_COUNT] = {};
-    size_t loo_cap[LOO_BUF_COUNT] = {};   // bytes
     // profiling
     bool profiling = false;
     int profile_only = -1;    // >= 0: only launches of this kernel id are bracketed (medgp_profile_enable(ctx, 2 + id))
@@ -273,21 +257,61 @@ void free_all(medgp_ctx *c) {
     for (void *p : c->retired) (void)hipFree(p);
     c->retired.clear();
     c->retired_bytes = 0;
-    for (void **p : {(void **)&c->d_post_t2, (void **)&c->d_post_work, (void **)&c->d_post_m2, (void **)&c->d_post_mean, (void **)&c->d_post_var,
-                     (void **)&c->d_post_parts, (void **)&c->d_post_tiles, (void **)&c->d_joint_pats, (void **)&c->d_joint_pairs, (void **)&c->d_joint_blks,
-                     (void **)&c->d_joint_C, (void **)&c->d_joint_eps, (void **)&c->d_joint_cov, (void **)&c->d_joint_samp, (void **)&c->d_joint_cstat,
-                     (void **)&c->d_fore_prefix, (void **)&c->d_fore_y2, (void **)&c->d_fore_lpd}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
+    for (DevBuf &b : c->buf) {
+        if (b.p) (void)hipFree(b.p);
+        b = DevBuf{};
     }
-    for (int i = 0; i < LOO_BUF_COUNT; i++) {
-        if (c->d_loo[i]) (void)hipFree(c->d_loo[i]);
-        c->d_loo[i] = nullptr;
-        c->loo_cap[i] = 0;
+}
+
+template <typename T>
+T *buf(medgp_ctx *c, int id) { return (T *)c->buf[id].p; }
+
+// at least `bytes` in buffer `id`: the block is kept when large enough, otherwise replaced after the queued work that may still read it
+int buf_ensure(medgp_ctx *c, int id, size_t bytes) {
+    DevBuf &b = c->buf[id];
+    if (bytes <= b.cap && b.p) return MEDGP_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (b.p) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(b.p);
+        b = DevBuf{};
     }
-    c->post_cap_pts = c->post_cap_m2 = c->post_cap_mean = c->post_cap_var = c->post_cap_parts = c->post_cap_tiles = c->post_cap_work = 0;
-    c->joint_cap_pats = c->joint_cap_pairs = c->joint_cap_blks = c->joint_cap_C = c->joint_cap_eps = c->joint_cap_cov = c->joint_cap_samp = c->joint_cap_cstat = 0;
-    c->fore_cap_prefix = c->fore_cap_y2 = c->fore_cap_lpd = 0;
+    const size_t want = std::max<size_t>(bytes, 256);
+    hipError_t e = hipMalloc(&b.p, want);
+    c->alloc_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    c->alloc_calls++;
+    if (e != hipSuccess) { b.p = nullptr; return fail(c, MEDGP_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e)); }
+    b.cap = want;
+    return MEDGP_OK;
+}
+
+// Dispatch on the component count Q: f is a generic lambda called with std::integral_constants, so that every launch site names its
+// kernel template once.  with_q8: <Q> for 1 .. 8, else <0> (the kernel's generic component loop).
+template <int N> using QConst = std::integral_constant<int, N>;
+template <class F>
+void with_q8(int Q, F &&f) {
+    switch (Q) {
+    case 1: f(QConst<1>{}); break;
+    case 2: f(QConst<2>{}); break;
+    case 3: f(QConst<3>{}); break;
+    case 4: f(QConst<4>{}); break;
+    case 5: f(QConst<5>{}); break;
+    case 6: f(QConst<6>{}); break;
+    case 7: f(QConst<7>{}); break;
+    case 8: f(QConst<8>{}); break;
+    default: f(QConst<0>{}); break;
+    }
+}
+// with_q16: f(<Q>, <0>) for 1 .. 8; for 9 .. 16 f(<8>, <0>), then f(<Q - 8>, <8>) for the rest of the components; false (nothing called)
+// for any other Q: the caller takes its generic route
+template <class F>
+bool with_q16(int Q, F &&f) {
+    if (Q < 1 || Q > 16) return false;
+    if (Q > 8) f(QConst<8>{}, QConst<0>{});
+    with_q8(Q > 8 ? Q - 8 : Q, [&](auto q) {
+        if constexpr (decltype(q)::value > 0) { if (Q > 8) f(q, QConst<8>{}); else f(q, QConst<0>{}); }
+    });
+    return true;
 }
 
 int num_cov(int kidx, int Q, int D, int R) {
@@ -376,6 +400,19 @@ inline int size_bucket(int nb) { int j = 0; while ((1 << j) < nb) j++; return j;
 // Cost model of one entry on ONE workgroup (k_cholinv), fitted to profiles/r04_route_table.txt (ms = 4.4e-4 nb^2 (nb + 17):
 // N = 256 0.15, 512 0.70, 768 1.83, 1024 3.7; N = 8192: 1.05 s against 1.33 s measured).  Integer, so the route rule is exact.
 inline long long wg_cost(int nb) { return (long long)nb * nb * (nb + 17); }
+
+// The grid of k_wgrad (and of k_loo_kinv / k_loo_wgrad, which walk the same tiles) for a class of nbatch entries of sizes entry_n, nt64
+// 64-blocks the largest.  ragged: entries of different 64-block counts in the class.  Entries of different sizes in a launch of few
+// entries: odd stride nbp of the entry index, so that every entry's tiles go to all XCDs (kernels_wgrad.h); equally large entries keep
+// the stride nbatch (balanced as it is, and the measured form).
+struct WgradGrid { bool ragged; int nbp, wg_tiles; dim3 grid; };
+inline WgradGrid wgrad_grid(const int *entry_n, int nbatch, int nt64) {
+    WgradGrid g{false, nbatch, tri(nt64), dim3()};
+    for (int bb = 1; bb < nbatch; bb++) g.ragged = g.ragged || blocks64(entry_n[bb]) != blocks64(entry_n[0]);
+    if (g.ragged && nbatch < 64) g.nbp = nbatch | 1;
+    g.grid = dim3(std::max(8 * ((nbatch + 7) / 8), g.nbp) * g.wg_tiles);
+    return g;
+}
 
 // Lay out the plan of a call from the sizes of its entries alone (en[b] = n of caller entry b): internal order, size classes, memory
 // waves, offsets, needs.  with_u: the call forms U = L^-T (gradient / factor outputs / predict); an nlml-only call touches neither
@@ -652,27 +689,15 @@ int ensure_la(medgp_ctx *c, std::vector<LaNeed> &v, bool with_u, size_t part0 = 
 int run_pipeline_one(medgp_ctx *c, hipStream_t stream, const MedgpDev &L, int nbatch, int nt64, const double *theta_dev,
                      int flag_grad, bool need_inverse, int min_n, double *nlml_dev, double *grad_dev, int32_t *status_dev,
                      bool store_ukk, const int *entry_n, int route, const LaArgs *la_in) {
-    bool ragged = false;   // entries of different 64-block counts in this class
-    for (int bb = 1; bb < nbatch; bb++) ragged = ragged || blocks64(entry_n[bb]) != blocks64(entry_n[0]);
+    const WgradGrid wg = wgrad_grid(entry_n, nbatch, nt64);
+    const bool ragged = wg.ragged;
     { Launcher l(c, KID_PREP, stream); hipLaunchKernelGGL(k_prep, dim3(nbatch, 1 + (L.Q * L.ldn + PREP_CHUNK - 1) / PREP_CHUNK + ((theta_dev && L.kidx == 7) ? (L.Q * L.D * L.D + PREP_BCHUNK - 1) / PREP_BCHUNK : 0)), dim3(256), 0, stream, L, theta_dev, min_n); }
     auto launch_assemble = [&]() {
         Launcher l(c, KID_ASSEMBLE, stream);
         const dim3 tg(tri(nt64), nbatch), tb(256);
-        switch (c->use_v0 ? 0 : L.Q) {
-        case 1: hipLaunchKernelGGL(k_assemble_t<1>, tg, tb, 0, stream, L); break;
-        case 2: hipLaunchKernelGGL(k_assemble_t<2>, tg, tb, 0, stream, L); break;
-        case 3: hipLaunchKernelGGL(k_assemble_t<3>, tg, tb, 0, stream, L); break;
-        case 4: hipLaunchKernelGGL(k_assemble_t<4>, tg, tb, 0, stream, L); break;
-        case 5: hipLaunchKernelGGL(k_assemble_t<5>, tg, tb, 0, stream, L); break;
-        case 6: hipLaunchKernelGGL(k_assemble_t<6>, tg, tb, 0, stream, L); break;
-        case 7: hipLaunchKernelGGL(k_assemble_t<7>, tg, tb, 0, stream, L); break;
-        case 8: hipLaunchKernelGGL(k_assemble_t<8>, tg, tb, 0, stream, L); break;
         // 9 .. 16 components: the first eight, then the rest added to the same tiles (kernels_assemble.h)
-#define MEDGP_ASM2(QR) case 8 + QR: hipLaunchKernelGGL(k_assemble_t<8>, tg, tb, 0, stream, L); hipLaunchKernelGGL((k_assemble_t<QR, 8>), tg, tb, 0, stream, L); break;
-        MEDGP_ASM2(1) MEDGP_ASM2(2) MEDGP_ASM2(3) MEDGP_ASM2(4) MEDGP_ASM2(5) MEDGP_ASM2(6) MEDGP_ASM2(7) MEDGP_ASM2(8)
-#undef MEDGP_ASM2
-        default: hipLaunchKernelGGL(k_assemble_v0, tg, tb, 0, stream, L); break;   // Q > 16 (or MEDGP_V0): generic kernel
-        }
+        if (c->use_v0 || !with_q16(L.Q, [&](auto q, auto q0) { hipLaunchKernelGGL((k_assemble_t<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, stream, L); }))
+            hipLaunchKernelGGL(k_assemble_v0, tg, tb, 0, stream, L);   // Q > 16 (or MEDGP_V0): generic kernel
     };
     const bool inv = flag_grad || need_inverse;
     const int want_mode = inv ? 1 : (store_ukk ? 2 : 0);   // bit 0: U rows + alpha; 2: diagonal blocks U_kk only (k_predict)
@@ -741,28 +766,18 @@ int run_pipeline_one(medgp_ctx *c, hipStream_t stream, const MedgpDev &L, int nb
     if (getenv("MEDGP_DBG_NOWGRAD")) { HIPCHK(c, hipGetLastError()); return MEDGP_OK; }
 #endif
     if (flag_grad) {
-        const int wg_tiles = tri(nt64);
-        // entries of different sizes in a launch of few entries: odd stride of the entry index, so that every entry's tiles go to all
-        // XCDs (kernels_wgrad.h); equally large entries keep the stride nbatch (balanced as it is, and the measured form)
-        const int nbp = (ragged && nbatch < 64) ? (nbatch | 1) : nbatch;
-        const dim3 tg(std::max(8 * ((nbatch + 7) / 8), nbp) * wg_tiles), tb(WG_THREADS);
-        from_slab = 1;
+        const int wg_tiles = wg.wg_tiles, nbp = wg.nbp;
+        const dim3 tg = wg.grid, tb(WG_THREADS);
         Launcher lw(c, KID_WGRAD, stream);
         // few large patients (the launch fills the chip less than four times): operand prefetch two chunks ahead + serpentine tile order (kernels_wgrad.h)
         const int pf = c->wgrad_deep >= 0 ? c->wgrad_deep : ((long)nbatch * wg_tiles <= 16L * c->num_cu ? 2 : 1);
-#define MEDGP_WGL(QQ, Q0) do { if (pf >= 2) hipLaunchKernelGGL((k_wgrad<QQ, Q0, 2>), tg, tb, 0, stream, L, nbatch, wg_tiles, nbp); \
-                               else hipLaunchKernelGGL((k_wgrad<QQ, Q0, 1>), tg, tb, 0, stream, L, nbatch, wg_tiles, nbp); } while (0)
-#define MEDGP_WG1(QQ) case QQ: MEDGP_WGL(QQ, 0); break;
-        // 9 .. 16 components: two launches, each reducing its own components into its own slab planes (kernels_wgrad.h)
-#define MEDGP_WG2(QR) case 8 + QR: MEDGP_WGL(8, 0); MEDGP_WGL(QR, 8); break;
-        switch (c->use_v0 ? 0 : L.Q) {
-        MEDGP_WG1(1) MEDGP_WG1(2) MEDGP_WG1(3) MEDGP_WG1(4) MEDGP_WG1(5) MEDGP_WG1(6) MEDGP_WG1(7) MEDGP_WG1(8)
-        MEDGP_WG2(1) MEDGP_WG2(2) MEDGP_WG2(3) MEDGP_WG2(4) MEDGP_WG2(5) MEDGP_WG2(6) MEDGP_WG2(7) MEDGP_WG2(8)
-#undef MEDGP_WG1
-#undef MEDGP_WG2
-#undef MEDGP_WGL
-        default: from_slab = 0; break;   // Q > 16 (or MEDGP_V0): generic kernels below
-        }
+        // 9 .. 16 components: two launches, each reducing its own components into its own slab planes (kernels_wgrad.h);
+        // Q > 16 (or MEDGP_V0): generic kernels below
+        from_slab = !c->use_v0 && with_q16(L.Q, [&](auto q, auto q0) {
+            constexpr int QQ = decltype(q)::value, Q0 = decltype(q0)::value;
+            if (pf >= 2) hipLaunchKernelGGL((k_wgrad<QQ, Q0, 2>), tg, tb, 0, stream, L, nbatch, wg_tiles, nbp);
+            else hipLaunchKernelGGL((k_wgrad<QQ, Q0, 1>), tg, tb, 0, stream, L, nbatch, wg_tiles, nbp);
+        });
         if (!from_slab) lw.kid = -1;   // nothing was launched under this label: its events go back to the pool unread
         lw.finish();
         if (!from_slab) {
@@ -958,6 +973,95 @@ int run_pipeline(medgp_ctx *c, int nbatch, int max_n, const double *theta_dev, i
                     HIPCHK(c, hipStreamWaitEvent(st_main, c->ev_join[ai], 0));
                 }
     }
+    return MEDGP_OK;
+}
+
+// ---- what the inference entry points share (fit_predict, factor, posterior, joint posterior, forecast, LOO, LOO gradient) ------
+// the context is reserved, the batch fits it and every slot holds a patient
+int check_call(medgp_ctx *c, int nbatch, const int32_t *slots) {
+    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
+    if (nbatch < 1 || nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
+    for (int b = 0; b < nbatch; b++)
+        if (slots[b] < 0 || slots[b] >= c->max_slots || c->h_n[slots[b]] < 0) return fail(c, MEDGP_ERR_ARG, "slots[%d] = %d is not a resident patient", b, slots[b]);
+    return MEDGP_OK;
+}
+
+// the test points of a call: patient b owns points [offsets[b], offsets[b + 1]) of meta2 / t2 / mean / var
+int check_points(medgp_ctx *c, int nbatch, const int64_t *offsets, const int32_t *meta2, const float *t2, const float *mean, const float *var) {
+    if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
+    for (int b = 0; b < nbatch; b++)
+        if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
+    const int64_t M = offsets[nbatch];
+    if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
+    if (M > 0 && (!t2 || !mean || !var)) return fail(c, MEDGP_ERR_ARG, "t2 / mean / var is NULL");
+    if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
+    return MEDGP_OK;
+}
+
+// the M test points as the device takes them (double times, int outputs): device point k is the caller's point src[k] (null: k)
+int stage_points(medgp_ctx *c, int64_t M, const int32_t *meta2, const float *t2, const int64_t *src, std::vector<double> &ht2, std::vector<int> &hm2) {
+    ht2.resize(M);
+    hm2.assign(M, 0);
+    for (int64_t k = 0; k < M; k++) {
+        const int64_t j = src ? src[k] : k;
+        ht2[k] = (double)t2[j];
+        if (meta2 && c->kidx == MEDGP_KERNEL_LMC_SM) {
+            if (meta2[j] < 0 || meta2[j] >= c->D) return fail(c, MEDGP_ERR_ARG, "meta2[%lld] = %d outside [0, %d)", (long long)j, meta2[j], c->D);
+            hm2[k] = meta2[j];
+        }
+    }
+    return MEDGP_OK;
+}
+
+// theta to the device and the ONE pipeline run of an inference call: factor and z = L^-1 y of every entry, with U = L^-T and
+// alpha = K^-1 y (need_inverse: medgp_get_factor is valid afterwards) or the diagonal-block inverses U_kk (store_ukk).  The call reads
+// per-entry buffers of all entries afterwards: it must fit one memory wave.
+int factor_run(medgp_ctx *c, int nbatch, int max_n, const double *theta, bool need_inverse, bool store_ukk) {
+    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
+    return run_pipeline(c, nbatch, max_n, c->d_theta, 0, need_inverse, 1, nullptr, nullptr, nullptr, store_ukk, true);
+}
+
+// The end of a blocking call: the status words of its entries are read back behind whatever the caller has queued, the stream is
+// waited for, and they are scattered from the plan's internal order to the caller's (status; null: not wanted).  internal: the words
+// in internal order, for callers that go on with them.
+int read_status(medgp_ctx *c, int nbatch, int32_t *status, std::vector<int> *internal = nullptr) {
+    std::vector<int> tmp;
+    std::vector<int> &st = internal ? *internal : tmp;
+    st.assign(nbatch, 0);
+    if (status || internal) HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (status) for (int i = 0; i < nbatch; i++) status[c->plan.order[i]] = st[i];
+    return MEDGP_OK;
+}
+
+// the size classes of the last plan as the table builders take them (inference_tables.h)
+std::vector<TableClass> table_classes(const BatchPlan &P) {
+    std::vector<TableClass> v;
+    for (const SizeClass &k : P.cls) v.push_back({k.b0, k.count, k.ld});
+    return v;
+}
+// the per-point buffers of a posterior / forecast call of M points, and the staged points on their way into them
+int upload_points(medgp_ctx *c, int64_t M, const std::vector<double> &ht2, const std::vector<int> &hm2) {
+    const size_t Mz = (size_t)std::max<int64_t>(M, 1);
+    int rc;
+    if ((rc = buf_ensure(c, BUF_T2, Mz * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_META2, Mz * sizeof(int)))) return rc;
+    if ((rc = buf_ensure(c, BUF_MEAN, Mz * sizeof(float)))) return rc;
+    if ((rc = buf_ensure(c, BUF_VAR, Mz * sizeof(float)))) return rc;
+    if (M > 0) {
+        HIPCHK(c, hipMemcpyAsync(buf<double>(c, BUF_T2), ht2.data(), sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(buf<int>(c, BUF_META2), hm2.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
+    }
+    return MEDGP_OK;
+}
+
+// host table -> buffer `id` (grown as needed); an empty table uploads nothing
+template <class T>
+int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
+    if (v.empty()) return MEDGP_OK;
+    int rc = buf_ensure(c, id, v.size() * sizeof(T));
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->buf[id].p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
     return MEDGP_OK;
 }
 
@@ -1174,7 +1278,6 @@ int medgp_reserve(medgp_ctx *c, int max_slots, int max_n, int max_batch) {
     c->last_nbatch = 0;
     c->plan = BatchPlan{};
     c->last_has_inverse = false;
-    c->pred_cap = 0;
     c->d_stage = nullptr;   // freed by free_all above
     if (c->h_stage) { (void)hipHostFree(c->h_stage); c->h_stage = nullptr; }
     c->stage_cap = 0;
@@ -1768,49 +1871,35 @@ static int fit_predict_impl(medgp_ctx *c, int nbatch, const int32_t *slots, cons
                             const int32_t *meta2, const float *t2, float *mean, float *var, int32_t *status) {
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !t2 || !mean || !var || nstar < 1 || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
-    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
+    int max_n = 0, rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
     if (c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
     HIPCHK(c, hipSetDevice(c->device));
     const int ntot = nbatch * nstar;
-    if (ntot > c->pred_cap) {
-        int cap = std::max(ntot, 64), rc;
-        if ((rc = dalloc(c, &c->d_t2, cap))) return rc;
-        if ((rc = dalloc(c, &c->d_meta2, cap))) return rc;
-        if ((rc = dalloc(c, &c->d_mean, cap))) return rc;
-        if ((rc = dalloc(c, &c->d_var, cap))) return rc;
-        if ((rc = dalloc(c, &c->d_ks, (size_t)cap * c->ldn))) return rc;   // k* -> v = L^-1 k* work rows
-        c->pred_cap = cap;
-    }
-    int max_n = 0, rc;
+    std::vector<double> ht2;
+    std::vector<int> hm2;
+    if ((rc = stage_points(c, ntot, meta2, t2, nullptr, ht2, hm2))) return rc;
+    if ((rc = buf_ensure(c, BUF_T2, ntot * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_META2, ntot * sizeof(int)))) return rc;
+    if ((rc = buf_ensure(c, BUF_MEAN, ntot * sizeof(float)))) return rc;
+    if ((rc = buf_ensure(c, BUF_VAR, ntot * sizeof(float)))) return rc;
+    if ((rc = buf_ensure(c, BUF_WORK, (size_t)ntot * c->ldn * sizeof(double)))) return rc;   // k* -> v = L^-1 k* work rows
     // patients are used in the caller's order when that differs from the grouped one?  No: mean / var are permutation
     // invariant, the grouped copy serves.
     if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;   // (the diagonal blocks U_kk live in Linv)
-    std::vector<double> ht2(ntot);
-    std::vector<int> hm2(ntot, 0);
-    for (int j = 0; j < ntot; j++) {
-        ht2[j] = (double)t2[j];
-        if (meta2 && c->kidx == MEDGP_KERNEL_LMC_SM) {
-            if (meta2[j] < 0 || meta2[j] >= c->D) return fail(c, MEDGP_ERR_ARG, "meta2[%d] = %d outside [0, %d)", j, meta2[j], c->D);
-            hm2[j] = meta2[j];
-        }
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_t2, ht2.data(), sizeof(double) * ntot, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_meta2, hm2.data(), sizeof(int) * ntot, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(buf<double>(c, BUF_T2), ht2.data(), sizeof(double) * ntot, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(buf<int>(c, BUF_META2), hm2.data(), sizeof(int) * ntot, hipMemcpyHostToDevice, c->stream));
     // factor + z = L^-1 y only (no inverse): k* rides along as one more right-hand side in k_predict
-    if ((rc = run_pipeline(c, nbatch, max_n, c->d_theta, 0, false, 1, nullptr, nullptr, nullptr, true, true))) return rc;
+    if ((rc = factor_run(c, nbatch, max_n, theta, false, true))) return rc;
     for (const SizeClass &k : c->plan.cls) {   // (behind the join of the classes' chains: one launch per class view)
         Launcher l(c, KID_PREDICT);
-        hipLaunchKernelGGL(k_predict, dim3(nstar, k.count), dim3(256), 0, c->stream, class_view(c, c->plan, k), nstar, c->d_meta2, c->d_t2, c->d_ks, c->d_mean, c->d_var);
+        hipLaunchKernelGGL(k_predict, dim3(nstar, k.count), dim3(256), 0, c->stream, class_view(c, c->plan, k), nstar, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2),
+                           buf<double>(c, BUF_WORK), buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR));
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(mean, c->d_mean, sizeof(float) * ntot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(var, c->d_var, sizeof(float) * ntot, hipMemcpyDeviceToHost, c->stream));
-    std::vector<int> st(nbatch, 0);
-    if (status) HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (status) for (int i = 0; i < nbatch; i++) status[c->plan.order[i]] = st[i];   // internal order -> the caller's
-    return MEDGP_OK;
+    HIPCHK(c, hipMemcpyAsync(mean, buf<float>(c, BUF_MEAN), sizeof(float) * ntot, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(var, buf<float>(c, BUF_VAR), sizeof(float) * ntot, hipMemcpyDeviceToHost, c->stream));
+    return read_status(c, nbatch, status);
 }
 
 int medgp_factor_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, double *const *Lout, double *const *zout,
@@ -1821,15 +1910,9 @@ int medgp_factor_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const dou
     HIPCHK(c, hipSetDevice(c->device));
     int max_n = 0, rc;
     if ((rc = set_batch(c, nbatch, slots, &max_n, true, false))) return rc;       // the CALLER's observation order; size classes; L and z only: no Linv
-    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
-    if ((rc = run_pipeline(c, nbatch, max_n, c->d_theta, 0, false, 1, nullptr, nullptr, nullptr, false, true))) return rc;
-    std::vector<int> st(nbatch, 0);
-    {
-        std::vector<int> sti(nbatch, 0);
-        HIPCHK(c, hipMemcpyAsync(sti.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int i = 0; i < nbatch; i++) st[c->plan.order[i]] = sti[i];   // internal order -> the caller's
-    }
+    if ((rc = factor_run(c, nbatch, max_n, theta, false, false))) return rc;
+    std::vector<int32_t> st(nbatch, 0);
+    if ((rc = read_status(c, nbatch, st.data()))) return rc;
     if (status) for (int b = 0; b < nbatch; b++) status[b] = st[b];
     // every entry's rows of the batch buffers (its size class's view) and leading dimension
     std::vector<MedgpDev> ev(nbatch);
@@ -1910,65 +1993,31 @@ int medgp_fit_predict(medgp_ctx *c, int slot, const double *theta, int nstar, co
 
 int medgp_fit_predict_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int32_t *meta2,
                             const float *t2, float *mean, float *var, int32_t *status) {
-    if (c && nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
     return fit_predict_impl(c, nbatch, slots, theta, 1, meta2, t2, mean, var, status);
 }
 
 namespace {
-// a device block of at least `bytes` in *p (capacity *cap): replaced when too small, after the queued work that may still read it
-int post_buf(medgp_ctx *c, void **p, size_t *cap, size_t bytes) {
-    if (bytes <= *cap && *p) return MEDGP_OK;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (*p) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-    }
-    const size_t want = std::max<size_t>(bytes, 256);
-    hipError_t e = hipMalloc(p, want);
-    c->alloc_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    c->alloc_calls++;
-    if (e != hipSuccess) { *p = nullptr; return fail(c, MEDGP_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e)); }
-    *cap = want;
-    return MEDGP_OK;
-}
-
 void launch_posterior(medgp_ctx *c, const MedgpDev &V, int ntiles, const PostTile *tiles, size_t stride, int with_parts, int parts_lds) {
-    const dim3 tg(ntiles), tb(256);
     const size_t lds = parts_lds ? sizeof(double) * 64 * V.D : 0;
-#define MEDGP_POST(QQ) hipLaunchKernelGGL(k_posterior<QQ>, tg, tb, lds, c->stream, V, tiles, c->d_post_m2, c->d_post_t2, c->d_post_work, stride, \
-                                          with_parts, parts_lds, c->d_post_mean, c->d_post_var, c->d_post_parts)
-    switch (V.Q) {
-    case 1: MEDGP_POST(1); break;
-    case 2: MEDGP_POST(2); break;
-    case 3: MEDGP_POST(3); break;
-    case 4: MEDGP_POST(4); break;
-    case 5: MEDGP_POST(5); break;
-    case 6: MEDGP_POST(6); break;
-    case 7: MEDGP_POST(7); break;
-    case 8: MEDGP_POST(8); break;
-    default: MEDGP_POST(0); break;   // Q > 8: generic component loop
-    }
-#undef MEDGP_POST
+    with_q8(V.Q, [&](auto q) {   // Q > 8: generic component loop
+        hipLaunchKernelGGL(k_posterior<decltype(q)::value>, dim3(ntiles), dim3(256), lds, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2),
+                           buf<double>(c, BUF_WORK), stride, with_parts, parts_lds, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), buf<float>(c, BUF_PARTS));
+    });
 }
 
 void launch_postcov(medgp_ctx *c, const MedgpDev &V, int npairs, const JointTile *pairs, size_t stride, float *cov) {
-    const dim3 tg(npairs), tb(256);
-#define MEDGP_PCOV(QQ) hipLaunchKernelGGL(k_postcov<QQ>, tg, tb, 0, c->stream, V, c->d_joint_pats, pairs, c->d_post_m2, c->d_post_t2, c->d_post_work, stride, \
-                                          c->d_joint_C, cov)
-    switch (V.Q) {
-    case 1: MEDGP_PCOV(1); break;
-    case 2: MEDGP_PCOV(2); break;
-    case 3: MEDGP_PCOV(3); break;
-    case 4: MEDGP_PCOV(4); break;
-    case 5: MEDGP_PCOV(5); break;
-    case 6: MEDGP_PCOV(6); break;
-    case 7: MEDGP_PCOV(7); break;
-    case 8: MEDGP_PCOV(8); break;
-    default: MEDGP_PCOV(0); break;   // Q > 8: generic component loop
-    }
-#undef MEDGP_PCOV
+    with_q8(V.Q, [&](auto q) {   // Q > 8: generic component loop
+        hipLaunchKernelGGL(k_postcov<decltype(q)::value>, dim3(npairs), dim3(256), 0, c->stream, V, buf<JointPat>(c, BUF_PATS), pairs, buf<int>(c, BUF_META2),
+                           buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK), stride, buf<double>(c, BUF_C), cov);
+    });
+}
+
+void launch_forecast(medgp_ctx *c, const MedgpDev &V, int ntiles, const ForeTile *tiles, size_t stride, bool with_lpd, double log2pi) {
+    with_q8(V.Q, [&](auto q) {   // Q > 8: generic component loop
+        hipLaunchKernelGGL(k_forecast<decltype(q)::value>, dim3(ntiles), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2),
+                           buf<int>(c, BUF_PREFIX), with_lpd ? buf<double>(c, BUF_Y2) : nullptr, buf<double>(c, BUF_WORK), stride, log2pi,
+                           buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), buf<double>(c, BUF_LPD));
+    });
 }
 
 // the joint outputs of medgp_posterior_joint_batch (null: medgp_posterior_batch)
@@ -1986,11 +2035,9 @@ int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
                    const int32_t *meta2, const float *t2, float *mean, float *var, float *parts, int32_t *status, const JointReq *jq) {
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
-    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
-    if (nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
-    if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
-    for (int b = 0; b < nbatch; b++)
-        if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
+    int max_n = 0, rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    if ((rc = check_points(c, nbatch, offsets, meta2, t2, mean, var))) return rc;
     const int64_t M = offsets[nbatch];
     const bool want_cov = jq && jq->cov, want_samp = jq && jq->nsamp > 0;
     if (jq) {
@@ -1999,188 +2046,95 @@ int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
         if (want_samp && M > 0 && (!jq->eps || !jq->samples)) return fail(c, MEDGP_ERR_ARG, "eps / samples is NULL with nsamp = %d", jq->nsamp);
         if (want_samp && M * (int64_t)jq->nsamp > (int64_t)INT32_MAX) return fail(c, MEDGP_ERR_ARG, "%lld x %d sample values in one call", (long long)M, jq->nsamp);
     }
-    if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
-    if (M > 0 && (!t2 || !mean || !var)) return fail(c, MEDGP_ERR_ARG, "t2 / mean / var is NULL");
-    if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
     const int D = c->D;
     std::vector<size_t> cov_off(want_cov ? nbatch : 0);   // start of patient b's block in cov (floats)
     if (want_cov) { size_t o = 0; for (int b = 0; b < nbatch; b++) { cov_off[b] = o; const size_t m = (size_t)(offsets[b + 1] - offsets[b]); o += m * m; } }
-    std::vector<double> ht2(M);
-    std::vector<int> hm2(M, 0);
-    for (int64_t j = 0; j < M; j++) {
-        ht2[j] = (double)t2[j];
-        if (meta2 && c->kidx == MEDGP_KERNEL_LMC_SM) {
-            if (meta2[j] < 0 || meta2[j] >= D) return fail(c, MEDGP_ERR_ARG, "meta2[%lld] = %d outside [0, %d)", (long long)j, meta2[j], D);
-            hm2[j] = meta2[j];
-        }
-    }
+    std::vector<double> ht2;
+    std::vector<int> hm2;
+    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    int max_n = 0, rc;
     // the parts, like mean and var, are invariant under a permutation of the training observations: the grouped copy serves
     if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
     const bool with_parts = parts != nullptr;
     const int parts_lds = D <= POST_PARTS_LDS_MAX_D;
-    const size_t Mz = (size_t)std::max<int64_t>(M, 1);
-    if ((rc = post_buf(c, (void **)&c->d_post_t2, &c->post_cap_pts, Mz * sizeof(double)))) return rc;
-    if ((rc = post_buf(c, (void **)&c->d_post_m2, &c->post_cap_m2, Mz * sizeof(int)))) return rc;
-    if ((rc = post_buf(c, (void **)&c->d_post_mean, &c->post_cap_mean, Mz * sizeof(float)))) return rc;
-    if ((rc = post_buf(c, (void **)&c->d_post_var, &c->post_cap_var, Mz * sizeof(float)))) return rc;
-    if (with_parts && (rc = post_buf(c, (void **)&c->d_post_parts, &c->post_cap_parts, Mz * D * sizeof(float)))) return rc;
-    // tile table, per size class (entries of a class share the view's leading dimension, hence the work-row stride), and chunks
-    // of consecutive tiles of one class whose work rows stay within the budget
-    // (joint call: chunks of whole patients, with their patients [pat0, pat0 + npat), tile pairs and row blocks)
-    struct Chunk { const SizeClass *k; int t0, nt; size_t stride; int pat0, npat, pair0, npair, blk0, nblk; };
-    std::vector<PostTile> tiles;
-    std::vector<Chunk> chunks;
-    std::vector<JointPat> jpats;
-    std::vector<JointTile> jpairs, jblks;
-    size_t work_need = 0, c_need = 0, cov_need = 0;
-    for (const SizeClass &k : c->plan.cls) {
-        const int t_begin = (int)tiles.size();
-        const size_t stride = (size_t)k.ld * 64 + ((with_parts && !parts_lds) ? (size_t)D * 64 : 0);   // doubles per tile
-        if (jq) {
-            Chunk ch{&k, t_begin, 0, stride, (int)jpats.size(), 0, (int)jpairs.size(), 0, (int)jblks.size(), 0};
-            size_t wbytes = 0, cdbl = 0, cflt = 0;
-            auto close = [&]() {
-                if (ch.npat == 0) return;
-                chunks.push_back(ch);
-                work_need = std::max(work_need, wbytes); c_need = std::max(c_need, cdbl * sizeof(double)); cov_need = std::max(cov_need, cflt * sizeof(float));
-                ch.t0 += ch.nt; ch.nt = 0; ch.pat0 += ch.npat; ch.npat = 0; ch.pair0 += ch.npair; ch.npair = 0; ch.blk0 += ch.nblk; ch.nblk = 0;
-                wbytes = cdbl = cflt = 0;
-            };
-            for (int i = k.b0; i < k.b0 + k.count; i++) {
-                const int b = c->plan.order[i];
-                const int64_t m = offsets[b + 1] - offsets[b];
-                if (m == 0) continue;
-                const int nt = (int)((m + POST_TW - 1) / POST_TW);
-                const size_t mpad = (size_t)nt * 64;
-                // V of all its tiles, C, and its float block of cov
-                const size_t need = (size_t)nt * stride * sizeof(double) + mpad * mpad * sizeof(double) + (want_cov ? (size_t)m * m * sizeof(float) : 0);
-                if (need > c->posterior_budget)
-                    return fail(c, MEDGP_ERR_CAPACITY, "patient %d: the joint posterior of %lld points on %d observations needs %zu MB at once, the budget is %zu MB (MEDGP_POSTERIOR_BUDGET_GB)",
-                                b, (long long)m, c->plan.en[i], need >> 20, c->posterior_budget >> 20);
-                if (wbytes + cdbl * sizeof(double) + cflt * sizeof(float) + need > c->posterior_budget) close();
-                const int pidx = (int)jpats.size();
-                jpats.push_back({i - k.b0, b, (int)offsets[b], (int)m, ch.nt, 0, (long long)cdbl, (long long)cflt});
-                for (int64_t p = offsets[b]; p < offsets[b + 1]; p += POST_TW)
-                    tiles.push_back({i - k.b0, (int)p, (int)std::min<int64_t>(POST_TW, offsets[b + 1] - p), 0});
-                for (int I = 0; I < nt; I++) {
-                    for (int J = 0; J <= I; J++) jpairs.push_back({pidx, I, J, 0});
-                    jblks.push_back({pidx, I, 0, 0});
-                }
-                ch.nt += nt; ch.npat++; ch.npair += nt * (nt + 1) / 2; ch.nblk += nt;
-                wbytes += (size_t)nt * stride * sizeof(double); cdbl += mpad * mpad; if (want_cov) cflt += (size_t)m * m;
-            }
-            close();
-            continue;
-        }
-        for (int i = k.b0; i < k.b0 + k.count; i++) {
-            const int b = c->plan.order[i];
-            for (int64_t p = offsets[b]; p < offsets[b + 1]; p += POST_TW)
-                tiles.push_back({i - k.b0, (int)p, (int)std::min<int64_t>(POST_TW, offsets[b + 1] - p), 0});
-        }
-        const int per_chunk = (int)std::max<size_t>(1, c->posterior_budget / (stride * sizeof(double)));
-        for (int t0 = t_begin; t0 < (int)tiles.size(); t0 += per_chunk) {
-            const int nt = std::min(per_chunk, (int)tiles.size() - t0);
-            chunks.push_back({&k, t0, nt, stride, 0, 0, 0, 0, 0, 0});
-            work_need = std::max(work_need, (size_t)nt * stride * sizeof(double));
-        }
+    JointTables T;
+    const size_t extra = (with_parts && !parts_lds) ? (size_t)D * 64 : 0;   // doubles per tile beyond its 64 work rows
+    if (!jq) build_point_tiles(table_classes(c->plan), c->plan.order.data(), offsets, nullptr, extra, c->posterior_budget, T);
+    else {
+        TableError e;
+        if (!build_joint_chunks(table_classes(c->plan), c->plan.order.data(), offsets, extra, want_cov, c->posterior_budget, T, e))
+            return fail(c, MEDGP_ERR_CAPACITY, "patient %d: the joint posterior of %lld points on %d observations needs %zu MB at once, the budget is %zu MB (MEDGP_POSTERIOR_BUDGET_GB)",
+                        e.b, e.m, c->plan.en[e.entry], e.need >> 20, c->posterior_budget >> 20);
     }
-    if (!tiles.empty()) {
-        if ((rc = post_buf(c, (void **)&c->d_post_tiles, &c->post_cap_tiles, tiles.size() * sizeof(PostTile)))) return rc;
-        if ((rc = post_buf(c, (void **)&c->d_post_work, &c->post_cap_work, work_need))) return rc;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
-    if (M > 0) {
-        HIPCHK(c, hipMemcpyAsync(c->d_post_t2, ht2.data(), sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_post_m2, hm2.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_post_tiles, tiles.data(), sizeof(PostTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
-    }
+    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if (with_parts && (rc = buf_ensure(c, BUF_PARTS, (size_t)std::max<int64_t>(M, 1) * D * sizeof(float)))) return rc;
+    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
+    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
     if (jq) {
-        if ((rc = post_buf(c, (void **)&c->d_joint_cstat, &c->joint_cap_cstat, sizeof(int) * nbatch))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->d_joint_cstat, 0, sizeof(int) * nbatch, c->stream));
+        if ((rc = buf_ensure(c, BUF_CSTAT, sizeof(int) * nbatch))) return rc;
+        HIPCHK(c, hipMemsetAsync(buf<int>(c, BUF_CSTAT), 0, sizeof(int) * nbatch, c->stream));
     }
-    if (jq && !jpats.empty()) {
-        if ((rc = post_buf(c, (void **)&c->d_joint_pats, &c->joint_cap_pats, jpats.size() * sizeof(JointPat)))) return rc;
-        if ((rc = post_buf(c, (void **)&c->d_joint_pairs, &c->joint_cap_pairs, jpairs.size() * sizeof(JointTile)))) return rc;
-        if ((rc = post_buf(c, (void **)&c->d_joint_blks, &c->joint_cap_blks, jblks.size() * sizeof(JointTile)))) return rc;
-        if ((rc = post_buf(c, (void **)&c->d_joint_C, &c->joint_cap_C, c_need))) return rc;
-        if (want_cov && (rc = post_buf(c, (void **)&c->d_joint_cov, &c->joint_cap_cov, cov_need))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->d_joint_pats, jpats.data(), sizeof(JointPat) * jpats.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_joint_pairs, jpairs.data(), sizeof(JointTile) * jpairs.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_joint_blks, jblks.data(), sizeof(JointTile) * jblks.size(), hipMemcpyHostToDevice, c->stream));
+    if (jq && !T.pats.empty()) {
+        if ((rc = upload_table(c, BUF_PATS, T.pats))) return rc;
+        if ((rc = upload_table(c, BUF_PAIRS, T.pairs))) return rc;
+        if ((rc = upload_table(c, BUF_BLKS, T.blks))) return rc;
+        if ((rc = buf_ensure(c, BUF_C, T.c_need))) return rc;
+        if (want_cov && (rc = buf_ensure(c, BUF_COV, T.cov_need))) return rc;
         if (want_samp) {
             const size_t ns = (size_t)M * jq->nsamp;
-            if ((rc = post_buf(c, (void **)&c->d_joint_eps, &c->joint_cap_eps, ns * sizeof(double)))) return rc;
-            if ((rc = post_buf(c, (void **)&c->d_joint_samp, &c->joint_cap_samp, ns * sizeof(float)))) return rc;
-            HIPCHK(c, hipMemcpyAsync(c->d_joint_eps, jq->eps, ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            if ((rc = buf_ensure(c, BUF_EPS, ns * sizeof(double)))) return rc;
+            if ((rc = buf_ensure(c, BUF_SAMP, ns * sizeof(float)))) return rc;
+            HIPCHK(c, hipMemcpyAsync(buf<double>(c, BUF_EPS), jq->eps, ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
         }
     }
     // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
-    if ((rc = run_pipeline(c, nbatch, max_n, c->d_theta, 0, false, 1, nullptr, nullptr, nullptr, true, true))) return rc;
+    if ((rc = factor_run(c, nbatch, max_n, theta, false, true))) return rc;
     if (with_parts && M > 0)
         for (const SizeClass &k : c->plan.cls) {   // (behind the join of the classes' chains)
             Launcher l(c, KID_ALPHA);
             hipLaunchKernelGGL(k_alpha, dim3(k.count), dim3(256), 0, c->stream, class_view(c, c->plan, k));
         }
-    for (const Chunk &ch : chunks) {   // chunks reuse the work rows in stream order
+    const JointPat *d_pats = buf<JointPat>(c, BUF_PATS);
+    double *d_C = buf<double>(c, BUF_C);
+    int *d_cstat = buf<int>(c, BUF_CSTAT);
+    for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
         Launcher l(c, KID_POSTERIOR);
-        const MedgpDev V = class_view(c, c->plan, *ch.k);
-        launch_posterior(c, V, ch.nt, c->d_post_tiles + ch.t0, ch.stride, with_parts ? 1 : 0, parts_lds);
+        const MedgpDev V = class_view(c, c->plan, c->plan.cls[ch.cls]);
+        launch_posterior(c, V, ch.nt, buf<PostTile>(c, BUF_TILES) + ch.t0, ch.stride, with_parts ? 1 : 0, parts_lds);
         if (!jq) continue;
         l.finish();
         {
             Launcher lc(c, KID_POSTCOV);
-            launch_postcov(c, V, ch.npair, c->d_joint_pairs + ch.pair0, ch.stride, want_cov ? c->d_joint_cov : nullptr);
+            launch_postcov(c, V, ch.npair, buf<JointTile>(c, BUF_PAIRS) + ch.pair0, ch.stride, want_cov ? buf<float>(c, BUF_COV) : nullptr);
         }
         if (want_samp) {   // (a covariance-only call factors nothing)
             {
                 Launcher lf(c, KID_POSTFACTOR);
-                hipLaunchKernelGGL(k_postfactor, dim3(ch.npat), dim3(256), 0, c->stream, V, c->d_joint_pats + ch.pat0, c->d_joint_C, c->d_joint_cstat);
+                hipLaunchKernelGGL(k_postfactor, dim3(ch.npat), dim3(256), 0, c->stream, V, d_pats + ch.pat0, d_C, d_cstat);
             }
             Launcher ld(c, KID_POSTDRAW);
-            hipLaunchKernelGGL(k_postdraw, dim3(ch.nblk), dim3(256), 0, c->stream, V, c->d_joint_pats, c->d_joint_blks + ch.blk0, c->d_post_work, ch.stride,
-                               c->d_joint_C, c->d_joint_cstat, c->d_joint_eps, jq->nsamp, c->d_joint_samp);
+            hipLaunchKernelGGL(k_postdraw, dim3(ch.nblk), dim3(256), 0, c->stream, V, d_pats, buf<JointTile>(c, BUF_BLKS) + ch.blk0, buf<double>(c, BUF_WORK), ch.stride,
+                               d_C, d_cstat, buf<double>(c, BUF_EPS), jq->nsamp, buf<float>(c, BUF_SAMP));
         }
         if (want_cov)   // the chunk's blocks go home before the next chunk reuses the buffer (stream order)
             for (int i = ch.pat0; i < ch.pat0 + ch.npat; i++) {
-                const JointPat &P = jpats[i];
-                HIPCHK(c, hipMemcpyAsync(jq->cov + cov_off[P.b], c->d_joint_cov + P.voff, sizeof(float) * (size_t)P.m * P.m, hipMemcpyDeviceToHost, c->stream));
+                const JointPat &P = T.pats[i];
+                HIPCHK(c, hipMemcpyAsync(jq->cov + cov_off[P.b], buf<float>(c, BUF_COV) + P.voff, sizeof(float) * (size_t)P.m * P.m, hipMemcpyDeviceToHost, c->stream));
             }
     }
     HIPCHK(c, hipGetLastError());
     if (M > 0) {
-        HIPCHK(c, hipMemcpyAsync(mean, c->d_post_mean, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(var, c->d_post_var, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        if (with_parts) HIPCHK(c, hipMemcpyAsync(parts, c->d_post_parts, sizeof(float) * M * D, hipMemcpyDeviceToHost, c->stream));
-        if (want_samp) HIPCHK(c, hipMemcpyAsync(jq->samples, c->d_joint_samp, sizeof(float) * (size_t)M * jq->nsamp, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(mean, buf<float>(c, BUF_MEAN), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(var, buf<float>(c, BUF_VAR), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        if (with_parts) HIPCHK(c, hipMemcpyAsync(parts, buf<float>(c, BUF_PARTS), sizeof(float) * M * D, hipMemcpyDeviceToHost, c->stream));
+        if (want_samp) HIPCHK(c, hipMemcpyAsync(jq->samples, buf<float>(c, BUF_SAMP), sizeof(float) * (size_t)M * jq->nsamp, hipMemcpyDeviceToHost, c->stream));
     }
-    std::vector<int> st(nbatch, 0), cst(nbatch, 0);
-    if (status || jq) HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    if (jq) HIPCHK(c, hipMemcpyAsync(cst.data(), c->d_joint_cstat, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (status) for (int i = 0; i < nbatch; i++) status[c->plan.order[i]] = st[i];   // internal order -> the caller's
+    std::vector<int> st, cst(nbatch, 0);
+    if (jq) HIPCHK(c, hipMemcpyAsync(cst.data(), d_cstat, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = read_status(c, nbatch, status, jq ? &st : nullptr))) return rc;
     if (jq && jq->cov_status)   // (caller order on the device; a patient without a factor has no C either)
         for (int i = 0; i < nbatch; i++) { const int b = c->plan.order[i]; jq->cov_status[b] = (st[i] < 0 || cst[b] < 0) ? -1 : 0; }
     return MEDGP_OK;
-}
-
-void launch_forecast(medgp_ctx *c, const MedgpDev &V, int ntiles, const ForeTile *tiles, size_t stride, bool with_lpd, double log2pi) {
-    const dim3 tg(ntiles), tb(256);
-#define MEDGP_FORE(QQ) hipLaunchKernelGGL(k_forecast<QQ>, tg, tb, 0, c->stream, V, tiles, c->d_post_m2, c->d_post_t2, c->d_fore_prefix, \
-                                          with_lpd ? c->d_fore_y2 : nullptr, c->d_post_work, stride, log2pi, c->d_post_mean, c->d_post_var, c->d_fore_lpd)
-    switch (V.Q) {
-    case 1: MEDGP_FORE(1); break;
-    case 2: MEDGP_FORE(2); break;
-    case 3: MEDGP_FORE(3); break;
-    case 4: MEDGP_FORE(4); break;
-    case 5: MEDGP_FORE(5); break;
-    case 6: MEDGP_FORE(6); break;
-    case 7: MEDGP_FORE(7); break;
-    case 8: MEDGP_FORE(8); break;
-    default: MEDGP_FORE(0); break;   // Q > 8: generic component loop
-    }
-#undef MEDGP_FORE
 }
 
 // medgp_forecast_batch (kernels_forecast.h): the posterior call's pipeline run on the CALLER-order copies, then k_forecast over tiles
@@ -2191,20 +2145,10 @@ int forecast_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
     if ((y2 == nullptr) != (lpd == nullptr)) return fail(c, MEDGP_ERR_ARG, "y2 and lpd must both be given or both be NULL");
-    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
-    if (nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
-    if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
-    for (int b = 0; b < nbatch; b++)
-        if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
+    int max_n = 0, rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    if ((rc = check_points(c, nbatch, offsets, meta2, t2, mean, var))) return rc;
     const int64_t M = offsets[nbatch];
-    if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
-    if (M > 0 && (!t2 || !mean || !var)) return fail(c, MEDGP_ERR_ARG, "t2 / mean / var is NULL");
-    if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
-    for (int b = 0; b < nbatch; b++) {
-        const int s = slots[b];
-        if (s < 0 || s >= c->max_slots || c->h_n[s] < 0) return fail(c, MEDGP_ERR_ARG, "slots[%d] = %d is not a resident patient", b, s);
-    }
-    const int D = c->D;
     // the device order of the points: inside each patient stably sorted by prefix (src[k] = the caller's index of device point k)
     std::vector<int64_t> src(M);
     std::vector<int> hpf(M);
@@ -2219,88 +2163,44 @@ int forecast_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *
             std::stable_sort(src.begin() + offsets[b], src.begin() + offsets[b + 1], [&](int64_t a, int64_t z) { return prefix[a] < prefix[z]; });
         for (int64_t k = offsets[b]; k < offsets[b + 1]; k++) hpf[k] = prefix ? prefix[src[k]] : n;
     }
-    std::vector<double> ht2(M), hy2(y2 ? M : 0);
-    std::vector<int> hm2(M, 0);
-    for (int64_t k = 0; k < M; k++) {
-        const int64_t j = src[k];
-        ht2[k] = (double)t2[j];
-        if (y2) hy2[k] = (double)y2[j];
-        if (meta2 && c->kidx == MEDGP_KERNEL_LMC_SM) {
-            if (meta2[j] < 0 || meta2[j] >= D) return fail(c, MEDGP_ERR_ARG, "meta2[%lld] = %d outside [0, %d)", (long long)j, meta2[j], D);
-            hm2[k] = meta2[j];
-        }
-    }
+    std::vector<double> ht2, hy2(y2 ? M : 0);
+    std::vector<int> hm2;
+    if ((rc = stage_points(c, M, meta2, t2, src.data(), ht2, hm2))) return rc;
+    for (int64_t k = 0; y2 && k < M; k++) hy2[k] = (double)y2[src[k]];
     HIPCHK(c, hipSetDevice(c->device));
-    int max_n = 0, rc;
     // "the first p observations" is the caller's order: a patient not uploaded grouped by output is factored on its caller-order copy
     if ((rc = set_batch(c, nbatch, slots, &max_n, true, true))) return rc;
-    const size_t Mz = (size_t)std::max<int64_t>(M, 1);
-    if ((rc = post_buf(c, (void **)&c->d_post_t2, &c->post_cap_pts, Mz * sizeof(double)))) return rc;
-    if ((rc = post_buf(c, (void **)&c->d_post_m2, &c->post_cap_m2, Mz * sizeof(int)))) return rc;
-    if ((rc = post_buf(c, (void **)&c->d_post_mean, &c->post_cap_mean, Mz * sizeof(float)))) return rc;
-    if ((rc = post_buf(c, (void **)&c->d_post_var, &c->post_cap_var, Mz * sizeof(float)))) return rc;
-    if ((rc = post_buf(c, (void **)&c->d_fore_prefix, &c->fore_cap_prefix, Mz * sizeof(int)))) return rc;
-    if (y2 && (rc = post_buf(c, (void **)&c->d_fore_y2, &c->fore_cap_y2, Mz * sizeof(double)))) return rc;
-    if (y2 && (rc = post_buf(c, (void **)&c->d_fore_lpd, &c->fore_cap_lpd, Mz * sizeof(double)))) return rc;
-    // tile table per size class and launch chunks within the budget, as the posterior call's
-    struct Chunk { const SizeClass *k; int t0, nt; size_t stride; };
-    std::vector<ForeTile> tiles;
-    std::vector<Chunk> chunks;
-    size_t work_need = 0;
-    for (const SizeClass &k : c->plan.cls) {
-        const int t_begin = (int)tiles.size();
-        const size_t stride = (size_t)k.ld * 64;   // doubles per tile
-        for (int i = k.b0; i < k.b0 + k.count; i++) {
-            const int b = c->plan.order[i];
-            for (int64_t p = offsets[b]; p < offsets[b + 1]; p += POST_TW) {
-                const int cnt = (int)std::min<int64_t>(POST_TW, offsets[b + 1] - p);
-                tiles.push_back({i - k.b0, (int)p, cnt, hpf[p + cnt - 1]});   // (sorted: the tile's last point has its largest prefix)
-            }
-        }
-        const int per_chunk = (int)std::max<size_t>(1, c->posterior_budget / (stride * sizeof(double)));
-        for (int t0 = t_begin; t0 < (int)tiles.size(); t0 += per_chunk) {
-            const int nt = std::min(per_chunk, (int)tiles.size() - t0);
-            chunks.push_back({&k, t0, nt, stride});
-            work_need = std::max(work_need, (size_t)nt * stride * sizeof(double));
-        }
-    }
+    // tile table per size class and launch chunks within the budget, as the posterior call's -- and in its buffers
     static_assert(sizeof(ForeTile) == sizeof(PostTile), "the forecast tiles travel in the posterior call's tile buffer");
-    if (!tiles.empty()) {
-        if ((rc = post_buf(c, (void **)&c->d_post_tiles, &c->post_cap_tiles, tiles.size() * sizeof(ForeTile)))) return rc;
-        if ((rc = post_buf(c, (void **)&c->d_post_work, &c->post_cap_work, work_need))) return rc;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
-    if (M > 0) {
-        HIPCHK(c, hipMemcpyAsync(c->d_post_t2, ht2.data(), sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_post_m2, hm2.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_fore_prefix, hpf.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
-        if (y2) HIPCHK(c, hipMemcpyAsync(c->d_fore_y2, hy2.data(), sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_post_tiles, tiles.data(), sizeof(ForeTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
-    }
+    PointTables<ForeTile> T;
+    build_point_tiles(table_classes(c->plan), c->plan.order.data(), offsets, hpf.data(), 0, c->posterior_budget, T);
+    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if ((rc = upload_table(c, BUF_PREFIX, hpf))) return rc;
+    if (y2 && (rc = upload_table(c, BUF_Y2, hy2))) return rc;
+    if (y2 && (rc = buf_ensure(c, BUF_LPD, (size_t)std::max<int64_t>(M, 1) * sizeof(double)))) return rc;
+    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
+    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
     // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
-    if ((rc = run_pipeline(c, nbatch, max_n, c->d_theta, 0, false, 1, nullptr, nullptr, nullptr, true, true))) return rc;
+    if ((rc = factor_run(c, nbatch, max_n, theta, false, true))) return rc;
     const double log2pi = std::log(2.0 * c->pi);
-    for (const Chunk &ch : chunks) {   // chunks reuse the work rows in stream order
+    for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
         Launcher l(c, KID_FORECAST);
-        launch_forecast(c, class_view(c, c->plan, *ch.k), ch.nt, (const ForeTile *)c->d_post_tiles + ch.t0, ch.stride, y2 != nullptr, log2pi);
+        launch_forecast(c, class_view(c, c->plan, c->plan.cls[ch.cls]), ch.nt, buf<ForeTile>(c, BUF_TILES) + ch.t0, ch.stride, y2 != nullptr, log2pi);
     }
     HIPCHK(c, hipGetLastError());
     std::vector<float> hmean(M), hvar(M);
     std::vector<double> hlpd(y2 ? M : 0);
     if (M > 0) {
-        HIPCHK(c, hipMemcpyAsync(hmean.data(), c->d_post_mean, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(hvar.data(), c->d_post_var, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        if (y2) HIPCHK(c, hipMemcpyAsync(hlpd.data(), c->d_fore_lpd, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(hmean.data(), buf<float>(c, BUF_MEAN), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(hvar.data(), buf<float>(c, BUF_VAR), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        if (y2) HIPCHK(c, hipMemcpyAsync(hlpd.data(), buf<double>(c, BUF_LPD), sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
     }
-    std::vector<int> st(nbatch, 0);
-    if (status) HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = read_status(c, nbatch, status))) return rc;
     for (int64_t k = 0; k < M; k++) {   // sorted order -> the caller's
         mean[src[k]] = hmean[k];
         var[src[k]] = hvar[k];
         if (y2) lpd[src[k]] = hlpd[k];
     }
-    if (status) for (int i = 0; i < nbatch; i++) status[c->plan.order[i]] = st[i];   // internal order -> the caller's
     return MEDGP_OK;
 }
 }  // namespace
@@ -2334,15 +2234,13 @@ int medgp_loo_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     if (!slots || !theta || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
     if (!mean && !var && !lpd && !total) return fail(c, MEDGP_ERR_ARG, "none of mean, var, lpd and total asked for");
     if (group && !ngroups) return fail(c, MEDGP_ERR_ARG, "ngroups is NULL with group ids");
-    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
-    if (nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
+    int max_n = 0, rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
     std::vector<int64_t> ooff(nbatch + 1, 0), goff(nbatch + 1, 0);   // first observation / first group of patient b in the call
     for (int b = 0; b < nbatch; b++) {
-        const int s = slots[b];
-        if (s < 0 || s >= c->max_slots || c->h_n[s] < 0) return fail(c, MEDGP_ERR_ARG, "slots[%d] = %d is not a resident patient", b, s);
         if (group && ngroups[b] < 0) return fail(c, MEDGP_ERR_ARG, "ngroups[%d] = %d", b, ngroups[b]);
-        ooff[b + 1] = ooff[b] + c->h_n[s];
-        goff[b + 1] = goff[b] + (group ? ngroups[b] : c->h_n[s]);
+        ooff[b + 1] = ooff[b] + c->h_n[slots[b]];
+        goff[b + 1] = goff[b] + (group ? ngroups[b] : c->h_n[slots[b]]);
     }
     const int64_t NO = ooff[nbatch], NG = goff[nbatch];
     if (NO > (int64_t)INT32_MAX || NG > (int64_t)INT32_MAX) return fail(c, MEDGP_ERR_ARG, "%lld observations in %lld groups in one call", (long long)NO, (long long)NG);
@@ -2352,113 +2250,49 @@ int medgp_loo_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double
                 if (group[i] < -1 || group[i] >= ngroups[b])
                     return fail(c, MEDGP_ERR_ARG, "group[%lld] = %d outside [-1, %d) (patient %d)", (long long)i, group[i], ngroups[b], b);
     HIPCHK(c, hipSetDevice(c->device));
-    int max_n = 0, rc;
     if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
     const bool want_lpd = lpd || total;
-    // tables: per size class its singletons; chunks of larger groups (whole groups, blocks within the budget) with their tile pairs
-    // and solve jobs -- one workgroup per table row, so ragged groups cost no idle workgroups
-    struct Chunk { const SizeClass *k; int g0, ng, pair0, npair, job0, njob; };
-    struct ClassSingles { const SizeClass *k; int s0, ns; };
-    std::vector<LooSingle> singles;
-    std::vector<ClassSingles> csing;
-    std::vector<LooRow> rows;
-    std::vector<JointPat> groups;
-    std::vector<JointTile> pairs, jobs;
-    std::vector<Chunk> chunks;
-    std::vector<int> gsize((size_t)NG, 0), cnt, start, fill;
-    size_t blk_need = 0;
-    for (const SizeClass &k : c->plan.cls) {
-        const int s0 = (int)singles.size();
-        Chunk ch{&k, (int)groups.size(), 0, (int)pairs.size(), 0, (int)jobs.size(), 0};
-        size_t cdbl = 0;
-        auto close = [&]() {
-            if (ch.ng == 0) return;
-            chunks.push_back(ch);
-            blk_need = std::max(blk_need, cdbl * sizeof(double));
-            ch.g0 += ch.ng; ch.ng = 0; ch.pair0 += ch.npair; ch.npair = 0; ch.job0 += ch.njob; ch.njob = 0;
-            cdbl = 0;
-        };
-        for (int i = k.b0; i < k.b0 + k.count; i++) {
-            const int b = c->plan.order[i], slot = slots[b], n = c->plan.en[i], G = (int)(goff[b + 1] - goff[b]);
-            const bool ident = c->h_perm_identity[slot] != 0;
-            const std::vector<int> &perm = c->h_perm[slot];
-            auto gid_of = [&](int r, int *cobs) { *cobs = ident ? r : perm[r]; return group ? group[ooff[b] + *cobs] : *cobs; };
-            cnt.assign(G, 0); start.assign(G, -1); fill.assign(G, 0);
-            int co;
-            for (int r = 0; r < n; r++) { const int gid = gid_of(r, &co); if (gid >= 0) cnt[gid]++; }
-            for (int gid = 0; gid < G; gid++) {
-                gsize[goff[b] + gid] = cnt[gid];
-                if (cnt[gid] < 2) continue;
-                const size_t need = loo_block_doubles(cnt[gid]) * sizeof(double);
-                if (need > c->posterior_budget)
-                    return fail(c, MEDGP_ERR_CAPACITY, "patient %d: group %d of %d observations needs %zu MB at once, the budget is %zu MB (MEDGP_POSTERIOR_BUDGET_GB)",
-                                b, gid, cnt[gid], need >> 20, c->posterior_budget >> 20);
-                if (cdbl * sizeof(double) + need > c->posterior_budget) close();
-                const int gidx = (int)groups.size(), nt = medgp_roundup(cnt[gid], 64) / 64;
-                start[gid] = (int)rows.size();
-                rows.resize(rows.size() + cnt[gid]);
-                groups.push_back({i - k.b0, (int)(goff[b] + gid), start[gid], cnt[gid], 0, 0, (long long)cdbl, 0});
-                for (int I = 0; I < nt; I++)
-                    for (int J = 0; J <= I; J++) pairs.push_back({gidx, I, J, 0});
-                int nj = 0;
-                if (var) for (int I = 0; I < nt; I++, nj++) jobs.push_back({gidx, I, 0, 0});
-                if (mean || want_lpd) { jobs.push_back({gidx, 0, 1, 0}); nj++; }
-                ch.ng++; ch.npair += nt * (nt + 1) / 2; ch.njob += nj;
-                cdbl += loo_block_doubles(cnt[gid]);
-            }
-            for (int r = 0; r < n; r++) {   // (rows ascending: the index list of a group is sorted, stably)
-                const int gid = gid_of(r, &co);
-                if (gid < 0) continue;
-                if (cnt[gid] == 1) singles.push_back({i - k.b0, r, (int)(ooff[b] + co), (int)(goff[b] + gid)});
-                else rows[start[gid] + fill[gid]++] = {r, (int)(ooff[b] + co)};
-            }
-        }
-        close();
-        csing.push_back({&k, s0, (int)singles.size() - s0});
-    }
-    void **D = c->d_loo;
-    size_t *cap = c->loo_cap;
+    std::vector<const int *> perm(nbatch);   // internal row -> caller observation (null: the patient was uploaded grouped)
+    for (int b = 0; b < nbatch; b++) perm[b] = c->h_perm_identity[slots[b]] ? nullptr : c->h_perm[slots[b]].data();
+    LooTables T;
+    TableError e;
+    if (!build_loo_tables(table_classes(c->plan), c->plan.order.data(), c->plan.en.data(), ooff.data(), goff.data(), nbatch, group, perm.data(),
+                          var != nullptr, mean || want_lpd, c->posterior_budget, T, e))
+        return fail(c, MEDGP_ERR_CAPACITY, "patient %d: group %d of %d observations needs %zu MB at once, the budget is %zu MB (MEDGP_POSTERIOR_BUDGET_GB)",
+                    e.b, e.gid, (int)e.m, e.need >> 20, c->posterior_budget >> 20);
     const size_t NOz = (size_t)std::max<int64_t>(NO, 1), NGz = (size_t)std::max<int64_t>(NG, 1);
-    if ((rc = post_buf(c, &D[LOO_MEAN], &cap[LOO_MEAN], NOz * sizeof(float)))) return rc;
-    if ((rc = post_buf(c, &D[LOO_VAR], &cap[LOO_VAR], NOz * sizeof(float)))) return rc;
-    if ((rc = post_buf(c, &D[LOO_LPD], &cap[LOO_LPD], NGz * sizeof(double)))) return rc;
-    if ((rc = post_buf(c, &D[LOO_GSTAT], &cap[LOO_GSTAT], NGz * sizeof(int)))) return rc;
-    if ((rc = post_buf(c, &D[LOO_SINGLES], &cap[LOO_SINGLES], singles.size() * sizeof(LooSingle)))) return rc;
-    if ((rc = post_buf(c, &D[LOO_ROWS], &cap[LOO_ROWS], rows.size() * sizeof(LooRow)))) return rc;
-    if ((rc = post_buf(c, &D[LOO_GROUPS], &cap[LOO_GROUPS], groups.size() * sizeof(JointPat)))) return rc;
-    if ((rc = post_buf(c, &D[LOO_PAIRS], &cap[LOO_PAIRS], pairs.size() * sizeof(JointTile)))) return rc;
-    if ((rc = post_buf(c, &D[LOO_JOBS], &cap[LOO_JOBS], jobs.size() * sizeof(JointTile)))) return rc;
-    if ((rc = post_buf(c, &D[LOO_BLOCKS], &cap[LOO_BLOCKS], blk_need))) return rc;
-    float *d_mean = (float *)D[LOO_MEAN], *d_var = (float *)D[LOO_VAR];
-    double *d_lpd = (double *)D[LOO_LPD], *d_blocks = (double *)D[LOO_BLOCKS];
-    int *d_gstat = (int *)D[LOO_GSTAT];
-    const LooSingle *d_singles = (const LooSingle *)D[LOO_SINGLES];
-    const LooRow *d_rows = (const LooRow *)D[LOO_ROWS];
-    const JointPat *d_groups = (const JointPat *)D[LOO_GROUPS];
-    const JointTile *d_pairs = (const JointTile *)D[LOO_PAIRS], *d_jobs = (const JointTile *)D[LOO_JOBS];
-    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
+    if ((rc = buf_ensure(c, BUF_MEAN, NOz * sizeof(float)))) return rc;
+    if ((rc = buf_ensure(c, BUF_VAR, NOz * sizeof(float)))) return rc;
+    if ((rc = buf_ensure(c, BUF_LPD, NGz * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_CSTAT, NGz * sizeof(int)))) return rc;
+    if ((rc = buf_ensure(c, BUF_C, T.blk_need))) return rc;
+    float *d_mean = buf<float>(c, BUF_MEAN), *d_var = buf<float>(c, BUF_VAR);
+    double *d_lpd = buf<double>(c, BUF_LPD), *d_blocks = buf<double>(c, BUF_C);
+    int *d_gstat = buf<int>(c, BUF_CSTAT);
     HIPCHK(c, hipMemsetAsync(d_mean, 0xFF, NOz * sizeof(float), c->stream));   // all ones: NaN, float and double
     HIPCHK(c, hipMemsetAsync(d_var, 0xFF, NOz * sizeof(float), c->stream));
     HIPCHK(c, hipMemsetAsync(d_lpd, 0xFF, NGz * sizeof(double), c->stream));
     HIPCHK(c, hipMemsetAsync(d_gstat, 0, NGz * sizeof(int), c->stream));
-    if (!singles.empty()) HIPCHK(c, hipMemcpyAsync(D[LOO_SINGLES], singles.data(), singles.size() * sizeof(LooSingle), hipMemcpyHostToDevice, c->stream));
-    if (!groups.empty()) {
-        HIPCHK(c, hipMemcpyAsync(D[LOO_ROWS], rows.data(), rows.size() * sizeof(LooRow), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(D[LOO_GROUPS], groups.data(), groups.size() * sizeof(JointPat), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(D[LOO_PAIRS], pairs.data(), pairs.size() * sizeof(JointTile), hipMemcpyHostToDevice, c->stream));
-        if (!jobs.empty()) HIPCHK(c, hipMemcpyAsync(D[LOO_JOBS], jobs.data(), jobs.size() * sizeof(JointTile), hipMemcpyHostToDevice, c->stream));
-    }
+    if ((rc = upload_table(c, BUF_SINGLES, T.singles))) return rc;
+    if ((rc = upload_table(c, BUF_ROWS, T.rows))) return rc;
+    if ((rc = upload_table(c, BUF_PATS, T.groups))) return rc;
+    if ((rc = upload_table(c, BUF_PAIRS, T.pairs))) return rc;
+    if ((rc = upload_table(c, BUF_BLKS, T.jobs))) return rc;
+    const LooSingle *d_singles = buf<LooSingle>(c, BUF_SINGLES);
+    const LooRow *d_rows = buf<LooRow>(c, BUF_ROWS);
+    const JointPat *d_groups = buf<JointPat>(c, BUF_PATS);
+    const JointTile *d_pairs = buf<JointTile>(c, BUF_PAIRS), *d_jobs = buf<JointTile>(c, BUF_BLKS);
     // factor, U = L^-T and alpha = K^-1 y of every entry: the ONE pipeline run of the call (medgp_get_factor is valid afterwards)
-    if ((rc = run_pipeline(c, nbatch, max_n, c->d_theta, 0, true, 1, nullptr, nullptr, nullptr, false, true))) return rc;
+    if ((rc = factor_run(c, nbatch, max_n, theta, true, false))) return rc;
     const double log2pi = std::log(2.0 * c->pi);
-    for (const ClassSingles &s : csing) {
+    for (const LooClassSingles &s : T.csing) {
         if (s.ns == 0) continue;
         Launcher l(c, KID_LOO_DIAG);
-        hipLaunchKernelGGL(k_loo_diag, dim3((s.ns + 3) / 4), dim3(256), 0, c->stream, class_view(c, c->plan, *s.k), d_singles + s.s0, s.ns, log2pi,
+        hipLaunchKernelGGL(k_loo_diag, dim3((s.ns + 3) / 4), dim3(256), 0, c->stream, class_view(c, c->plan, c->plan.cls[s.cls]), d_singles + s.s0, s.ns, log2pi,
                            mean ? d_mean : nullptr, var ? d_var : nullptr, want_lpd ? d_lpd : nullptr);
     }
-    for (const Chunk &ch : chunks) {   // chunks reuse the blocks in stream order
-        const MedgpDev V = class_view(c, c->plan, *ch.k);
+    for (const LooChunk &ch : T.chunks) {   // chunks reuse the blocks in stream order
+        const MedgpDev V = class_view(c, c->plan, c->plan.cls[ch.cls]);
         {
             Launcher l(c, KID_LOO_GRAM);
             hipLaunchKernelGGL(k_loo_gram, dim3(ch.npair), dim3(256), 0, c->stream, V, d_groups, d_pairs + ch.pair0, d_rows, d_blocks);
@@ -2476,23 +2310,21 @@ int medgp_loo_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     HIPCHK(c, hipGetLastError());
     std::vector<double> hl(lpd ? 0 : (want_lpd ? (size_t)NG : 0));
     double *lp = lpd ? lpd : hl.data();
-    std::vector<int> st(nbatch, 0), gst((size_t)NG, 0);
+    std::vector<int> st, gst((size_t)NG, 0);
     if (mean && NO > 0) HIPCHK(c, hipMemcpyAsync(mean, d_mean, sizeof(float) * NO, hipMemcpyDeviceToHost, c->stream));
     if (var && NO > 0) HIPCHK(c, hipMemcpyAsync(var, d_var, sizeof(float) * NO, hipMemcpyDeviceToHost, c->stream));
     if (want_lpd && NG > 0) HIPCHK(c, hipMemcpyAsync(lp, d_lpd, sizeof(double) * NG, hipMemcpyDeviceToHost, c->stream));
     if (NG > 0) HIPCHK(c, hipMemcpyAsync(gst.data(), d_gstat, sizeof(int) * NG, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = read_status(c, nbatch, status, &st))) return rc;
     for (int i = 0; i < nbatch; i++) {
-        const int b = c->plan.order[i];   // internal order -> the caller's
+        const int b = c->plan.order[i];
         const bool ok = st[i] >= 0;
-        if (status) status[b] = st[i];
         double sum = 0.0;
         for (int64_t g = goff[b]; g < goff[b + 1]; g++) {
             if (group_status) group_status[g] = (!ok || gst[g] < 0) ? -1 : 0;
             if (!want_lpd) continue;
-            if (ok && gsize[g] == 0) lp[g] = 0.0;   // an empty group
-            sum += lp[g];                            // (group-id order)
+            if (ok && T.gsize[g] == 0) lp[g] = 0.0;   // an empty group
+            sum += lp[g];                              // (group-id order)
         }
         if (total) total[b] = ok ? sum : (double)NAN;
     }
@@ -2510,22 +2342,20 @@ int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
     if (flag_grad && !grad) return fail(c, MEDGP_ERR_ARG, "grad is NULL with flag_grad set");
     if (c->Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_loo_grad supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds K^-1 here", c->Q);
-    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
-    if (nbatch < 1 || nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
-    HIPCHK(c, hipSetDevice(c->device));
     int max_n = 0, rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
     if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
     const BatchPlan &P = c->plan;
-    if ((rc = post_buf(c, &c->d_loo[LOO_GVEC], &c->loo_cap[LOO_GVEC], 4 * P.need_vec * sizeof(double)))) return rc;
-    double *gvec = (double *)c->d_loo[LOO_GVEC];
+    if ((rc = buf_ensure(c, BUF_GVEC, 4 * P.need_vec * sizeof(double)))) return rc;
+    double *gvec = buf<double>(c, BUF_GVEC);
     const size_t H = c->H;
     // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
     if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
-    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * H * nbatch, hipMemcpyHostToDevice, c->stream));
     // the generic kernels (MEDGP_V0) keep W where P goes: this call always takes the templated ones
     const bool v0 = c->use_v0;
     c->use_v0 = false;
-    rc = run_pipeline(c, nbatch, max_n, c->d_theta, 0, true, 1, nullptr, nullptr, nullptr, false, true);
+    rc = factor_run(c, nbatch, max_n, theta, true, false);
     c->use_v0 = v0;
     if (rc) return rc;
     const double log2pi = std::log(2.0 * c->pi);
@@ -2538,24 +2368,15 @@ int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
             Launcher l(c, KID_LOO_VEC);
             hipLaunchKernelGGL(k_loo_vec, dim3(1, nb), dim3(256), 0, c->stream, V, vec, 2, log2pi);
         } else {
-            bool ragged = false;
-            for (int bb = 1; bb < nb; bb++) ragged = ragged || blocks64(P.en[k.b0 + bb]) != blocks64(P.en[k.b0]);
-            const int wg_tiles = tri(nt64), nbp = (ragged && nb < 64) ? (nb | 1) : nb;   // (k_wgrad's grid)
-            const dim3 tg(std::max(8 * ((nb + 7) / 8), nbp) * wg_tiles), tb(WG_THREADS);
-            { Launcher l(c, KID_LOO_KINV); hipLaunchKernelGGL(k_loo_kinv, tg, tb, 0, c->stream, V, nb, wg_tiles, nbp); }
+            const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
+            const dim3 tg = wg.grid, tb(WG_THREADS);
+            { Launcher l(c, KID_LOO_KINV); hipLaunchKernelGGL(k_loo_kinv, tg, tb, 0, c->stream, V, nb, wg.wg_tiles, wg.nbp); }
             { Launcher l(c, KID_LOO_VEC); hipLaunchKernelGGL(k_loo_vec, dim3(4 * nt64, nb), dim3(256), 0, c->stream, V, vec, 1, log2pi); }
             {
-                Launcher l(c, KID_LOO_WGRAD);
-#define MEDGP_LWG1(QQ) case QQ: hipLaunchKernelGGL((k_loo_wgrad<QQ, 0>), tg, tb, 0, c->stream, V, vec, nb, wg_tiles, nbp); break;
-#define MEDGP_LWG2(QR) case 8 + QR: hipLaunchKernelGGL((k_loo_wgrad<8, 0>), tg, tb, 0, c->stream, V, vec, nb, wg_tiles, nbp); \
-                                    hipLaunchKernelGGL((k_loo_wgrad<QR, 8>), tg, tb, 0, c->stream, V, vec, nb, wg_tiles, nbp); break;
-                switch (V.Q) {
-                MEDGP_LWG1(1) MEDGP_LWG1(2) MEDGP_LWG1(3) MEDGP_LWG1(4) MEDGP_LWG1(5) MEDGP_LWG1(6) MEDGP_LWG1(7) MEDGP_LWG1(8)
-                MEDGP_LWG2(1) MEDGP_LWG2(2) MEDGP_LWG2(3) MEDGP_LWG2(4) MEDGP_LWG2(5) MEDGP_LWG2(6) MEDGP_LWG2(7) MEDGP_LWG2(8)
-                default: break;   // (not reached: Q <= 16 was checked)
-                }
-#undef MEDGP_LWG1
-#undef MEDGP_LWG2
+                Launcher l(c, KID_LOO_WGRAD);   // (Q <= 16 was checked)
+                with_q16(V.Q, [&](auto q, auto q0) {
+                    hipLaunchKernelGGL((k_loo_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, vec, nb, wg.wg_tiles, wg.nbp);
+                });
             }
             const int nbins3 = 3 * V.Q * tri(V.D);
             Launcher l(c, KID_EPILOGUE);
