@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 8: medgp_forecast_batch (7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 9: medgp_trend_batch (8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -364,6 +364,39 @@ int medgp_loo_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const doubl
 int medgp_forecast_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
                          const int32_t *meta2, const float *t2, const int32_t *prefix, const float *y2,
                          float *mean, float *var, double *lpd, int32_t *status);
+
+/* Posterior of the latent SLOPE at the test points, next to the posterior of the value: is the covariate rising or falling at t*,
+ * how fast, and how sure is the model.  The derivative of a GP is a GP, and the SE / SM / LMC-SM covariances are differentiable
+ * in closed form.
+ *   ref: core/gp_regression.cpp:128-214 (GP_Regression::predict), kernel/c_kernel_LMC_SM.cpp:329-372 (cross Gram)
+ * The reference has no such output; the definition is the fp64 / long-double restatement of tests/trend_ref.py.
+ * Component q is k_q(tau) = cos(w_q tau) exp(-c_q tau^2), w_q = 2 pi mu_q, c_q = 2 (pi v_q)^2 (SE: w = 0, c = 1 / (2 l^2),
+ * B = sf^2).  For a test point (m*, t*) and a training observation (m_i, t_i), tau = t* - t_i:
+ *   K*'[i]  = sum_q B_q[m_i, m*] (-w_q sin(w_q tau) - 2 c_q tau cos(w_q tau)) exp(-c_q tau^2)     (d/dt* of the cross Gram)
+ *   k''**   = sum_q B_q[m*, m*] (w_q^2 + 2 c_q)                                                   (prior variance of f')
+ *   V = L^-1 K*,  V' = L^-1 K*',  z = L^-1 y
+ *   dmean[j] = V'^T z            posterior mean of f'_{m*}(t*), per hour, in the units of y
+ *   dvar[j]  = k''** - sum V'^2   posterior variance of the LATENT slope (a noisy observation has no derivative: no sigma^2)
+ *   cross[j] = - sum V V'         posterior cov(f(t*), f'(t*)); the prior term k'(0) is exactly 0.  May be NULL.
+ *   mean[j], var[j]              exactly those of medgp_posterior_batch(parts = NULL) on the same call, bit for bit (var carries
+ *                                sigma^2_{m*} once)
+ * nbatch, slots, theta, offsets, meta2, t2, mean, var and status mean exactly what they mean for medgp_posterior_batch: one
+ * factorisation per patient, no n > 2 guard, status[b] = jitter rounds or -1, meta2 may be NULL for SE / SM, an empty range of
+ * points is allowed.  dmean and dvar are required (NULL: MEDGP_ERR_ARG before any device work).  The points of a patient with
+ * status[b] < 0 get NaN in all five outputs.  After k jitter rounds every quantity is that of the matrix that was factored,
+ * K + k diag(sigma^2) (the rule of the posterior, LOO and forecast calls).
+ * Supported range of the time stamps: |t| <= 2^14 h, of the training observations (medgp_set_patient) AND of the test points: the
+ * slope is formed from the same cos / sin (w t_i) tables as the value, sin(w (t_i - t*)) = sn_i cos(w t*) - cs_i sin(w t*).
+ * A point's five outputs depend on the patient, theta and the point alone: not on the other points of the call, their order, the
+ * tile or column a point lands in, the launch chunk, or -- with the route pinned -- the batch-mates.
+ * The points go in tiles of 32 per workgroup: the 64 columns of the forward solve on fp64 MFMA are the value and the slope
+ * column of every point (kernels_trend.h).  Work memory per launch within MEDGP_POSTERIOR_BUDGET_GB; a call whose per-entry
+ * matrices exceed the memory budget fails with MEDGP_ERR_CAPACITY, like medgp_posterior_batch.
+ * Accuracy: tests/test_trend_gpu.py holds all five outputs to the project's bar of 2 fp32 ulps of max(|ref|, 1e-3 S).
+ * All pointers are HOST memory. */
+int medgp_trend_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                      const int32_t *meta2, const float *t2, float *mean, float *var,
+                      float *dmean, float *dvar, float *cross, int32_t *status);
 
 /* Cohort statistics, the step after training: for each of nseries independent sample series
  * (series s = data[off[s] .. off[s] + cnt[s])) the Gaussian kernel density estimate with Silverman's bandwidth evaluated AT the

@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_trend_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at",
 ]
 
@@ -97,6 +97,7 @@ def load():
     lib.medgp_loo_batch.argtypes = [vp, C.c_int, i32p, dp, i32p, i32p, fp, fp, dp, dp, i32p, i32p]
     lib.medgp_loo_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, i32p]
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
+    lib.medgp_trend_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, fp, fp, i32p]
     lib.medgp_synchronize.argtypes = [vp]
     lib.medgp_profile_enable.argtypes = [vp, C.c_int]
     lib.medgp_profile_num_kernels.restype = C.c_int
@@ -471,6 +472,31 @@ class Context:
         for b in range(nb):
             a, e = int(offsets[b]), int(offsets[b + 1])
             out.append((mean[a:e].copy(), var[a:e].copy(), lpd[a:e].copy() if lpd is not None else None))
+        return out, st
+
+    def trend(self, slots, theta, meta2_list, t2_list, cross=True):
+        """medgp_trend_batch: the posterior of the latent slope f'(t*) at every test point, next to the posterior of the value.
+        Arguments as posterior().  Returns ([(mean[m], var[m], dmean[m], dvar[m], cross[m] or None) per patient], status): mean /
+        var are posterior(parts=False)'s, bit for bit; dmean is the slope per hour in the units of y, dvar the variance of the
+        LATENT slope (no noise term), cross = cov(f(t*), f'(t*)).  medgp_amd.trend turns them into P(rising) and rate intervals."""
+        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
+        nb = slots.shape[0]
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([x.shape[0] for x in ts])
+        M = int(offsets[-1])
+        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
+        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+        mean, var, dmean, dvar = (np.empty(max(M, 1), dtype=np.float32) for _ in range(4))
+        cr = np.empty(max(M, 1), dtype=np.float32) if cross else None
+        st = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_trend_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
+                                              offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
+                                              _ptr(mean, C.c_float), _ptr(var, C.c_float), _ptr(dmean, C.c_float), _ptr(dvar, C.c_float),
+                                              _ptr(cr, C.c_float), _ptr(st, C.c_int32)))
+        out = []
+        for b in range(nb):
+            a, e = int(offsets[b]), int(offsets[b + 1])
+            out.append((mean[a:e].copy(), var[a:e].copy(), dmean[a:e].copy(), dvar[a:e].copy(), cr[a:e].copy() if cross else None))
         return out, st
 
     def posterior_joint(self, slots, theta, meta2_list, t2_list, eps_list=None, cov=True):

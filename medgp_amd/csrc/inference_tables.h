@@ -18,6 +18,7 @@
 #endif
 
 #define POST_TW 64    // test points per tile (one workgroup)
+#define TREND_TW 32   // test points per tile of k_trend: the tile's 64 columns hold the value and the slope column of each point
 
 // one workgroup of k_posterior: entry e of the class view, test points [p0, p0 + cnt) of the call (cnt <= POST_TW)
 struct PostTile { int e, p0, cnt, pad; };
@@ -69,11 +70,11 @@ struct PointTables {
     size_t work_need = 0;   // bytes of work rows of the largest chunk
 };
 
-// the tiles of points [p0, p1) of entry e; prefix (the points' prefixes, sorted ascending inside the patient) fills pmax
+// the tiles of points [p0, p1) of entry e, tw points each; prefix (the points' prefixes, sorted ascending inside the patient) fills pmax
 template <class Tile>
-inline void push_point_tiles(std::vector<Tile> &tiles, int e, int64_t p0, int64_t p1, const int *prefix) {
-    for (int64_t p = p0; p < p1; p += POST_TW) {
-        const int cnt = (int)std::min<int64_t>(POST_TW, p1 - p);
+inline void push_point_tiles(std::vector<Tile> &tiles, int e, int64_t p0, int64_t p1, const int *prefix, int tw = POST_TW) {
+    for (int64_t p = p0; p < p1; p += tw) {
+        const int cnt = (int)std::min<int64_t>(tw, p1 - p);
         tiles.push_back({e, (int)p, cnt, prefix ? prefix[p + cnt - 1] : 0});   // (sorted: the tile's last point has its largest prefix)
     }
 }
@@ -82,12 +83,12 @@ inline void push_point_tiles(std::vector<Tile> &tiles, int e, int64_t p0, int64_
 // hence the work-row stride ld * 64 + extra doubles) and chunks of consecutive tiles of one class whose work rows stay within the budget
 template <class Tile>
 inline void build_point_tiles(const std::vector<TableClass> &cls, const int *order, const int64_t *offsets, const int *prefix,
-                              size_t extra, size_t budget, PointTables<Tile> &T) {
+                              size_t extra, size_t budget, PointTables<Tile> &T, int tw = POST_TW) {
     for (size_t ci = 0; ci < cls.size(); ci++) {
         const TableClass &k = cls[ci];
         const int t_begin = (int)T.tiles.size();
         const size_t stride = (size_t)k.ld * 64 + extra;
-        for (int i = k.b0; i < k.b0 + k.count; i++) push_point_tiles(T.tiles, i - k.b0, offsets[order[i]], offsets[order[i] + 1], prefix);
+        for (int i = k.b0; i < k.b0 + k.count; i++) push_point_tiles(T.tiles, i - k.b0, offsets[order[i]], offsets[order[i] + 1], prefix, tw);
         const int per_chunk = (int)std::max<size_t>(1, budget / (stride * sizeof(double)));
         for (int t0 = t_begin; t0 < (int)T.tiles.size(); t0 += per_chunk) {
             const int nt = std::min(per_chunk, (int)T.tiles.size() - t0);
@@ -95,6 +96,13 @@ inline void build_point_tiles(const std::vector<TableClass> &cls, const int *ord
             T.work_need = std::max(T.work_need, (size_t)nt * stride * sizeof(double));
         }
     }
+}
+
+// medgp_trend_batch: the posterior call's tables with TREND_TW points per tile.  A tile's work rows are still ld x 64 doubles: its 64
+// columns are the value and the slope columns of its points (kernels_trend.h).
+inline void build_trend_tiles(const std::vector<TableClass> &cls, const int *order, const int64_t *offsets, size_t budget,
+                              PointTables<PostTile> &T) {
+    build_point_tiles(cls, order, offsets, nullptr, 0, budget, T, TREND_TW);
 }
 
 struct JointTables : PointTables<PostTile> {

@@ -14,6 +14,7 @@
 #include "kernels_posterior.h"
 #include "kernels_posterior_joint.h"
 #include "kernels_forecast.h"
+#include "kernels_trend.h"
 #include "kernels_loo.h"
 #include "kernels_loo_grad.h"
 
@@ -30,8 +31,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_FORECAST, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_forecast"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -102,10 +103,11 @@ struct Arena {
 //   one tile needs more; medgp_fit_predict*: the k* rows); the forecast's prefix and y2; lpd (forecast: per point, LOO: per group);
 //   joint posterior: the patient / tile-pair / row-block tables of the call, C and the float covariance blocks of one launch chunk, the
 //   call's eps and samples, cov_status -- LOO: its group / tile-pair / job tables, the blocks of one launch chunk, group_status;
-//   LOO: the singleton table and the index lists; BUF_GVEC: the per-entry vectors [u | s | v | log p] of medgp_loo_grad
+//   LOO: the singleton table and the index lists; BUF_GVEC: the per-entry vectors [u | s | v | log p] of medgp_loo_grad;
+//   BUF_SLOPE: the per-point outputs [dmean | dvar | cross] of medgp_trend_batch
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -1069,7 +1071,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 8; }
+int medgp_abi_version(void) { return 9; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2203,7 +2205,60 @@ int forecast_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *
     }
     return MEDGP_OK;
 }
+
+// medgp_trend_batch (kernels_trend.h): the posterior call's pipeline run, then k_trend over tiles of TREND_TW points whose 64 columns
+// carry the value and the slope column of every point through the same panel loop.  Launch chunks within the posterior budget.
+int trend_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets, const int32_t *meta2,
+               const float *t2, float *mean, float *var, float *dmean, float *dvar, float *cross, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
+    if (!dmean || !dvar) return fail(c, MEDGP_ERR_ARG, "dmean / dvar is NULL");
+    int max_n = 0, rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    if ((rc = check_points(c, nbatch, offsets, meta2, t2, mean, var))) return rc;
+    const int64_t M = offsets[nbatch];
+    const size_t Mz = (size_t)std::max<int64_t>(M, 1);
+    std::vector<double> ht2;
+    std::vector<int> hm2;
+    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the five outputs are invariant under a permutation of the training observations: the grouped copy serves, as for the posterior
+    if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
+    PointTables<PostTile> T;
+    build_trend_tiles(table_classes(c->plan), c->plan.order.data(), offsets, c->posterior_budget, T);
+    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if ((rc = buf_ensure(c, BUF_SLOPE, 3 * Mz * sizeof(float)))) return rc;
+    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
+    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
+    // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
+    if ((rc = factor_run(c, nbatch, max_n, theta, false, true))) return rc;
+    float *d_dmean = buf<float>(c, BUF_SLOPE), *d_dvar = d_dmean + Mz, *d_cross = d_dvar + Mz;
+    for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
+        Launcher l(c, KID_TREND);
+        const MedgpDev V = class_view(c, c->plan, c->plan.cls[ch.cls]);
+        with_q8(V.Q, [&](auto q) {   // Q > 8: generic component loop
+            hipLaunchKernelGGL(k_trend<decltype(q)::value>, dim3(ch.nt), dim3(256), 0, c->stream, V, buf<PostTile>(c, BUF_TILES) + ch.t0, buf<int>(c, BUF_META2),
+                               buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK), ch.stride, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), d_dmean, d_dvar,
+                               cross ? d_cross : nullptr);
+        });
+    }
+    HIPCHK(c, hipGetLastError());
+    if (M > 0) {
+        HIPCHK(c, hipMemcpyAsync(mean, buf<float>(c, BUF_MEAN), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(var, buf<float>(c, BUF_VAR), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dmean, d_dmean, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dvar, d_dvar, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        if (cross) HIPCHK(c, hipMemcpyAsync(cross, d_cross, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+    }
+    return read_status(c, nbatch, status);
+}
 }  // namespace
+
+int medgp_trend_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                      const int32_t *meta2, const float *t2, float *mean, float *var, float *dmean, float *dvar, float *cross,
+                      int32_t *status) {
+    return trend_impl(c, nbatch, slots, theta, offsets, meta2, t2, mean, var, dmean, dvar, cross, status);
+}
 
 int medgp_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
                           const int32_t *meta2, const float *t2, float *mean, float *var, float *parts, int32_t *status) {
