@@ -17,6 +17,10 @@
 //            flushed at each change and reduced over the column segments in a FIXED order -> bitwise
 //            reproducible; every (16-row piece of d) x (column tile piece of e) owns one slab entry, written
 //            exactly once (no atomics).  k_epilogue adds the pieces in fixed order.
+// The pieces (wg_tile_of, the macro WG_PROLOGUE, wg_phase1, wg_phase2, wg_phase3) are defined once and shared with the LOO kernels of
+// kernels_loo_grad.h, which differ by a phase-1 hook and by the tile element alone.  Against the form with the pieces written out in
+// its body no instantiation of k_wgrad needs more registers, scratch or LDS, and the counts of MFMA, memory and fp64 instructions are
+// the same, but the schedule is not: another instruction stream.  What was measured: profiles/wgrad_shared_resources.txt.
 #pragma once
 #include "medgp_dev.h"
 #include "kernels_assemble.h"
@@ -26,6 +30,69 @@
 #ifndef WG_MINWAVES
 #define WG_MINWAVES 3
 #endif
+// staging buffers Bs[2][64][WG_KC + 2] (phase 1) and the W tile Ws[64][66] (phases 2 and 3; 4224 <= 4352 doubles) share storage
+#define WG_SMEM_DOUBLES (2 * 64 * (WG_KC + 2))
+
+// what a workgroup knows about its tile: entry b (patient slot `slot`, n observations, npad = n rounded up to 64-blocks), tile (I, J), I >= J
+struct WgTile { int b, slot, n, ld, npad, I, J, tid, lane, li, g, w; };
+
+// 1-D grid of 8 * ceil(nbatch / 8) * ntiles workgroups, dealt round-robin over the 8 XCDs by the hardware.
+// id -> (patient, tile) keeps a patient on ONE XCD (its U rows are re-read by every tile: they must share an L2) and
+// makes the tiles of a patient consecutive in dispatch order, so that an XCD works on about three patients at a time
+// (3 x 1.2 MB of U fits its 4 MB L2).  Patient-major over the whole batch instead (all patients' tile 0, then tile
+// 1, ...) cycles 64 patients x 1.2 MB through each L2 between two tiles of the same patient: every tile re-read U
+// from HBM (PMC: 3.6 GB fetched per launch for 0.6 GB of U).
+// With fewer than 64 patients that would leave XCDs idle (one patient = one XCD): spread instead, patient index
+// fastest (tiles of a patient then land on XCD b % 8 only when nbatch is a multiple of 8, which no longer matters).
+// nbp (launches of fewer than 64 entries): stride of the entry index in the workgroup id, nbatch or nbatch | 1.  Workgroup ids go round-robin
+// over the 8 XCDs, so with the entry index fastest entry b's tiles land on 8 / gcd(stride, 8) ... of them: harmless when all entries are
+// equally large (every XCD gets the same work: 4 x N = 2048 0.062 ms per entry, 5 x 0.062), but in a RAGGED class of 2, 4 or 8 entries
+// the largest entry's tiles -- most of the work -- queue on half, a quarter, an eighth of the chip (round 5, scratch/wgrad_ragged.py:
+// N = 3595 + 3 x 2400: 1.18 ms, + 4 x 2400: 0.73 ms).  An odd stride puts every entry on all XCDs; the ids of the padding entry exit.
+// SERP: a launch of at most 1024 workgroups (all resident at once) deals its tiles in serpentine order (see k_wgrad).
+template <bool SERP>
+__device__ __forceinline__ bool wg_tile_of(int nbatch, int ntiles, int nbp, int &b, int &tix) {
+    if (nbatch >= 64) {
+        const int xcd = blockIdx.x & 7, rest = blockIdx.x >> 3;
+        b = (rest / ntiles) * 8 + xcd;
+        tix = rest % ntiles;
+    } else {
+        int x = blockIdx.x;
+        const int total = nbp * ntiles;
+        if (x >= total) return false;
+        if (SERP && total <= 1024 && ((x >> 8) & 1)) {   // odd group of 256: reversed
+            const int v0 = x & ~255, m = min(256, total - v0);
+            x = v0 + (m - 1 - (x & 255));
+        }
+        b = x % nbp;
+        tix = x / nbp;
+    }
+    return b < nbatch;
+}
+
+// The prologue of a kernel with the arguments (MedgpDev L, ..., int nbatch, int ntiles, int nbp): leaves `const WgTile T`, or returns when
+// there is nothing to do (a padding id, a failed entry, a tile beyond the entry's own blocks).  A macro so that these are returns of the kernel.
+#define WG_PROLOGUE(SERP) \
+    int b_, tix_; \
+    if (!wg_tile_of<(SERP)>(nbatch, ntiles, nbp, b_, tix_)) return; \
+    if (L.status[b_] < 0) return; \
+    const int slot_ = __builtin_amdgcn_readfirstlane(L.bslot[b_]); \
+    const int n_ = __builtin_amdgcn_readfirstlane(L.pn[slot_]); \
+    const int npad_ = medgp_roundup(n_, 64); \
+    int I_, J_; \
+    tile_decode(tix_, I_, J_); \
+    if (I_ >= npad_ / 64) return; \
+    const int tid_ = threadIdx.x, lane_ = tid_ & 63; \
+    const WgTile T{b_, slot_, n_, L.ldn, npad_, I_, J_, tid_, lane_, lane_ & 15, lane_ >> 4, __builtin_amdgcn_readfirstlane(tid_ >> 6)}
+
+// Phase-1 hooks: applied to a fragment (two adjacent doubles at column `col` of row `row` of M, in chunk c of the k range) between its
+// load and its use.  staged: the J rows on their way into LDS; streamed: the I rows.  Values go in and out by value: a local array handed
+// to a function by reference is kept as ONE wide vector by the compiler (k_wgrad<5, 0, 1>: 168 VGPRs and 212 bytes of scratch against 120 / 0).
+struct WgNoHook {
+    __device__ __forceinline__ v2d staged(v2d x, int, int, int) const { return x; }
+    __device__ __forceinline__ v2d streamed(v2d x, int, int, int) const { return x; }
+};
+struct WgAcc { v4d a[4]; };   // a[ct]: rows 16w.. of block I, cols 16ct.. of block J
 
 // one chunk of the MFMA block of phase 1: rows 16w.. (A fragment ac, streamed) x the four column tiles of the staged J rows
 #define WG_CHUNK_MFMA(ac, buf) \
@@ -36,158 +103,77 @@
             _Pragma("unroll") for (int s = 0; s < 2; s++) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[h][s], bf[s], acc[ct], 0, 0, 0); \
         }
 
-// QT = mixture components this launch reduces, Q0 = index of the first one (Q <= 8: one launch <Q, 0>; 8 < Q <= 16: <8, 0> and
-// <Q - 8, 8>, each forming the W tile again -- N^3/3 more MFMA work for a route no BASELINE config takes).
-// PF = chunks the phase-1 loop prefetches ahead.  PF = 2 for launches of few large patients (the chip is filled less than four times): a
-// workgroup then shares its SIMDs with at most a few others and little hides the latency of its operand stream; measured k_wgrad 0.123 ->
-// 0.108 ms (1 x N = 2048), 0.072 -> 0.064 ms (4 x N = 1024), 0.449 -> 0.437 ms (1 x N = 4096), neutral on full launches (which keep PF = 1,
-// the round-3 code path); four chunks ahead and a branch-free MFMA block for the off-diagonal tiles were both slower (DESIGN_LOG A.7).  Such a
-// launch of at most 1024 workgroups (all resident at once, so placement is static: workgroups x, x + 256, x + 512 share a CU -- traced) also
-// deals its tiles in serpentine order, so that the CU holding the longest k range gets the shortest one next.  Scheduling only: same MFMA
-// sequence per tile, same bits.
-// nbp (launches of fewer than 64 entries): stride of the entry index in the workgroup id, nbatch or nbatch | 1.  Workgroup ids go round-robin
-// over the 8 XCDs, so with the entry index fastest entry b's tiles land on 8 / gcd(stride, 8) ... of them: harmless when all entries are
-// equally large (every XCD gets the same work: 4 x N = 2048 0.062 ms per entry, 5 x 0.062), but in a RAGGED class of 2, 4 or 8 entries
-// the largest entry's tiles -- most of the work -- queue on half, a quarter, an eighth of the chip (round 5, scratch/wgrad_ragged.py:
-// N = 3595 + 3 x 2400: 1.18 ms, + 4 x 2400: 0.73 ms).  An odd stride puts every entry on all XCDs; the ids of the padding entry exit.
-template <int QT, int Q0 = 0, int PF = 1>
-__global__ void __launch_bounds__(WG_THREADS, WG_MINWAVES) k_wgrad(MedgpDev L, int nbatch, int ntiles, int nbp) {
-    // staging buffers (phase 1) and the W tile (phase 2/3) share storage
-    __shared__ __attribute__((aligned(16))) double smem[2 * 64 * (WG_KC + 2)];
-    typedef double (*BsT)[64][WG_KC + 2];
-    BsT Bs = (BsT)smem;                       // Bs[2][64][34]
-    double (*Ws)[66] = (double (*)[66])smem;   // Ws[64][66]  (4224 <= 4352 doubles)
-    __shared__ __attribute__((aligned(16))) double rowc[4][16][2 + 2 * QT];   // row constants of each wave's 16 rows
-
-    // 1-D grid of 8 * ceil(nbatch / 8) * ntiles workgroups, dealt round-robin over the 8 XCDs by the hardware.
-    // id -> (patient, tile) keeps a patient on ONE XCD (its U rows are re-read by every tile: they must share an L2) and
-    // makes the tiles of a patient consecutive in dispatch order, so that an XCD works on about three patients at a time
-    // (3 x 1.2 MB of U fits its 4 MB L2).  Patient-major over the whole batch instead (all patients' tile 0, then tile
-    // 1, ...) cycles 64 patients x 1.2 MB through each L2 between two tiles of the same patient: every tile re-read U
-    // from HBM (PMC: 3.6 GB fetched per launch for 0.6 GB of U).
-    // With fewer than 64 patients that would leave XCDs idle (one patient = one XCD): spread instead, patient index
-    // fastest (tiles of a patient then land on XCD b % 8 only when nbatch is a multiple of 8, which no longer matters).
-    int b, tix;
-    if (nbatch >= 64) {
-        const int xcd = blockIdx.x & 7, rest = blockIdx.x >> 3;
-        b = (rest / ntiles) * 8 + xcd;
-        tix = rest % ntiles;
-    } else {
-        int x = blockIdx.x;
-        const int total = nbp * ntiles;
-        if (x >= total) return;
-        if (PF > 1 && total <= 1024 && ((x >> 8) & 1)) {   // odd group of 256: reversed
-            const int v0 = x & ~255, m = min(256, total - v0);
-            x = v0 + (m - 1 - (x & 255));
-        }
-        b = x % nbp;
-        tix = x / nbp;
-    }
-    if (b >= nbatch) return;
-    if (L.status[b] < 0) return;
-    const int slot = __builtin_amdgcn_readfirstlane(L.bslot[b]);
-    const int n = __builtin_amdgcn_readfirstlane(L.pn[slot]);
-    const int ld = L.ldn, npad = medgp_roundup(n, 64), nb = npad / 64;
-    int I, J;
-    tile_decode(tix, I, J);
-    if (I >= nb) return;
-    const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const double *U = L.Linv + (size_t)b * ld * ld;
-
-#ifdef MEDGP_STAMPS
-    unsigned long long wst[4] = {0, 0, 0, 0}, wlast;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wlast)::"memory");
-#define WSTAMP(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); wst[k] += t_ - wlast; wlast = t_; } while (0)
-#else
-#define WSTAMP(k) do {} while (0)
-#endif
-    // ---------------- phase 1: acc[ct] (rows 16w.. of block I, cols 16ct.. of block J)
+// Phase 1: the tile  sum over the columns k >= k0 of M[I rows][k] M[J rows][k], one chunk of WG_KC columns prefetched ahead.
+template <class Hook>
+__device__ __forceinline__ WgAcc wg_phase1(double *smem, const WgTile T, const double *M, int k0, const Hook hk) {
+    double (*Bs)[64][WG_KC + 2] = (double (*)[64][WG_KC + 2])smem;   // Bs[2][64][34]
     v4d acc[4];
 #pragma unroll
     for (int ct = 0; ct < 4; ct++) acc[ct] = (v4d){0.0, 0.0, 0.0, 0.0};
-    {
-        const int k0 = 64 * I, nch = (npad - k0) / WG_KC;
-        const int ctmax = (I == J) ? w : 3;   // wave-uniform
-        const double *Arow = U + (size_t)(64 * I + 16 * w + li) * ld + k0 + 2 * g;
-        const int srow = tid >> 2, scg = (tid & 3) * 8;
-        const double *Bsrc = U + (size_t)(64 * J + srow) * ld + k0 + scg;
-        if constexpr (PF == 1) {
-            v2d bst[4], an[4];
+    const int nch = (T.npad - k0) / WG_KC;
+    const int ctmax = (T.I == T.J) ? T.w : 3;   // wave-uniform
+    const int li = T.li, g = T.g;
+    const int srow = T.tid >> 2, scg = (T.tid & 3) * 8;
+    const int arow = 64 * T.I + 16 * T.w + li, brow = 64 * T.J + srow;
+    const double *Arow = M + (size_t)arow * T.ld + k0 + 2 * g;
+    const double *Bsrc = M + (size_t)brow * T.ld + k0 + scg;
+    v2d bst[4], an[4];
 #pragma unroll
-            for (int u = 0; u < 4; u++) bst[u] = *(const v2d *)(Bsrc + 2 * u);
+    for (int u = 0; u < 4; u++) bst[u] = hk.staged(*(const v2d *)(Bsrc + 2 * u), 0, brow, k0 + scg + 2 * u);
 #pragma unroll
-            for (int h = 0; h < 4; h++) an[h] = *(const v2d *)(Arow + 8 * h);
+    for (int h = 0; h < 4; h++) an[h] = hk.streamed(*(const v2d *)(Arow + 8 * h), 0, arow, k0 + 2 * g + 8 * h);
 #pragma unroll
-            for (int u = 0; u < 4; u++) *(v2d *)&Bs[0][srow][scg + 2 * u] = bst[u];
-            __syncthreads();
-            for (int c = 0; c < nch; c++) {
-                const int buf = c & 1;
-                v2d ac[4];
+    for (int u = 0; u < 4; u++) *(v2d *)&Bs[0][srow][scg + 2 * u] = bst[u];
+    __syncthreads();
+    for (int c = 0; c < nch; c++) {
+        const int buf = c & 1;
+        v2d ac[4];
 #pragma unroll
-                for (int h = 0; h < 4; h++) ac[h] = an[h];
-                if (c + 1 < nch) {
+        for (int h = 0; h < 4; h++) ac[h] = an[h];
+        if (c + 1 < nch) {
+            const int kc = (c + 1) * WG_KC;
 #pragma unroll
-                    for (int u = 0; u < 4; u++) bst[u] = *(const v2d *)(Bsrc + (c + 1) * WG_KC + 2 * u);
+            for (int u = 0; u < 4; u++) bst[u] = hk.staged(*(const v2d *)(Bsrc + kc + 2 * u), c + 1, brow, k0 + kc + scg + 2 * u);
 #pragma unroll
-                    for (int h = 0; h < 4; h++) an[h] = *(const v2d *)(Arow + (c + 1) * WG_KC + 8 * h);
-                }
-                WG_CHUNK_MFMA(ac, buf);
-                if (c + 1 < nch) {
-#pragma unroll
-                    for (int u = 0; u < 4; u++) *(v2d *)&Bs[buf ^ 1][srow][scg + 2 * u] = bst[u];
-                }
-                __syncthreads();
-            }
-        } else {
-            // PF register sets, set s carries the chunks c = s (mod PF): a set is refilled (chunk c + PF) as soon as its A fragment has been
-            // copied out; its staged J rows go to LDS one iteration before they are used (the LDS stays double buffered)
-            v2d bst[PF][4], an[PF][4];
-#pragma unroll
-            for (int st = 0; st < PF; st++)
-                if (st < nch) {
-#pragma unroll
-                    for (int u = 0; u < 4; u++) bst[st][u] = *(const v2d *)(Bsrc + st * WG_KC + 2 * u);
-#pragma unroll
-                    for (int h = 0; h < 4; h++) an[st][h] = *(const v2d *)(Arow + st * WG_KC + 8 * h);
-                }
-#pragma unroll
-            for (int u = 0; u < 4; u++) *(v2d *)&Bs[0][srow][scg + 2 * u] = bst[0][u];
-            __syncthreads();
-            for (int c0 = 0; c0 < nch; c0 += PF) {
-#pragma unroll
-                for (int st = 0; st < PF; st++) {
-                    const int c = c0 + st;
-                    if (c >= nch) break;
-                    v2d ac[4];
-#pragma unroll
-                    for (int h = 0; h < 4; h++) ac[h] = an[st][h];
-                    if (c + PF < nch) {
-#pragma unroll
-                        for (int u = 0; u < 4; u++) bst[st][u] = *(const v2d *)(Bsrc + (c + PF) * WG_KC + 2 * u);
-#pragma unroll
-                        for (int h = 0; h < 4; h++) an[st][h] = *(const v2d *)(Arow + (c + PF) * WG_KC + 8 * h);
-                    }
-                    WG_CHUNK_MFMA(ac, (st & 1));
-                    if (c + 1 < nch) {
-#pragma unroll
-                        for (int u = 0; u < 4; u++) *(v2d *)&Bs[(st + 1) & 1][srow][scg + 2 * u] = bst[(st + 1) % PF][u];
-                    }
-                    __syncthreads();
-                }
-            }
+            for (int h = 0; h < 4; h++) an[h] = hk.streamed(*(const v2d *)(Arow + kc + 8 * h), c + 1, arow, k0 + kc + 2 * g + 8 * h);
         }
+        WG_CHUNK_MFMA(ac, buf);
+        if (c + 1 < nch) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) *(v2d *)&Bs[buf ^ 1][srow][scg + 2 * u] = bst[u];
+        }
+        __syncthreads();
     }
-    WSTAMP(0);
-    // ---------------- phase 2: W tile -> LDS (all waves are past the last staging read: barrier above)
+    return WgAcc{{acc[0], acc[1], acc[2], acc[3]}};
+}
+
+// Phase 2: tile -> LDS (all waves are past the last staging read: the barrier that ends phase 1)
+__device__ __forceinline__ void wg_phase2(const WgAcc acc, double *smem, const WgTile T) {
+    double (*Ws)[66] = (double (*)[66])smem;   // Ws[64][66]
 #pragma unroll
     for (int ct = 0; ct < 4; ct++)
 #pragma unroll
-        for (int r = 0; r < 4; r++) Ws[16 * w + 4 * r + g][16 * ct + li] = acc[ct][r];
+        for (int r = 0; r < 4; r++) Ws[16 * T.w + 4 * r + T.g][16 * ct + T.li] = acc.a[ct][r];
     __syncthreads();
+}
 
-    WSTAMP(1);
-    // ---------------- phase 3
+// Phase-3 element policies: the tile element from the accumulated Ws_ij, alpha_i, alpha_j and NX (0 or 1) further constants of the
+// row and of the column, which extra(k) loads for observation k (NX = 0: no load).  The nlml gradient: W_ij = (K^-1)_ij - alpha_i alpha_j.
+struct WgElemNlml {
+    static constexpr int NX = 0;
+    __device__ __forceinline__ double extra(int) const { return 0.0; }
+    __device__ __forceinline__ double elem(double ws, double ai, double aj, double, double) const { return ws - ai * aj; }
+};
+// a row of rowc: t, alpha, [extra, -,] (cos, sin) x QT
+template <class Elem, int QT> constexpr int wg_rowc_stride = 2 + 2 * Elem::NX + 2 * QT;
+
+// Phase 3 on the tile in Ws; rowc: [4][16][wg_rowc_stride] doubles of LDS, the row constants of each wave's 16 rows.
+// QT = mixture components this launch reduces, Q0 = index of the first one.
+template <int QT, int Q0, class Elem>
+__device__ __forceinline__ void wg_phase3(const MedgpDev &L, const WgTile T, const double *smem, double (*rowc)[16][wg_rowc_stride<Elem, QT>], const Elem el) {
+    constexpr int NX = Elem::NX, RC = 2 + 2 * NX;   // RC: where the (cos, sin) pairs of a rowc row start
+    const double (*Ws)[66] = (const double (*)[66])smem;
+    const int b = T.b, slot = T.slot, n = T.n, ld = T.ld, I = T.I, J = T.J, lane = T.lane, w = T.w;
     const double *hyp = L.hyp + (size_t)b * L.hyp_stride;
     const double *t = L.pt + (size_t)slot * L.pld;
     const int *meta = L.pmeta + (size_t)slot * L.pld;
@@ -209,6 +195,7 @@ __global__ void __launch_bounds__(WG_THREADS, WG_MINWAVES) k_wgrad(MedgpDev L, i
     const int j = 64 * J + lane;
     const bool jv = j < n;
     const double tj = t[j], aj = alpha[j];
+    const double xj = el.extra(j);
     const int mj = jv ? meta[j] : -1;
     double csj[QT], snj[QT];
 #pragma unroll
@@ -237,6 +224,7 @@ __global__ void __launch_bounds__(WG_THREADS, WG_MINWAVES) k_wgrad(MedgpDev L, i
     // dependent scalar loads per row iteration
     const int irow = 64 * I + 16 * w + (lane & 15);
     const double r_t = t[irow], r_a = alpha[irow];
+    const double r_x = el.extra(irow);
     const int r_m = (irow < n) ? meta[irow] : -1;
     double r_cs[QT], r_sn[QT];
 #pragma unroll
@@ -245,8 +233,9 @@ __global__ void __launch_bounds__(WG_THREADS, WG_MINWAVES) k_wgrad(MedgpDev L, i
     // v_readlane per double cost 2 + 4Q VALU per row (measured: k_wgrad 1.12 -> 1.07 ms, and 17 VGPRs fewer)
     if (lane < 16) {
         rowc[w][lane][0] = r_t; rowc[w][lane][1] = r_a;
+        if constexpr (NX) { rowc[w][lane][2] = r_x; rowc[w][lane][3] = 0.0; }
 #pragma unroll
-        for (int q = 0; q < QT; q++) { rowc[w][lane][2 + 2 * q] = r_cs[q]; rowc[w][lane][3 + 2 * q] = r_sn[q]; }
+        for (int q = 0; q < QT; q++) { rowc[w][lane][RC + 2 * q] = r_cs[q]; rowc[w][lane][RC + 1 + 2 * q] = r_sn[q]; }
     }
     __builtin_amdgcn_wave_barrier();
     for (int rr = 0; rr <= 16; rr++) {
@@ -285,8 +274,9 @@ __global__ void __launch_bounds__(WG_THREADS, WG_MINWAVES) k_wgrad(MedgpDev L, i
         if (rr == 16 || mi < 0) continue;
         const v2d ta = *(const v2d *)&rowc[w][rr][0];
         const double ti = ta[0], ai = ta[1];
-        double wv = Ws[16 * w + rr][lane] - ai * aj;
-        if (I == J && j == i) L.wdiag[(size_t)b * ld + i] = wv;   // noise gradient needs diag(W)
+        const double xi = NX ? rowc[w][rr][2] : 0.0;
+        double wv = el.elem(Ws[16 * w + rr][lane], ai, aj, xi, xj);
+        if (I == J && j == i) L.wdiag[(size_t)b * ld + i] = wv;   // noise gradient needs the diagonal of the tile matrix
         const bool valid = jv && (j <= i);
         wv = valid ? ((mi == mj && j < i) ? 2.0 * wv : wv) : 0.0;
         const double dt = ti - tj, dd = dt * dt;
@@ -294,7 +284,7 @@ __global__ void __launch_bounds__(WG_THREADS, WG_MINWAVES) k_wgrad(MedgpDev L, i
         // (-w_q, -2 c_q) are applied once per flush -- 3 VALU less per (pair, component)
 #pragma unroll
         for (int q = 0; q < QT; q++) {
-            const v2d csn = *(const v2d *)&rowc[w][rr][2 + 2 * q];
+            const v2d csn = *(const v2d *)&rowc[w][rr][RC + 2 * q];
             const double ci = csn[0], si = csn[1];
             const double we = wv * exp2_nonpos(cq2n[q] * dd);
             const double cd = ci * csj[q] + si * snj[q];
@@ -305,10 +295,88 @@ __global__ void __launch_bounds__(WG_THREADS, WG_MINWAVES) k_wgrad(MedgpDev L, i
             sV[q] += p * dd;
         }
     }
+}
+
+// QT = mixture components this launch reduces, Q0 = index of the first one (Q <= 8: one launch <Q, 0>; 8 < Q <= 16: <8, 0> and
+// <Q - 8, 8>, each forming the W tile again -- N^3/3 more MFMA work for a route no BASELINE config takes).
+// PF = chunks the phase-1 loop prefetches ahead.  PF = 2 for launches of few large patients (the chip is filled less than four times): a
+// workgroup then shares its SIMDs with at most a few others and little hides the latency of its operand stream; measured k_wgrad 0.123 ->
+// 0.108 ms (1 x N = 2048), 0.072 -> 0.064 ms (4 x N = 1024), 0.449 -> 0.437 ms (1 x N = 4096), neutral on full launches (which keep PF = 1,
+// the round-3 code path); four chunks ahead and a branch-free MFMA block for the off-diagonal tiles were both slower (DESIGN_LOG A.7).  Such a
+// launch of at most 1024 workgroups (all resident at once, so placement is static: workgroups x, x + 256, x + 512 share a CU -- traced) also
+// deals its tiles in serpentine order, so that the CU holding the longest k range gets the shortest one next.  Scheduling only: same MFMA
+// sequence per tile, same bits.
+template <int QT, int Q0 = 0, int PF = 1>
+__global__ void __launch_bounds__(WG_THREADS, WG_MINWAVES) k_wgrad(MedgpDev L, int nbatch, int ntiles, int nbp) {
+    __shared__ __attribute__((aligned(16))) double smem[WG_SMEM_DOUBLES];
+    __shared__ __attribute__((aligned(16))) double rowc[4][16][wg_rowc_stride<WgElemNlml, QT>];
+    WG_PROLOGUE((PF > 1));
+    const double *U = L.Linv + (size_t)T.b * T.ld * T.ld;
+
+#ifdef MEDGP_STAMPS
+    unsigned long long wst[4] = {0, 0, 0, 0}, wlast;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wlast)::"memory");
+#define WSTAMP(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); wst[k] += t_ - wlast; wlast = t_; } while (0)
+#else
+#define WSTAMP(k) do {} while (0)
+#endif
+    WgAcc A;
+    if constexpr (PF == 1) A = wg_phase1(smem, T, U, 64 * T.I, WgNoHook());
+    else {
+        // PF register sets, set s carries the chunks c = s (mod PF): a set is refilled (chunk c + PF) as soon as its A fragment has been
+        // copied out; its staged J rows go to LDS one iteration before they are used (the LDS stays double buffered)
+        double (*Bs)[64][WG_KC + 2] = (double (*)[64][WG_KC + 2])smem;
+        v4d (&acc)[4] = A.a;
+#pragma unroll
+        for (int ct = 0; ct < 4; ct++) acc[ct] = (v4d){0.0, 0.0, 0.0, 0.0};
+        const int k0 = 64 * T.I, nch = (T.npad - k0) / WG_KC, li = T.li, g = T.g;
+        const int ctmax = (T.I == T.J) ? T.w : 3;   // wave-uniform
+        const double *Arow = U + (size_t)(64 * T.I + 16 * T.w + li) * T.ld + k0 + 2 * g;
+        const int srow = T.tid >> 2, scg = (T.tid & 3) * 8;
+        const double *Bsrc = U + (size_t)(64 * T.J + srow) * T.ld + k0 + scg;
+        v2d bst[PF][4], an[PF][4];
+#pragma unroll
+        for (int st = 0; st < PF; st++)
+            if (st < nch) {
+#pragma unroll
+                for (int u = 0; u < 4; u++) bst[st][u] = *(const v2d *)(Bsrc + st * WG_KC + 2 * u);
+#pragma unroll
+                for (int h = 0; h < 4; h++) an[st][h] = *(const v2d *)(Arow + st * WG_KC + 8 * h);
+            }
+#pragma unroll
+        for (int u = 0; u < 4; u++) *(v2d *)&Bs[0][srow][scg + 2 * u] = bst[0][u];
+        __syncthreads();
+        for (int c0 = 0; c0 < nch; c0 += PF) {
+#pragma unroll
+            for (int st = 0; st < PF; st++) {
+                const int c = c0 + st;
+                if (c >= nch) break;
+                v2d ac[4];
+#pragma unroll
+                for (int h = 0; h < 4; h++) ac[h] = an[st][h];
+                if (c + PF < nch) {
+#pragma unroll
+                    for (int u = 0; u < 4; u++) bst[st][u] = *(const v2d *)(Bsrc + (c + PF) * WG_KC + 2 * u);
+#pragma unroll
+                    for (int h = 0; h < 4; h++) an[st][h] = *(const v2d *)(Arow + (c + PF) * WG_KC + 8 * h);
+                }
+                WG_CHUNK_MFMA(ac, (st & 1));
+                if (c + 1 < nch) {
+#pragma unroll
+                    for (int u = 0; u < 4; u++) *(v2d *)&Bs[(st + 1) & 1][srow][scg + 2 * u] = bst[(st + 1) % PF][u];
+                }
+                __syncthreads();
+            }
+        }
+    }
+    WSTAMP(0);
+    wg_phase2(A, smem, T);
+    WSTAMP(1);
+    wg_phase3<QT, Q0>(L, T, smem, rowc, WgElemNlml());
     WSTAMP(2);
 #ifdef MEDGP_STAMPS
-    if (lane == 0 && b < 64) {
-        unsigned long long *dbg = (unsigned long long *)(L.xk + (size_t)b * 64 * 64);
+    if (T.lane == 0 && T.b < 64) {
+        unsigned long long *dbg = (unsigned long long *)(L.xk + (size_t)T.b * 64 * 64);
         for (int e = 0; e < 3; e++) atomicAdd(&dbg[e], wst[e]);
         atomicAdd(&dbg[3], 1ull);
     }

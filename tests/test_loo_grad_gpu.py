@@ -122,6 +122,33 @@ def test_bits_do_not_depend_on_the_batch():
     ctx.close()
 
 
+def test_bits_do_not_depend_on_the_batch_from_64_entries_on():
+    """route pinned: launches of 64 entries and more deal their tiles XCD-locally (the mapping k_loo_kinv / k_loo_wgrad share with
+    k_wgrad).  72 entries, the patients with n = 65, 130, 200 (2, 3, 4 tile rows: off-diagonal tiles, more than two chunks) 24 times
+    each; the size classes of a call are launched one by one and n = 65 is a class of its own, so a second call of 72 holds n = 130
+    and n = 200 alone, 36 times each: one ragged class of 72.  Every entry has the bits of its patient in a call of 8, through
+    medgp_loo_grad and through medgp_nlml_grad."""
+    c = G.case("lmc_sizes")
+    ps = [4] * 24 + [5] * 36 + [6] * 36                       # the patient of slot s
+    th = np.stack([c["th"][p] for p in ps])
+    ctx = make_ctx(G.fam(c), [c["pts"][p] for p in ps], "pinned")
+    eight = np.array([0, 24, 60, 1, 25, 61, 2, 26])
+    mixed = np.stack([np.arange(24), np.arange(24, 48), np.arange(60, 84)], axis=1).ravel()    # 65, 130, 200, 65, ...
+    one_class = np.stack([np.arange(24, 60), np.arange(60, 96)], axis=1).ravel()               # 130, 200, 130, ...
+    assert mixed.shape[0] == 72 and one_class.shape[0] == 72
+    for call in (ctx.loo_grad, lambda s, t: ctx.nlml_grad(s, t, True)):
+        obj8, grad8, st8 = call(eight, th[eight])
+        assert np.all(st8 == 0), st8
+        bits = {ps[s]: (obj8.view(np.uint64)[i], grad8[i].view(np.uint64)) for i, s in list(enumerate(eight))[:3]}
+        for slots in (mixed, one_class):
+            obj, grad, st = call(slots, th[slots])
+            assert np.all(st == 0), st
+            for i, s in enumerate(slots):
+                assert obj.view(np.uint64)[i] == bits[ps[s]][0], (i, s)
+                assert np.array_equal(grad[i].view(np.uint64), bits[ps[s]][1]), (i, s)
+    ctx.close()
+
+
 _CHILD = """
 import sys
 import numpy as np
