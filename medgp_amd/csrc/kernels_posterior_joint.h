@@ -112,15 +112,15 @@ __global__ void __launch_bounds__(256) k_postcov(MedgpDev L, const JointPat *__r
             if (rin && j < m) {
                 const double d = tr - tc[cs], dd = d * d;
                 const double *Bq = B + mr * D + mc[cs];
-                double k = 0.0;
+                KStar k{0.0, 0.0};   // k_posterior's element, the row factors from the LDS tables
                 if constexpr (QT > 0) {
 #pragma unroll
                     for (int q = 0; q < QT; q++)
-                        k += Bq[q * D * D] * ((rowc[q][row] * colc[q][col] + rows[q][row] * cols[q][col]) * exp_neg(cq[q] * dd));
+                        k = kstar_sep<false>(k, Bq[q * D * D], rowc[q][row], rows[q][row], colc[q][col], cols[q][col], wq[q], cq[q], d, dd);
                 } else {
-                    for (int q = 0; q < Q; q++) k += Bq[q * D * D] * (cos(wq[q] * d) * exp(-cq[q] * dd));
+                    for (int q = 0; q < Q; q++) k = kstar_gen<false>(k, Bq[q * D * D], wq[q], cq[q], d, dd);
                 }
-                v = k - acc[cs][r];
+                v = k.k - acc[cs][r];
                 if (i == j) v += hyp[mr];
             }
             Rs[row * POST_LS + col] = v;

@@ -87,6 +87,26 @@ def test_prefix_null_is_prefix_n_bit_for_bit():
     ctx.close()
 
 
+def test_full_prefix_is_the_posterior_bit_for_bit():
+    """k_forecast and k_posterior run the same panel-solve functions (kernels_posterior.h), so on the same factor a column with
+    the full prefix goes through k_posterior's instructions: mean and var are equal as bits.  k_forecast works on the
+    caller-order copy, which is the internal order only for a grouped upload or D = 1: those patients, over one, two and five
+    panels, the separable and the generic K* form."""
+    for i, sel in ((0, [1, 3]), (1, [2]), (3, [1]), (5, [0, 1]), (2, [0])):
+        fam, pts, th, qs = FC.case_data(i)
+        assert all(fam[2] == 1 or np.all(np.diff(pts[p][0]) >= 0) for p in sel)   # the caller's order is the internal order
+        ctx = make_ctx(fam, [pts[p] for p in sel])
+        m2l, t2l, _, _ = FC.call_lists(fam, qs, sel)
+        f, sf = ctx.forecast(np.arange(len(sel)), th[sel], m2l, t2l)
+        a, sa = ctx.posterior(np.arange(len(sel)), th[sel], m2l, t2l, parts=False)
+        b, sb = ctx.posterior(np.arange(len(sel)), th[sel], m2l, t2l, parts=True)
+        ctx.close()
+        assert np.all(sf == 0) and np.all(sa == 0) and np.all(sb == 0)
+        for k, p in enumerate(sel):
+            assert f[k][0].shape == (qs[p][1].shape[0],)
+            assert same_bits(f[k][:2], a[k][:2]) and same_bits(f[k][:2], b[k][:2]), (i, p)
+
+
 @pytest.mark.parametrize("i,p", [(0, 0), (5, 0)])
 def test_var_is_monotone_in_the_prefix(i, p):
     """q only ever gains non-negative terms, in a fixed order: exactly non-increasing, across tiles and panel counts"""
