@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 9: medgp_trend_batch (8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 10: medgp_components_batch (9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -398,6 +398,41 @@ int medgp_trend_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const do
                       const int32_t *meta2, const float *t2, float *mean, float *var,
                       float *dmean, float *dvar, float *cross, int32_t *status);
 
+/* Posterior of every spectral COMPONENT of the latent function at the test points: which part of the model a prediction comes from.
+ * The SE / SM / LMC-SM prior is a sum of Q independent latent components, f = sum_q f_q, each with its own period 1 / mu_q and
+ * envelope scale; the posterior of every f_q at a test point is in closed form from the factorisation the other calls make.
+ *   ref: core/gp_regression.cpp:128-214 (GP_Regression::predict), kernel/c_kernel_LMC_SM.cpp:329-372 (cross Gram)
+ * The reference has no such output; the definition is the fp64 / long-double restatement of tests/components_ref.py.
+ * Component q is k_q(tau) = cos(w_q tau) exp(-c_q tau^2), w_q = 2 pi mu_q, c_q = 2 (pi v_q)^2 (SE: Q = 1, w = 0, c = 1 / (2 l^2),
+ * B = sf^2; SM: B_q = the 1 x 1 weight).  For a test point j = (m*, t*) and a training observation (m_i, t_i), tau = t* - t_i:
+ *   K*_q[i]     = B_q[m_i, m*] k_q(tau)                  (sum_q K*_q = K* of medgp_posterior_batch)
+ *   V_q = L^-1 K*_q,  z = L^-1 y                         (L: the ONE factor of the call, after its jitter rounds)
+ *   cmean[j*Q + q]         = V_q^T z                              posterior mean of f_q at (m*, t*)
+ *   ccov[(j*Q + q)*Q + r]  = delta_qr B_q[m*, m*] - V_q^T V_r     posterior covariance of (f_q, f_r) at the point; LATENT: no sigma^2
+ *   cvar[j*Q + q]          = ccov[(j*Q + q)*Q + q]
+ * In exact arithmetic sum_q cmean = mean and sum_qr ccov + sigma^2_{m*} = var of medgp_posterior_batch.  The mean of a band S of
+ * components is sum_{q in S} cmean, its variance sum_{q, r in S} ccov (medgp_amd/components.py).
+ * nbatch, slots, theta, offsets, meta2, t2 and status mean exactly what they mean for medgp_posterior_batch: one factorisation per
+ * patient, no n > 2 guard, status[b] = jitter rounds or -1, meta2 may be NULL for SE / SM, an empty range of points is allowed, j
+ * counts the points of the call (offsets[b] + i).  cmean and cvar are required (NULL: MEDGP_ERR_ARG before any device work).  ccov
+ * may be NULL: the pair sums are not formed then.  Both triangles of ccov are written and are exactly symmetric, its diagonal has the
+ * bits of cvar, an off-diagonal is written as 0.0 - sum.  All three covariance families, 1 <= Q <= 64: a point's Q columns must fit
+ * one 64-column tile, Q > 64 is MEDGP_ERR_ARG.  The points of a patient with status[b] < 0 get NaN in all three outputs.  After k
+ * jitter rounds every quantity is that of the matrix that was factored, K + k diag(sigma^2) (the rule of the other inference calls).
+ * Supported range of the time stamps: |t| <= 2^14 h, of the training observations AND of the test points, as medgp_trend_batch:
+ * cos(w_q (t_i - t*)) is formed from the tables cos / sin (w_q t_i) and cos / sin (w_q t*).
+ * A point's outputs depend on the patient, theta and the point alone: not on the other points of the call, their order, the tile or
+ * the columns a point lands in, the launch chunk, or -- with the route pinned -- the batch-mates.  Every sum runs in fixed row order
+ * on one thread.
+ * The points go in tiles of 64 / Q per workgroup: the 64 columns of the forward solve on fp64 MFMA are the Q component columns of
+ * every point (kernels_components.h).  Work memory per launch within MEDGP_POSTERIOR_BUDGET_GB; a call whose per-entry matrices
+ * exceed the memory budget fails with MEDGP_ERR_CAPACITY, like medgp_posterior_batch.
+ * Accuracy: tests/test_components_gpu.py holds cmean, cvar and ccov to the project's bar of 2 fp32 ulps of max(|ref|, 1e-3 S), S the
+ * patient's largest |ref| of the quantity (for ccov over the whole m x Q x Q block).
+ * All pointers are HOST memory. */
+int medgp_components_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                           const int32_t *meta2, const float *t2, float *cmean, float *cvar, float *ccov, int32_t *status);
+
 /* Cohort statistics, the step after training: for each of nseries independent sample series
  * (series s = data[off[s] .. off[s] + cnt[s])) the Gaussian kernel density estimate with Silverman's bandwidth evaluated AT the
  * samples, and its "mode": weighted != 0: sum x dens / sum dens; weighted == 0: the sample with the largest density (first one).
@@ -440,7 +475,8 @@ int medgp_synchronize(medgp_ctx *ctx);
    (medgp_profile_kernel_name) -- two events per step instead of two per launch (bench.py times its headline region this way:
    the events of all seven launches cost 1.6 % of a 512-patient step); enable = 0: off */
 int medgp_profile_enable(medgp_ctx *ctx, int enable);
-/* number of distinct kernels the library launches, and their names */
+/* number of distinct kernels the library launches, and their names.  The table counts profile ENTRIES: the launches of k_components
+   (medgp_components_batch) are accounted under the entry "k_posterior", so the table and every kernel id in it stay what they were */
 int medgp_profile_num_kernels(void);
 const char *medgp_profile_kernel_name(int k);
 /* synchronises, then returns accumulated milliseconds and launch count of kernel k since the

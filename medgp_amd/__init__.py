@@ -4,11 +4,12 @@ The product is libmedgp_hip.so (hand-written HIP for gfx950 behind the C ABI in
 include/medgp_hip.h).  This package is the thin Python host layer used by the tests and
 bench.py: a ctypes binding (`capi`), the synthetic cohort generator (`synth`) and the
 cohort sharding helper (`shard`); `trend` reads the slope posterior of `Context.trend`
-(`prob_rising`, `rate_interval`, `grid`).  There is no CPU fallback: importing works anywhere,
+(`prob_rising`, `rate_interval`, `grid`), `components` the per-component posterior of `Context.components`
+(`table`, `select`, `band`).  There is no CPU fallback: importing works anywhere,
 but every compute call needs the built library and a HIP device.
 """
-from . import capi, synth, shard, trend  # noqa: F401
+from . import capi, synth, shard, trend, components  # noqa: F401
 from .capi import Context, MedgpError, lib_path, load  # noqa: F401
 from .trend import grid, prob_rising, rate_interval  # noqa: F401
 
-__all__ = ["capi", "synth", "shard", "trend", "Context", "MedgpError", "lib_path", "load", "grid", "prob_rising", "rate_interval"]
+__all__ = ["capi", "synth", "shard", "trend", "components", "Context", "MedgpError", "lib_path", "load", "grid", "prob_rising", "rate_interval"]

@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_trend_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_trend_batch", "medgp_components_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at",
 ]
 
@@ -98,6 +98,7 @@ def load():
     lib.medgp_loo_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, i32p]
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
     lib.medgp_trend_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, fp, fp, i32p]
+    lib.medgp_components_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, i32p]
     lib.medgp_synchronize.argtypes = [vp]
     lib.medgp_profile_enable.argtypes = [vp, C.c_int]
     lib.medgp_profile_num_kernels.restype = C.c_int
@@ -497,6 +498,30 @@ class Context:
         for b in range(nb):
             a, e = int(offsets[b]), int(offsets[b + 1])
             out.append((mean[a:e].copy(), var[a:e].copy(), dmean[a:e].copy(), dvar[a:e].copy(), cr[a:e].copy() if cross else None))
+        return out, st
+
+    def components(self, slots, theta, meta2_list, t2_list, cov=True):
+        """medgp_components_batch: the posterior of every spectral component f_q of the latent f = sum_q f_q at every test point.
+        Arguments as posterior().  Returns ([(cmean[m, Q], cvar[m, Q], ccov[m, Q, Q] or None) per patient], status): cmean[j, q] the
+        posterior mean of f_q at point j, ccov[j] the Q x Q posterior covariance of the components there (LATENT: no noise term),
+        cvar[j] its diagonal.  medgp_amd.components names the components (period, length scale, weight) and sums bands of them."""
+        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
+        nb, Q = slots.shape[0], self.Q
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([x.shape[0] for x in ts])
+        M = int(offsets[-1])
+        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
+        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+        cmean, cvar = (np.empty((max(M, 1), Q), dtype=np.float32) for _ in range(2))
+        cc = np.empty((max(M, 1), Q, Q), dtype=np.float32) if cov else None
+        st = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_components_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
+                                                   offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
+                                                   _ptr(cmean, C.c_float), _ptr(cvar, C.c_float), _ptr(cc, C.c_float), _ptr(st, C.c_int32)))
+        out = []
+        for b in range(nb):
+            a, e = int(offsets[b]), int(offsets[b + 1])
+            out.append((cmean[a:e].copy(), cvar[a:e].copy(), cc[a:e].copy() if cov else None))
         return out, st
 
     def posterior_joint(self, slots, theta, meta2_list, t2_list, eps_list=None, cov=True):

@@ -105,6 +105,16 @@ inline void build_trend_tiles(const std::vector<TableClass> &cls, const int *ord
     build_point_tiles(cls, order, offsets, nullptr, 0, budget, T, TREND_TW);
 }
 
+// medgp_components_batch: the 64 columns of a tile are the Q component columns of 64 / Q points (kernels_components.h; Q <= 64)
+MEDGP_HD inline int components_tw(int Q) { return 64 / Q; }
+// doubles of a tile beyond its ld x 64 work rows: the running sums of its (64 / Q) Q (Q - 1) / 2 component pairs (at most 2016)
+MEDGP_HD inline size_t components_extra(int Q, bool with_cov) { return with_cov ? (size_t)components_tw(Q) * ((size_t)Q * (Q - 1) / 2) : 0; }
+// the posterior call's tables with that many points per tile and those extra doubles
+inline void build_components_tiles(const std::vector<TableClass> &cls, const int *order, const int64_t *offsets, int Q, bool with_cov,
+                                   size_t budget, PointTables<PostTile> &T) {
+    build_point_tiles(cls, order, offsets, nullptr, components_extra(Q, with_cov), budget, T, components_tw(Q));
+}
+
 struct JointTables : PointTables<PostTile> {
     std::vector<JointPat> pats;
     std::vector<JointTile> pairs, blks;

@@ -15,6 +15,7 @@
 #include "kernels_posterior_joint.h"
 #include "kernels_forecast.h"
 #include "kernels_trend.h"
+#include "kernels_components.h"
 #include "kernels_loo.h"
 #include "kernels_loo_grad.h"
 
@@ -104,10 +105,11 @@ struct Arena {
 //   joint posterior: the patient / tile-pair / row-block tables of the call, C and the float covariance blocks of one launch chunk, the
 //   call's eps and samples, cov_status -- LOO: its group / tile-pair / job tables, the blocks of one launch chunk, group_status;
 //   LOO: the singleton table and the index lists; BUF_GVEC: the per-entry vectors [u | s | v | log p] of medgp_loo_grad;
-//   BUF_SLOPE: the per-point outputs [dmean | dvar | cross] of medgp_trend_batch
+//   BUF_SLOPE: the per-point outputs [dmean | dvar | cross] of medgp_trend_batch;
+//   BUF_COMP: the per-point outputs [cmean | cvar | ccov] of medgp_components_batch (Q, Q and Q^2 floats per point)
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -988,14 +990,16 @@ int check_call(medgp_ctx *c, int nbatch, const int32_t *slots) {
     return MEDGP_OK;
 }
 
-// the test points of a call: patient b owns points [offsets[b], offsets[b + 1]) of meta2 / t2 / mean / var
-int check_points(medgp_ctx *c, int nbatch, const int64_t *offsets, const int32_t *meta2, const float *t2, const float *mean, const float *var) {
+// the test points of a call: patient b owns points [offsets[b], offsets[b + 1]) of meta2 / t2 / mean / var (or the two per-point
+// outputs the call requires in their place, named by `outs`)
+int check_points(medgp_ctx *c, int nbatch, const int64_t *offsets, const int32_t *meta2, const float *t2, const float *mean, const float *var,
+                 const char *outs = "mean / var") {
     if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
     for (int b = 0; b < nbatch; b++)
         if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
     const int64_t M = offsets[nbatch];
     if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
-    if (M > 0 && (!t2 || !mean || !var)) return fail(c, MEDGP_ERR_ARG, "t2 / mean / var is NULL");
+    if (M > 0 && (!t2 || !mean || !var)) return fail(c, MEDGP_ERR_ARG, "t2 / %s is NULL", outs);
     if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
     return MEDGP_OK;
 }
@@ -1071,7 +1075,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 9; }
+int medgp_abi_version(void) { return 10; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2252,7 +2256,57 @@ int trend_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *the
     }
     return read_status(c, nbatch, status);
 }
+
+// medgp_components_batch (kernels_components.h): the posterior call's pipeline run, then k_components over tiles of 64 / Q points whose
+// 64 columns are the Q component columns of every point.  Launch chunks within the posterior budget; the launches are accounted under
+// the profile entry of k_posterior (the profile table keeps its names).
+int components_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets, const int32_t *meta2,
+                    const float *t2, float *cmean, float *cvar, float *ccov, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
+    if (!cmean || !cvar) return fail(c, MEDGP_ERR_ARG, "cmean / cvar is NULL");
+    const int Q = c->Q;
+    if (Q > 64) return fail(c, MEDGP_ERR_ARG, "medgp_components_batch supports Q <= 64 (Q = %d): the component columns of a point share one 64-column tile", Q);
+    int max_n = 0, rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    if ((rc = check_points(c, nbatch, offsets, meta2, t2, cmean, cvar, "cmean / cvar"))) return rc;
+    const int64_t M = offsets[nbatch];
+    const size_t MQ = (size_t)std::max<int64_t>(M, 1) * Q;
+    std::vector<double> ht2;
+    std::vector<int> hm2;
+    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the outputs are invariant under a permutation of the training observations: the grouped copy serves, as for the posterior
+    if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
+    PointTables<PostTile> T;
+    build_components_tiles(table_classes(c->plan), c->plan.order.data(), offsets, Q, ccov != nullptr, c->posterior_budget, T);
+    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if ((rc = buf_ensure(c, BUF_COMP, MQ * (2 + (ccov ? (size_t)Q : 0)) * sizeof(float)))) return rc;
+    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
+    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
+    // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
+    if ((rc = factor_run(c, nbatch, max_n, theta, false, true))) return rc;
+    float *d_cmean = buf<float>(c, BUF_COMP), *d_cvar = d_cmean + MQ, *d_ccov = d_cvar + MQ;
+    for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
+        Launcher l(c, KID_POSTERIOR);
+        hipLaunchKernelGGL(k_components, dim3(ch.nt), dim3(256), 0, c->stream, class_view(c, c->plan, c->plan.cls[ch.cls]), buf<PostTile>(c, BUF_TILES) + ch.t0,
+                           buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK), ch.stride, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR),
+                           d_cmean, d_cvar, ccov ? d_ccov : nullptr);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (M > 0) {
+        HIPCHK(c, hipMemcpyAsync(cmean, d_cmean, sizeof(float) * M * Q, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cvar, d_cvar, sizeof(float) * M * Q, hipMemcpyDeviceToHost, c->stream));
+        if (ccov) HIPCHK(c, hipMemcpyAsync(ccov, d_ccov, sizeof(float) * M * Q * Q, hipMemcpyDeviceToHost, c->stream));
+    }
+    return read_status(c, nbatch, status);
+}
 }  // namespace
+
+int medgp_components_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                           const int32_t *meta2, const float *t2, float *cmean, float *cvar, float *ccov, int32_t *status) {
+    return components_impl(c, nbatch, slots, theta, offsets, meta2, t2, cmean, cvar, ccov, status);
+}
 
 int medgp_trend_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
                       const int32_t *meta2, const float *t2, float *mean, float *var, float *dmean, float *dvar, float *cross,
