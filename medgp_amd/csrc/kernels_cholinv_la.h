@@ -27,17 +27,11 @@
 // in-kernel.  No status is read back by the host: calls that take this schedule are asynchronous like all others.
 #pragma once
 #include "kernels_cholinv.h"
+#include "call_plan.h"
 
 #define LA_KC 32          // history columns staged per barrier
 #define LA_THREADS 256
-#define LA_SLICE 4        // panels (64 columns each) per look-ahead slice: the shortest slice (scratch is dimensioned for it)
-// Panels per slice of the partial sums PRODUCED at step k (consumed one step later).  It depends on the step alone -- not on the batch
-// or on the batch-mates' sizes, so a patient's arithmetic is the same in any call.  Late steps of a long factorisation use longer
-// slices: a single N = 4096 evaluation has 526-600 tasks per step from k = 37 on, a few more than the chip's 512 workgroup slots,
-// and paid a second, nearly empty round of 24-us tasks per step.  Measured at N = 4096 (k_la_step, interleaved on one box): 4 panels
-// throughout 2.20 ms; 5 from step 36 2.17; 5 from 36 + 6 from 52 2.11; 5 from 32 + 6 from 44 (this rule) 2.08; longer slices or
-// earlier switches 2.09-2.12.  (N <= 2048 never reaches step 32: unchanged.)
-__host__ __device__ inline int la_slice_len(int k) { return k < 32 ? LA_SLICE : (k < 44 ? LA_SLICE + 1 : LA_SLICE + 2); }
+// LA_SLICE and la_slice_len(k), the slice rule that also sizes the scratch on the host: call_plan.h
 #define LA_S 66           // LDS row stride of the 64x64 operand tiles
 #ifndef LA_F_LATE
 #define LA_F_LATE 0       // 1: F tasks request X_k / the pre-solve copy after their partial sums instead of up front

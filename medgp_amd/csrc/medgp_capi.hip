@@ -3,6 +3,7 @@
 // point fails with MEDGP_ERR_NODEVICE.
 #include "../../include/medgp_hip.h"
 #include "medgp_dev.h"
+#include "call_plan.h"
 #include "kernels_core.h"
 #include "kernels_v0.h"
 #include "kernels_cholinv.h"
@@ -39,38 +40,6 @@ thread_local std::string g_create_error;   // last medgp_create error of the cal
 
 struct EvPair { int kid; hipEvent_t a, b; };
 
-// ---- the plan of a call (round 5) --------------------------------------------------------------------------------------------
-// A call's entries are ordered by size internally and cut into SIZE CLASSES (64-block count in (2^(j-1), 2^j]): every class is a view
-// of the batch buffers with its own leading dimension (the class's largest n rounded up to 64), its own launch geometry and its own
-// factorisation route, and the classes of one call run beside each other on separate streams.  Why: the reference gives patients
-// resources by size (ref: scripts/slurm_della.json:6-62, medgpc/util/run_exp_generator.py:213-260); rounds 1-4 chose ONE route per
-// call from the call's largest patient, so one N ~ 6000 patient in a batch of 300 ran on one workgroup and set the time of the call.
-enum Route { ROUTE_WG44 = 0, ROUTE_WG84 = 1, ROUTE_LA = 2 };
-struct SizeClass {
-    int b0 = 0, count = 0;     // internal entries [b0, b0 + count)
-    int nbmax = 1;             // 64-blocks of the class's largest entry
-    int ld = 64;               // leading dimension of the class view
-    int wave = 0;              // memory wave of the call the class runs in (round 6; BatchPlan::nwaves)
-    size_t off_mat = 0, off_vec = 0, off_tab = 0, off_slab = 0;   // offsets (doubles) of the class inside Kmat/Linv, z/alpha/wdiag, cs/sn, slab (relative to its wave: waves reuse the arenas)
-    long long tsum = 0;        // sum of the cost model over its entries (route rule)
-    int route = ROUTE_WG84;    // last route taken (diagnostics: medgp_last_plan)
-};
-struct BatchPlan {
-    bool identity = true;      // internal order == caller order
-    std::vector<int> order;    // internal index -> caller index
-    std::vector<int> inv;      // caller index -> internal index
-    std::vector<int> en;       // n of every entry, internal order
-    std::vector<SizeClass> cls;
-    size_t need_mat = 0, need_vec = 0, need_tab = 0, need_slab = 0;   // doubles the call needs of each arena (largest wave)
-    // Memory waves (round 6): a call whose per-entry matrices exceed the context's budget (512 resident patients of N ~ 6000 would
-    // need 296 GB) is run as consecutive WAVES of whole size classes that each fit it; the waves reuse the arenas in stream order.
-    int nwaves = 1;
-    bool with_u = true;        // laid out for Kmat AND Linv (false: an nlml-only plan, 8 ld^2 bytes per entry instead of 16)
-    // Lane base (medgp_screen's two lanes, round 6): the plan's entries use rows [row0, row0 + n) of the batch-indexed buffers and the
-    // arenas from these offsets on (doubles), so that two plans can be in flight on two streams at once.  0 for every other call.
-    int row0 = 0;
-    size_t mat0 = 0, vec0 = 0, tab0 = 0, la_part0 = 0, la_small0 = 0;
-};
 constexpr int kAuxStreams = 4;
 
 // ---- device memory arenas (round 6) -----------------------------------------------------------------------------------------
@@ -117,10 +86,11 @@ enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, 
 
 struct medgp_ctx {
     int device = -1;
-    int kidx = 0, Q = 0, D = 0, R = 0, H = 0, nlik = 0;
+    int kidx = 0, R = 0, H = 0, nlik = 0;
+    PlanRules rules;          // what the plan of a call reads of the context (call_plan.h): Q, D, num_cu, max_batch, the budgets and the route knobs
     double pi = 3.14159265;   // ref: util/global_settings.h:6
     hipStream_t own_stream = nullptr, stream = nullptr;
-    int max_slots = 0, max_n = 0, max_batch = 0, ldn = 0;
+    int max_slots = 0, max_n = 0, ldn = 0;
     MedgpDev dev{};
     // device allocations
     std::vector<void *> allocs;
@@ -165,9 +135,6 @@ struct medgp_ctx {
     // calls or are sized once by medgp_reserve_plan (struct Arena).
     size_t full_mat = 0, full_vec = 0, full_tab = 0, full_slab = 0;
     Arena arena[AR_COUNT];
-    size_t mem_budget = (size_t)64 << 30;   // bytes of per-entry matrices one wave of a call may use (MEDGP_MEM_BUDGET_GB)
-    size_t screen_budget = (size_t)2 << 30; // the same for one chunk of medgp_screen (MEDGP_SCREEN_BUDGET_GB)
-    long long screen_work = 32768;  // block pairs (sum nb^2) at which a medgp_screen chunk of look-ahead entries is closed (MEDGP_SCREEN_WORK)
     // blocks that outgrown arenas left behind: kernels queued before the growth may still read them, so they are NOT freed there (no
     // wait at the growth) but at the next point where the context's streams are known to be idle (free_retired)
     std::vector<void *> retired;
@@ -196,23 +163,16 @@ struct medgp_ctx {
     bool profiling = false;
     int profile_only = -1;    // >= 0: only launches of this kernel id are bracketed (medgp_profile_enable(ctx, 2 + id))
     int wgrad_deep = -1;      // MEDGP_WGRAD_DEEP=1/2: force the prefetch depth of k_wgrad's operand stream (A-B; same bits); -1: by launch size
-    bool use_v0 = false;      // MEDGP_V0=1: the generic (non-templated) pair kernels of the Q > 8 route for any Q (debug / A-B parity)
-    int cholinv_nw = 0;       // MEDGP_CHOLINV_NW=44|84 forces the workgroup shape <waves, 16-row units per wave> (0 = auto)
     int la_park = 256;        // MEDGP_LA_PARK=<workgroup id>|0: where the look-ahead schedule parks its sleeping workgroup (0 = off)
     int la_park_maxbatch = 8; // MEDGP_LA_PARK_MAXBATCH: largest batch the parking is used for (measured: 4 x N=2048 -5 %, 16 x N=2048 +2 %)
-    int force_mc = 0;         // MEDGP_MULTI_CU=1 forces / -1 forbids the multi-CU factorisation (0 = auto)
-    int pin_route = 0;        // medgp_pin_route: every entry is factored by k_cholinv<8,4> whatever the batch (reproducible bits)
-    int num_cu = 256;
     int dbg_fail = 0;         // MEDGP_DEBUG_FAIL_ATTEMPTS=k: test hook, see MedgpDev::dbg_fail
     int class_streams = kAuxStreams;   // MEDGP_CLASS_STREAMS=0: the size classes of a call run back to back on the call's stream (A-B)
-    int no_classes = 0;       // MEDGP_NO_CLASSES=1: rounds 1-4 behaviour -- one class per call, one route from its largest entry (A-B)
     hipStream_t aux[kAuxStreams] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[kAuxStreams] = {nullptr, nullptr, nullptr, nullptr};
     // second lane of medgp_screen (round 6): chunks alternate between c->stream and s_screen1, each with its own rows of the batch
     // buffers and its own half of the arenas -- the assembly of one chunk runs beside the factorisation of the other
     hipStream_t s_screen1 = nullptr;
     hipEvent_t ev_fork1 = nullptr, ev_screen0 = nullptr;
-    int screen_lanes = 2;           // MEDGP_SCREEN_LANES=1: one lane (rounds 1-5)
     char *h_screen_tab = nullptr;   // pinned: the slot / position / theta-row tables of ALL chunks of one medgp_screen call
     size_t screen_tab_cap = 0;
     std::vector<EvPair> events;
@@ -397,90 +357,22 @@ int pin_stage(medgp_ctx *c, size_t bytes, void **out) {
     return MEDGP_OK;
 }
 
-inline int tri(int n) { return n * (n + 1) / 2; }
-inline int blocks64(int n) { return (std::max(n, 1) + 63) / 64; }
-// size class of an entry of nb 64-blocks: 0 -> {1}, 1 -> {2}, 2 -> {3, 4}, 3 -> {5 .. 8}, ...
-inline int size_bucket(int nb) { int j = 0; while ((1 << j) < nb) j++; return j; }
-// Cost model of one entry on ONE workgroup (k_cholinv), fitted to profiles/r04_route_table.txt (ms = 4.4e-4 nb^2 (nb + 17):
-// N = 256 0.15, 512 0.70, 768 1.83, 1024 3.7; N = 8192: 1.05 s against 1.33 s measured).  Integer, so the route rule is exact.
-inline long long wg_cost(int nb) { return (long long)nb * nb * (nb + 17); }
-
-// The grid of k_wgrad (and of k_loo_kinv / k_loo_wgrad, which walk the same tiles) for a class of nbatch entries of sizes entry_n, nt64
-// 64-blocks the largest.  ragged: entries of different 64-block counts in the class.  Entries of different sizes in a launch of few
-// entries: odd stride nbp of the entry index, so that every entry's tiles go to all XCDs (kernels_wgrad.h); equally large entries keep
-// the stride nbatch (balanced as it is, and the measured form).
-struct WgradGrid { bool ragged; int nbp, wg_tiles; dim3 grid; };
-inline WgradGrid wgrad_grid(const int *entry_n, int nbatch, int nt64) {
-    WgradGrid g{false, nbatch, tri(nt64), dim3()};
-    for (int bb = 1; bb < nbatch; bb++) g.ragged = g.ragged || blocks64(entry_n[bb]) != blocks64(entry_n[0]);
-    if (g.ragged && nbatch < 64) g.nbp = nbatch | 1;
-    g.grid = dim3(std::max(8 * ((nbatch + 7) / 8), g.nbp) * g.wg_tiles);
-    return g;
-}
-
-// Lay out the plan of a call from the sizes of its entries alone (en[b] = n of caller entry b): internal order, size classes, memory
-// waves, offsets, needs.  with_u: the call forms U = L^-T (gradient / factor outputs / predict); an nlml-only call touches neither
-// Linv nor the gradient slab.  Pure host arithmetic: medgp_reserve_plan runs it on announced sizes to find the high-water marks.
-void layout_plan(const medgp_ctx *c, const int *en, int nbatch, bool with_u, BatchPlan &P) {
-    P.order.resize(nbatch); P.inv.resize(nbatch); P.en.resize(nbatch);
-    P.cls.clear();
-    P.with_u = with_u;
-    int mx = 0;
-    for (int b = 0; b < nbatch; b++) { P.order[b] = b; mx = std::max(mx, en[b]); }
-    const bool classes = !c->no_classes;
-    // by 64-block count, largest first (what the hardware dispatches first runs longest: LPT inside every launch); ties keep the caller's order
-    if (classes) std::stable_sort(P.order.begin(), P.order.end(), [&](int a, int b) { return blocks64(en[a]) > blocks64(en[b]); });
-    P.identity = true;
-    for (int i = 0; i < nbatch; i++) { P.inv[P.order[i]] = i; P.en[i] = en[P.order[i]]; P.identity = P.identity && P.order[i] == i; }
-    const size_t Q = c->Q, D = c->D, bpe = with_u ? 16 : 8;   // bytes of per-entry matrices per ld^2
-    size_t om = 0, ov = 0, ot = 0, os = 0, wave_bytes = 0;
-    int wave = 0;
-    P.need_mat = P.need_vec = P.need_tab = P.need_slab = 0;
-    for (int i = 0; i < nbatch;) {
-        SizeClass k;
-        k.b0 = i;
-        const int bk = size_bucket(blocks64(P.en[i]));
-        k.nbmax = classes ? blocks64(P.en[i]) : blocks64(mx);   // (sorted: the first entry of a class is its largest)
-        k.ld = 64 * k.nbmax;
-        // a class is cut where its matrices would exceed the budget of one wave (512 entries of N ~ 6000: 296 GB)
-        const size_t per = bpe * (size_t)k.ld * k.ld;
-        const int cmax = classes ? (int)std::max<size_t>(1, c->mem_budget / per) : nbatch;
-        int j = i;
-        while (j < nbatch && j - i < cmax && (!classes || size_bucket(blocks64(P.en[j])) == bk)) { k.tsum += wg_cost(blocks64(P.en[j])); j++; }
-        k.count = j - i;
-        const size_t kbytes = per * k.count;
-        if (classes && wave_bytes > 0 && wave_bytes + kbytes > c->mem_budget) { wave++; om = ov = ot = os = 0; wave_bytes = 0; }
-        k.wave = wave;
-        wave_bytes += kbytes;
-        k.off_mat = om; k.off_vec = ov; k.off_tab = ot; k.off_slab = os;
-        om += (size_t)k.count * k.ld * k.ld; ov += (size_t)k.count * k.ld; ot += (size_t)k.count * Q * k.ld;
-        if (with_u) os += (size_t)k.count * 3 * Q * (k.ld / 16 + D) * (k.ld / 64 + D);
-        P.need_mat = std::max(P.need_mat, om); P.need_vec = std::max(P.need_vec, ov); P.need_tab = std::max(P.need_tab, ot); P.need_slab = std::max(P.need_slab, os);
-        P.cls.push_back(k);
-        i = j;
-    }
-    P.nwaves = wave + 1;
-}
-
 // Select the batch and lay out its plan.  caller_order: entries whose patient was not uploaded grouped by output use the caller-order
 // copy of the patient (slot + max_slots), so that the factor is the one the caller's order defines (no gradient on that copy).
-int set_batch(medgp_ctx *c, int nbatch, const int32_t *slots, int *max_n_out, bool caller_order, bool with_u) {
-    if (nbatch < 1 || nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
-    int mx = 0;
+int set_batch(medgp_ctx *c, int nbatch, const int32_t *slots, bool caller_order, bool with_u) {
+    if (nbatch < 1 || nbatch > c->rules.max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->rules.max_batch);
     std::vector<int> eff(nbatch), en(nbatch);
     for (int b = 0; b < nbatch; b++) {
         int s = slots[b];
         if (s < 0 || s >= c->max_slots || c->h_n[s] < 0) return fail(c, MEDGP_ERR_ARG, "slots[%d] = %d is not a resident patient", b, s);
-        mx = std::max(mx, c->h_n[s]);
         en[b] = c->h_n[s];
         eff[b] = (caller_order && !c->h_perm_identity[s]) ? s + c->max_slots : s;
     }
-    *max_n_out = mx;
     bool same = (nbatch == c->last_nbatch) && c->plan.with_u == with_u && std::memcmp(c->h_bslot.data(), eff.data(), sizeof(int) * nbatch) == 0;
     if (same) return MEDGP_OK;
     std::memcpy(c->h_bslot.data(), eff.data(), sizeof(int) * nbatch);
     BatchPlan &P = c->plan;
-    layout_plan(c, en.data(), nbatch, with_u, P);
+    layout_plan(c->rules, en.data(), nbatch, with_u, P);
     // the tables travel through the pinned ring: no wait for the device (the lock-step optimiser changes the active set on
     // most steps; stream order puts the copy behind the kernels of the previous call that still read the old tables)
     const bool need_pos = !(P.identity && P.cls.size() == 1);
@@ -504,8 +396,8 @@ MedgpDev class_view(const medgp_ctx *c, const BatchPlan &P, const SizeClass &k) 
     MedgpDev V = L;
     const size_t Q = L.Q, D = L.D, b0 = (size_t)k.b0 + (size_t)P.row0;
     V.ldn = k.ld;
-    V.slab_R = k.ld / 16 + (int)D; V.slab_C = k.ld / 64 + (int)D;
-    V.slab_stride = (size_t)3 * Q * V.slab_R * V.slab_C;
+    const SlabGeom sg = slab_geom(k.ld, L.Q, L.D);
+    V.slab_R = sg.R; V.slab_C = sg.C; V.slab_stride = sg.stride;
     V.bslot = L.bslot + b0;
     V.bpos = (P.identity && P.cls.size() == 1) ? nullptr : c->d_bpos + b0;
     V.tpos = c->tpos_on ? c->d_tpos + b0 : nullptr;
@@ -608,7 +500,7 @@ int arena_ensure(medgp_ctx *c, int id, size_t bytes, size_t limit, bool exact, b
     const size_t old = A.bytes;
     if (A.base) { c->retired.push_back(A.base); c->retired_bytes += A.bytes; }
     A = Arena{};
-    if (c->retired_bytes > c->mem_budget / 2) { int rc = sync_ctx_streams(c); if (rc) return rc; free_retired(c, false); }
+    if (c->retired_bytes > c->rules.mem_budget / 2) { int rc = sync_ctx_streams(c); if (rc) return rc; free_retired(c, false); }
     size_t want = exact ? bytes : std::max(bytes, old + old / 2);
     if (limit >= bytes) want = std::min(want, limit);
     void *q = nullptr;
@@ -651,39 +543,30 @@ int ensure_arena(medgp_ctx *c, size_t need_k, size_t need_u, size_t need_vec, si
     return MEDGP_OK;
 }
 
-// scratch of the look-ahead factorisation for the classes of a wave that take it: two arenas, carved up per class -- the classes run
-// on different streams.  with_u = false (nlml only): no U row blocks, so the partial-sum slab holds nbmax + 1 row blocks, not 2 nbmax + 1.
-struct LaNeed { int count, nbmax, ld; LaArgs A; };
-inline size_t la_part_doubles(const LaNeed &e, bool with_u) { return (size_t)e.count * 2 * ((with_u ? 2 : 1) * e.nbmax + 1) * ((e.nbmax + LA_SLICE - 1) / LA_SLICE) * 4096; }
-inline size_t la_small_doubles(const LaNeed &e) { return (size_t)e.count * (64 * (size_t)e.ld + 5 * 2 * 4096 + 2 * (size_t)((e.nbmax + LA_SLICE - 1) / LA_SLICE) * 4096 + 1); }
-int ensure_la(medgp_ctx *c, std::vector<LaNeed> &v, bool with_u, size_t part0 = 0, size_t small0 = 0) {
-    const size_t nring = 2;
-    size_t need_part = part0, need_small = small0;   // (part0 / small0: the lane base of the plan, doubles)
-    for (const LaNeed &e : v) { need_part += la_part_doubles(e, with_u); need_small += la_small_doubles(e); }
+// scratch of the look-ahead factorisation for the classes of a wave that take it: two arenas, carved up per class (la_layout,
+// call_plan.h) -- the classes run on different streams.  args[i] = the kernel arguments of v[i]; part0 / small0: the lane base of the
+// plan (doubles).
+int ensure_la(medgp_ctx *c, const std::vector<LaNeed> &v, bool with_u, std::vector<LaArgs> &args, size_t part0 = 0, size_t small0 = 0) {
+    size_t need_part = part0, need_small = small0;
+    for (const LaNeed &e : v) { const LaLayout Y = la_layout(e, with_u); need_part += Y.part_doubles; need_small += Y.small_doubles; }
     int rc;
     // (a block that must grow is replaced; the old one is retired, not freed: kernels queued on any of the context's streams may still read it)
     if ((rc = arena_ensure(c, AR_LA_PART, need_part * sizeof(double), 0, false, nullptr))) return rc;
     if ((rc = arena_ensure(c, AR_LA_SMALL, need_small * sizeof(double), 0, false, nullptr))) return rc;
     double *pp = (double *)c->arena[AR_LA_PART].base + part0, *ps = (double *)c->arena[AR_LA_SMALL].base + small0;
-    for (LaNeed &e : v) {
+    args.clear();
+    for (const LaNeed &e : v) {
+        const LaLayout Y = la_layout(e, with_u);
         LaArgs A{};
-        const size_t nb = e.count;
-        A.nbmax = e.nbmax;
-        A.maxslice = (e.nbmax + LA_SLICE - 1) / LA_SLICE;
-        A.rows = (with_u ? 2 : 1) * e.nbmax + 1;
+        A.nbmax = e.nbmax; A.maxslice = Y.maxslice; A.rows = Y.rows;
         A.ring = 1;
         A.nbatch = e.count;
         A.part = pp;
-        A.ybuf = ps;
-        A.xk2 = ps + nb * 64 * e.ld;
-        A.pnx = A.xk2 + nb * nring * 4096;
-        A.pnx2 = A.pnx + nb * nring * 4096;
-        A.dterm = A.pnx2 + nb * nring * 4096;
-        A.dsum = A.dterm + nb * nring * 4096;
-        A.dpart = A.dsum + nb * nring * 4096;
-        A.flag = (int *)(A.dpart + nb * 2 * A.maxslice * 4096);
-        e.A = A;
-        pp += la_part_doubles(e, with_u); ps += la_small_doubles(e);
+        A.ybuf = ps + Y.ybuf; A.xk2 = ps + Y.xk2; A.pnx = ps + Y.pnx; A.pnx2 = ps + Y.pnx2;
+        A.dterm = ps + Y.dterm; A.dsum = ps + Y.dsum; A.dpart = ps + Y.dpart;
+        A.flag = (int *)(ps + Y.flag);
+        args.push_back(A);
+        pp += Y.part_doubles; ps += Y.small_doubles;
     }
     return MEDGP_OK;
 }
@@ -700,13 +583,13 @@ int run_pipeline_one(medgp_ctx *c, hipStream_t stream, const MedgpDev &L, int nb
         Launcher l(c, KID_ASSEMBLE, stream);
         const dim3 tg(tri(nt64), nbatch), tb(256);
         // 9 .. 16 components: the first eight, then the rest added to the same tiles (kernels_assemble.h)
-        if (c->use_v0 || !with_q16(L.Q, [&](auto q, auto q0) { hipLaunchKernelGGL((k_assemble_t<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, stream, L); }))
+        if (c->rules.use_v0 || !with_q16(L.Q, [&](auto q, auto q0) { hipLaunchKernelGGL((k_assemble_t<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, stream, L); }))
             hipLaunchKernelGGL(k_assemble_v0, tg, tb, 0, stream, L);   // Q > 16 (or MEDGP_V0): generic kernel
     };
     const bool inv = flag_grad || need_inverse;
     const int want_mode = inv ? 1 : (store_ukk ? 2 : 0);   // bit 0: U rows + alpha; 2: diagonal blocks U_kk only (k_predict)
     // Few large patients: the multi-CU look-ahead schedule (kernels_cholinv_la.h) instead of one workgroup per patient; which classes
-    // of a call take it is decided in run_pipeline (route rule).
+    // of a call take it is decided by choose_routes (call_plan.h: the route rule).
     const bool multi_cu = route == ROUTE_LA;
     if (multi_cu) {
         // which entries the multi-CU schedule factors: more than one 64-block (host mirror of the patient sizes)
@@ -771,13 +654,13 @@ int run_pipeline_one(medgp_ctx *c, hipStream_t stream, const MedgpDev &L, int nb
 #endif
     if (flag_grad) {
         const int wg_tiles = wg.wg_tiles, nbp = wg.nbp;
-        const dim3 tg = wg.grid, tb(WG_THREADS);
+        const dim3 tg(wg.grid), tb(WG_THREADS);
         Launcher lw(c, KID_WGRAD, stream);
         // few large patients (the launch fills the chip less than four times): operand prefetch two chunks ahead + serpentine tile order (kernels_wgrad.h)
-        const int pf = c->wgrad_deep >= 0 ? c->wgrad_deep : ((long)nbatch * wg_tiles <= 16L * c->num_cu ? 2 : 1);
+        const int pf = c->wgrad_deep >= 0 ? c->wgrad_deep : ((long)nbatch * wg_tiles <= 16L * c->rules.num_cu ? 2 : 1);
         // 9 .. 16 components: two launches, each reducing its own components into its own slab planes (kernels_wgrad.h);
         // Q > 16 (or MEDGP_V0): generic kernels below
-        from_slab = !c->use_v0 && with_q16(L.Q, [&](auto q, auto q0) {
+        from_slab = !c->rules.use_v0 && with_q16(L.Q, [&](auto q, auto q0) {
             constexpr int QQ = decltype(q)::value, Q0 = decltype(q0)::value;
             if (pf >= 2) hipLaunchKernelGGL((k_wgrad<QQ, Q0, 2>), tg, tb, 0, stream, L, nbatch, wg_tiles, nbp);
             else hipLaunchKernelGGL((k_wgrad<QQ, Q0, 1>), tg, tb, 0, stream, L, nbatch, wg_tiles, nbp);
@@ -799,7 +682,7 @@ int run_pipeline_one(medgp_ctx *c, hipStream_t stream, const MedgpDev &L, int nb
         Launcher l(c, KID_EPILOGUE, stream);
         // few entries: the hypers of an entry are spread over workgroups (H = 2954 at D = 64: 0.18 -> 0.07 ms for one entry); with a
         // workgroup per CU anyway, one part per entry is faster (each part stages S and A again: 0.09 vs 0.20 ms at 512 entries)
-        const int nparts = (2 * nbatch >= c->num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (L.H + 255) / 256);
+        const int nparts = (2 * nbatch >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (L.H + 255) / 256);
         hipLaunchKernelGGL(k_epilogue, dim3(nbatch, nparts), dim3(256), 0, stream, L, theta_dev, flag_grad, from_slab, nlml_dev, grad_dev, (int *)status_dev);
     }
     HIPCHK(c, hipGetLastError());
@@ -809,126 +692,14 @@ int run_pipeline_one(medgp_ctx *c, hipStream_t stream, const MedgpDev &L, int nb
 
 // The evaluation pipeline; everything is asynchronous and ordered on c->stream.  Every size class of the plan gets its own kernel
 // chain; with more than one class the chains run on auxiliary streams forked from / joined into c->stream, so that the workgroup-per-
-// patient launches of the small classes fill the CUs a look-ahead chain of the large ones leaves idle.
-//
-// Route rule.  Measured on MI355X, round 4 (scratch/route_sweep.py -> profiles/r04_route_table.txt; factorisation ms per call, nlml +
-// gradient, LA = look-ahead schedule, 44 / 84 = k_cholinv<4,4> / <8,4>; the same table at D = 2 and D = 24):
-//   N=128: 44 wins at every batch size (0.069 vs LA 0.073 at 8 entries, 0.081 vs 0.112 at 256)
-//   N=256: LA <= 96 entries (0.127 / 0.168 vs 44: 0.168 / 0.182 at 8 / 96), 44 from 128 on (0.185 vs LA 0.197)
-//   N=384: LA <= 128 (0.390 vs 84: 0.395), 84 from 160 on (0.412 vs LA 0.473)
-//   N=512: LA <= 96 (0.560 vs 0.683), tie at 128 (0.709 / 0.705), 84 from 160 on (0.712 vs 0.885)
-//   N=768 / 1024: LA <= 128 (1.78 vs 1.86; 3.46 vs 3.69), 84 from 160 on (1.91 vs 2.19; 3.74 vs 4.34)
-// The LA time grows linearly with the batch, the single-workgroup time is flat up to one patient per CU.  For a uniform call that gave:
-// never for two blocks; up to 7/16 #CU entries (112) for three or four blocks; up to 9/16 #CU (144) from five blocks on.  Round 5 states the
-// same rule per size CLASS of a ragged call: with t(nb) the one-workgroup cost model (wg_cost) and S the summed cost of the entries not
-// yet given to the look-ahead schedule, a class (largest first) takes the look-ahead schedule when  t(nb_max) * #CU * f >= S  (f = 7/16
-// or 9/16 as above) -- i.e. when one of its entries on one workgroup would stick out of the average load per CU of everything that is
-// left.  For a uniform call S = n t and the rule is the old one (n <= 112 / 144); in a ragged call the heavy tail is peeled off class by
-// class until the rest is balanced.
-// routes of the classes of a plan (the rule above); returns the look-ahead scratch entries, la_of[i] = index into them or -1
-void choose_routes(const medgp_ctx *c, BatchPlan &P, std::vector<LaNeed> &las, std::vector<int> &la_of) {
-    long long S = 0;
-    for (const SizeClass &k : P.cls) S += k.tsum;
-    las.clear();
-    la_of.assign(P.cls.size(), -1);
-    for (size_t i = 0; i < P.cls.size(); i++) {
-        SizeClass &k = P.cls[i];
-        bool la = false;
-        if (!c->use_v0 && !c->pin_route && k.nbmax >= 2) {
-            if (c->force_mc > 0) la = true;   // (forced, A-B and tests: also for two blocks)
-            else if (c->force_mc == 0 && k.nbmax >= 3 && !c->no_classes) la = wg_cost(k.nbmax) * c->num_cu * (k.nbmax <= 4 ? 7 : 9) >= 16 * S;
-            else if (c->force_mc == 0 && k.nbmax >= 3) la = k.count <= (c->num_cu * (k.nbmax <= 4 ? 7 : 9)) / 16;   // rounds 1-4: by entry count alone
-        }
-        if (la) {
-            k.route = ROUTE_LA;
-            S -= k.tsum;
-            la_of[i] = (int)las.size();
-            las.push_back({k.count, k.nbmax, k.ld, LaArgs{}});
-        } else {
-            // more patients than CUs: 4-wave workgroups, two per CU (the serial diagonal phase of one overlaps the MFMA phase of the
-            // other).  At most one patient per CU: 8 waves (8 block slots per pass) once a step has more than 4 row blocks, else the
-            // 4-wave shape, whose 4 slots already cover every block of n <= 256 (measured, 256 patients x N=256, D=2: <4,4> 0.211 ms,
-            // <8,4> 0.232 ms -- half of its 8 slots idle).
-            const int shape = c->pin_route ? 84 : (c->cholinv_nw ? c->cholinv_nw : ((k.count > c->num_cu || k.nbmax <= 4) ? 44 : 84));
-            k.route = shape == 44 ? ROUTE_WG44 : ROUTE_WG84;
-        }
-    }
-}
-
-// what a plan needs of the look-ahead scratch arenas (doubles): the largest wave
-void la_needs(const BatchPlan &P, const std::vector<LaNeed> &las, const std::vector<int> &la_of, size_t *part, size_t *small) {
-    std::vector<size_t> wp(P.nwaves, 0), ws(P.nwaves, 0);
-    for (size_t i = 0; i < P.cls.size(); i++)
-        if (la_of[i] >= 0) { wp[P.cls[i].wave] += la_part_doubles(las[la_of[i]], P.with_u); ws[P.cls[i].wave] += la_small_doubles(las[la_of[i]]); }
-    *part = *small = 0;
-    for (int w = 0; w < P.nwaves; w++) { *part = std::max(*part, wp[w]); *small = std::max(*small, ws[w]); }
-}
-
-// End of the medgp_screen chunk that starts at entry e0 of the walk: entry e = (patient e / ninit of the walk, vector e % ninit); ns =
-// the patients' sizes in walk order (largest first).  A chunk holds at most max_batch entries and at most screen_budget bytes of
-// Gram matrices (8 ld^2 per entry: an nlml-only evaluation never forms U; ld taken at the upper end of the entry's size bucket, which
-// bounds the leading dimension of whatever class it lands in).  Entries of >= 45 blocks (64 MB of matrix each) take the look-ahead
-// schedule in any chunk this rule forms, and that schedule gains little beyond ~ 32 k block pairs per launch (measured on the four
-// largest patients of the heavy-tailed cohort, N = 3258 .. 5832, 200 vectors each: 1234 / 1073 / 799 / 679 / 665 ms for chunks
-// closed at 4 / 8 / 16 / 32 / 64 k block pairs, scratch/screen_work_sweep.sh): such a chunk is closed there or by the byte budget --
-// N = 5832: 3 entries = 0.83 GB of matrices + 0.42 GB of scratch per chunk where round 5 took 32 entries = 26 GB + 9 GB (obtaining
-// that much memory can cost seconds, see struct Arena).  The budget (2 GB) still gives every size its efficient route: 1024 entries of N <= 512 (one workgroup each, two per
-// CU), 256 of N <= 1024 (one per CU), 64 of N <= 2048 (look-ahead schedule, saturated from 16 on).
-size_t screen_chunk_end(const medgp_ctx *c, const std::vector<int> &ns, int ninit, size_t e0, size_t total, int max_entries) {
-    size_t e = e0, bytes = 0;
-    long long work = 0;
-    while (e < total && (int)(e - e0) < max_entries) {
-        const int nb = blocks64(ns[e / ninit]);
-        const size_t ldb = (size_t)64 << size_bucket(nb), per = 8 * ldb * ldb;
-        if (e > e0 && bytes + per > c->screen_budget) break;
-        if (e > e0 && nb >= 45 && work >= c->screen_work) break;
-        bytes += per; work += (long long)nb * nb; e++;
-    }
-    return e;
-}
-
-// How medgp_screen cuts `total` = walk_n.size() * ninit entries into chunks, whether it runs them on two lanes, and what ONE lane needs of
-// every arena (doubles; the largest chunk, laid out once per distinct composition).  Shared with medgp_reserve_plan.
-struct ScreenChunk { size_t e0, e1; };
-struct ScreenCut {
-    std::vector<ScreenChunk> chunks;
-    bool two = false;
-    int lane_rows = 0;
-    size_t cap_mat = 0, cap_vec = 0, cap_tab = 0, cap_part = 0, cap_small = 0;
-};
-void screen_cut(const medgp_ctx *c, const std::vector<int> &walk_n, int ninit, ScreenCut &S) {
-    const size_t total = walk_n.size() * (size_t)ninit;
-    S.two = c->screen_lanes >= 2 && c->max_batch >= 2 && screen_chunk_end(c, walk_n, ninit, 0, total, c->max_batch) < total;
-    S.lane_rows = S.two ? c->max_batch / 2 : c->max_batch;   // a lane's rows of the batch-indexed buffers = its chunks' entry cap
-    S.chunks.clear();
-    for (size_t e0 = 0; e0 < total;) { const size_t e = screen_chunk_end(c, walk_n, ninit, e0, total, S.lane_rows); S.chunks.push_back({e0, e}); e0 = e; }
-    BatchPlan P;
-    std::vector<LaNeed> las;
-    std::vector<int> la_of, en;
-    int lf = -1, ll = -1;
-    size_t lc = 0;
-    for (const ScreenChunk &ch : S.chunks) {
-        const int nf = walk_n[ch.e0 / ninit], nl = walk_n[(ch.e1 - 1) / ninit];
-        if (nf == nl && nf == lf && nl == ll && ch.e1 - ch.e0 == lc) continue;   // (runs of identical chunks: laid out once)
-        en.resize(ch.e1 - ch.e0);
-        for (size_t x = ch.e0; x < ch.e1; x++) en[x - ch.e0] = walk_n[x / ninit];
-        layout_plan(c, en.data(), (int)en.size(), false, P);
-        choose_routes(c, P, las, la_of);
-        size_t lp = 0, ls = 0;
-        la_needs(P, las, la_of, &lp, &ls);
-        S.cap_mat = std::max(S.cap_mat, P.need_mat); S.cap_vec = std::max(S.cap_vec, P.need_vec); S.cap_tab = std::max(S.cap_tab, P.need_tab);
-        S.cap_part = std::max(S.cap_part, lp); S.cap_small = std::max(S.cap_small, ls);
-        lf = nf; ll = nl; lc = ch.e1 - ch.e0;
-    }
-}
-
+// patient launches of the small classes fill the CUs a look-ahead chain of the large ones leaves idle.  The plan it carries out --
+// classes, waves, offsets, routes, look-ahead scratch -- is call_plan.h's (layout_plan in set_batch, plan_needs here).
 // persist: the caller reads per-entry buffers of ALL entries after the call (factor exports, k_predict): such a call must fit one wave.
 // Pp / st_main / aux0, naux: the plan to run, the stream its first class runs on and the auxiliary streams its other classes may use --
 // the context's own (c->plan, c->stream, all of c->aux) unless medgp_screen runs two plans at once on two lanes.
-int run_pipeline(medgp_ctx *c, int nbatch, int max_n, const double *theta_dev, int flag_grad, bool need_inverse, int min_n,
+int run_pipeline(medgp_ctx *c, const double *theta_dev, int flag_grad, bool need_inverse, int min_n,
                  double *nlml_dev, double *grad_dev, int32_t *status_dev, bool store_ukk = false, bool persist = false,
                  BatchPlan *Pp = nullptr, hipStream_t st_main = nullptr, int aux0 = 0, int naux = kAuxStreams, hipEvent_t ev_fork_in = nullptr) {
-    (void)max_n; (void)nbatch;
     BatchPlan &P = Pp ? *Pp : c->plan;
     if (!st_main) st_main = c->stream;
     hipEvent_t ev_fork = ev_fork_in ? ev_fork_in : c->ev_fork;
@@ -936,12 +707,12 @@ int run_pipeline(medgp_ctx *c, int nbatch, int max_n, const double *theta_dev, i
     if (forms_u && !P.with_u) return fail(c, MEDGP_ERR_ARG, "internal: plan laid out without Linv for a call that forms it");
     if (persist && P.nwaves > 1)
         return fail(c, MEDGP_ERR_CAPACITY, "the call's per-entry matrices exceed the memory budget of %zu GB (MEDGP_MEM_BUDGET_GB) and its outputs need all of them at once: split the call",
-                    c->mem_budget >> 30);
-    { int rc = ensure_arena(c, P.mat0 + P.need_mat, P.with_u ? P.mat0 + P.need_mat : 0, P.vec0 + P.need_vec, P.tab0 + P.need_tab, P.need_slab); if (rc) return rc; }
-    c->last_has_inverse = (flag_grad || need_inverse) && P.nwaves == 1;
+                    c->rules.mem_budget >> 30);
     std::vector<LaNeed> las;
     std::vector<int> la_of;
-    choose_routes(c, P, las, la_of);
+    const PlanNeeds nd = plan_needs(c->rules, P, las, la_of);   // (chooses the routes of the classes; the look-ahead arenas grow wave by wave below)
+    { int rc = ensure_arena(c, P.mat0 + nd.mat, P.with_u ? P.mat0 + nd.mat : 0, P.vec0 + nd.vec, P.tab0 + nd.tab, nd.slab); if (rc) return rc; }
+    c->last_has_inverse = (flag_grad || need_inverse) && P.nwaves == 1;
     const int nstr = std::max(0, std::min(c->class_streams, naux));
     for (int w = 0; w < P.nwaves; w++) {
         // this wave's classes [i0, i1) and their look-ahead scratch
@@ -952,7 +723,8 @@ int run_pipeline(medgp_ctx *c, int nbatch, int max_n, const double *theta_dev, i
         std::vector<LaNeed> wl;
         std::vector<int> wl_of(P.cls.size(), -1);
         for (size_t i = i0; i < i1; i++) if (la_of[i] >= 0) { wl_of[i] = (int)wl.size(); wl.push_back(las[la_of[i]]); }
-        if (!wl.empty()) { int rc = ensure_la(c, wl, P.with_u, P.la_part0, P.la_small0); if (rc) return rc; }
+        std::vector<LaArgs> wa;
+        if (!wl.empty()) { int rc = ensure_la(c, wl, P.with_u, wa, P.la_part0, P.la_small0); if (rc) return rc; }
         const bool fork = i1 - i0 > 1 && nstr > 0 && c->aux[aux0];
         if (fork) HIPCHK(c, hipEventRecord(ev_fork, st_main));
         bool used[kAuxStreams] = {false, false, false, false};
@@ -967,7 +739,7 @@ int run_pipeline(medgp_ctx *c, int nbatch, int max_n, const double *theta_dev, i
             }
             const MedgpDev V = class_view(c, P, k);
             int rc = run_pipeline_one(c, st, V, k.count, k.nbmax, theta_dev, flag_grad, need_inverse, min_n, nlml_dev, grad_dev, status_dev, store_ukk,
-                                      P.en.data() + k.b0, k.route, wl_of[i] >= 0 ? &wl[wl_of[i]].A : nullptr);
+                                      P.en.data() + k.b0, k.route, wl_of[i] >= 0 ? &wa[wl_of[i]] : nullptr);
             if (rc) return rc;
         }
         if (fork)
@@ -984,7 +756,7 @@ int run_pipeline(medgp_ctx *c, int nbatch, int max_n, const double *theta_dev, i
 // the context is reserved, the batch fits it and every slot holds a patient
 int check_call(medgp_ctx *c, int nbatch, const int32_t *slots) {
     if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
-    if (nbatch < 1 || nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
+    if (nbatch < 1 || nbatch > c->rules.max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->rules.max_batch);
     for (int b = 0; b < nbatch; b++)
         if (slots[b] < 0 || slots[b] >= c->max_slots || c->h_n[slots[b]] < 0) return fail(c, MEDGP_ERR_ARG, "slots[%d] = %d is not a resident patient", b, slots[b]);
     return MEDGP_OK;
@@ -1012,7 +784,7 @@ int stage_points(medgp_ctx *c, int64_t M, const int32_t *meta2, const float *t2,
         const int64_t j = src ? src[k] : k;
         ht2[k] = (double)t2[j];
         if (meta2 && c->kidx == MEDGP_KERNEL_LMC_SM) {
-            if (meta2[j] < 0 || meta2[j] >= c->D) return fail(c, MEDGP_ERR_ARG, "meta2[%lld] = %d outside [0, %d)", (long long)j, meta2[j], c->D);
+            if (meta2[j] < 0 || meta2[j] >= c->rules.D) return fail(c, MEDGP_ERR_ARG, "meta2[%lld] = %d outside [0, %d)", (long long)j, meta2[j], c->rules.D);
             hm2[k] = meta2[j];
         }
     }
@@ -1022,9 +794,9 @@ int stage_points(medgp_ctx *c, int64_t M, const int32_t *meta2, const float *t2,
 // theta to the device and the ONE pipeline run of an inference call: factor and z = L^-1 y of every entry, with U = L^-T and
 // alpha = K^-1 y (need_inverse: medgp_get_factor is valid afterwards) or the diagonal-block inverses U_kk (store_ukk).  The call reads
 // per-entry buffers of all entries afterwards: it must fit one memory wave.
-int factor_run(medgp_ctx *c, int nbatch, int max_n, const double *theta, bool need_inverse, bool store_ukk) {
+int factor_run(medgp_ctx *c, int nbatch, const double *theta, bool need_inverse, bool store_ukk) {
     HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
-    return run_pipeline(c, nbatch, max_n, c->d_theta, 0, need_inverse, 1, nullptr, nullptr, nullptr, store_ukk, true);
+    return run_pipeline(c, c->d_theta, 0, need_inverse, 1, nullptr, nullptr, nullptr, store_ukk, true);
 }
 
 // The end of a blocking call: the status words of its entries are read back behind whatever the caller has queued, the stream is
@@ -1099,7 +871,7 @@ int medgp_create(medgp_ctx **out, int device, int kernel_index, int Q, int D, in
     if (device < 0 || device >= ndev) return fail(nullptr, MEDGP_ERR_ARG, "device %d outside [0, %d)", device, ndev);
     medgp_ctx *c = new medgp_ctx();
     c->device = device;
-    c->kidx = kernel_index; c->Q = Q; c->D = D; c->R = R;
+    c->kidx = kernel_index; c->rules.Q = Q; c->rules.D = D; c->R = R;
     c->nlik = (kernel_index == MEDGP_KERNEL_LMC_SM) ? D : 1;
     c->H = c->nlik + nc;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
@@ -1107,19 +879,19 @@ int medgp_create(medgp_ctx **out, int device, int kernel_index, int Q, int D, in
         return fail(nullptr, MEDGP_ERR_HIP, "cannot initialise device %d", device);
     }
     c->stream = c->own_stream;
-    { const char *e = getenv("MEDGP_CHOLINV_NW"); c->cholinv_nw = e ? atoi(e) : 0; }
+    { const char *e = getenv("MEDGP_CHOLINV_NW"); c->rules.cholinv_nw = e ? atoi(e) : 0; }
     { const char *e = getenv("MEDGP_LA_PARK"); if (e) c->la_park = atoi(e); }
     { const char *e = getenv("MEDGP_LA_PARK_MAXBATCH"); if (e) c->la_park_maxbatch = atoi(e); }
-    { const char *e = getenv("MEDGP_MULTI_CU"); c->force_mc = e ? atoi(e) : 0; }
+    { const char *e = getenv("MEDGP_MULTI_CU"); c->rules.force_mc = e ? atoi(e) : 0; }
     { const char *e = getenv("MEDGP_CLASS_STREAMS"); if (e) c->class_streams = std::max(0, std::min(kAuxStreams, atoi(e))); }
-    { const char *e = getenv("MEDGP_NO_CLASSES"); c->no_classes = e ? atoi(e) : 0; }
+    { const char *e = getenv("MEDGP_NO_CLASSES"); c->rules.no_classes = e ? atoi(e) : 0; }
     { const char *e = getenv("MEDGP_WGRAD_DEEP"); c->wgrad_deep = e ? std::max(1, atoi(e)) : -1; }
     { const char *e = getenv("MEDGP_DEBUG_FAIL_ATTEMPTS"); c->dbg_fail = e ? atoi(e) : 0; }
-    { const char *e = getenv("MEDGP_V0"); c->use_v0 = e && e[0] == '1'; }
-    { const char *e = getenv("MEDGP_MEM_BUDGET_GB"); if (e && atof(e) > 0) c->mem_budget = (size_t)(atof(e) * 1073741824.0); }
-    { const char *e = getenv("MEDGP_SCREEN_LANES"); if (e && atoi(e) >= 1) c->screen_lanes = std::min(2, atoi(e)); }
-    { const char *e = getenv("MEDGP_SCREEN_WORK"); if (e && atoll(e) > 0) c->screen_work = atoll(e); }
-    { const char *e = getenv("MEDGP_SCREEN_BUDGET_GB"); if (e && atof(e) > 0) c->screen_budget = (size_t)(atof(e) * 1073741824.0); }
+    { const char *e = getenv("MEDGP_V0"); c->rules.use_v0 = e && e[0] == '1'; }
+    { const char *e = getenv("MEDGP_MEM_BUDGET_GB"); if (e && atof(e) > 0) c->rules.mem_budget = (size_t)(atof(e) * 1073741824.0); }
+    { const char *e = getenv("MEDGP_SCREEN_LANES"); if (e && atoi(e) >= 1) c->rules.screen_lanes = std::min(2, atoi(e)); }
+    { const char *e = getenv("MEDGP_SCREEN_WORK"); if (e && atoll(e) > 0) c->rules.screen_work = atoll(e); }
+    { const char *e = getenv("MEDGP_SCREEN_BUDGET_GB"); if (e && atof(e) > 0) c->rules.screen_budget = (size_t)(atof(e) * 1073741824.0); }
     { const char *e = getenv("MEDGP_POSTERIOR_BUDGET_GB"); if (e && atof(e) > 0) c->posterior_budget = (size_t)(atof(e) * 1073741824.0); }
     for (int i = 0; i < kAuxStreams; i++) {
         (void)hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking);
@@ -1128,7 +900,7 @@ int medgp_create(medgp_ctx **out, int device, int kernel_index, int Q, int D, in
     (void)hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
     (void)hipStreamCreateWithFlags(&c->s_screen1, hipStreamNonBlocking);
     for (hipEvent_t *e : {&c->ev_fork1, &c->ev_screen0}) (void)hipEventCreateWithFlags(e, hipEventDisableTiming);
-    { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess) c->num_cu = pr.multiProcessorCount; }
+    { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess) c->rules.num_cu = pr.multiProcessorCount; }
     *out = c;
     return MEDGP_OK;
 }
@@ -1196,12 +968,12 @@ int medgp_reserve(medgp_ctx *c, int max_slots, int max_n, int max_batch) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_all(c);
-    c->max_slots = max_slots; c->max_n = max_n; c->max_batch = max_batch;
+    c->max_slots = max_slots; c->max_n = max_n; c->rules.max_batch = max_batch;
     // leading dimension = padded n.  (Padding it off the power of two was measured: no effect -- the HBM channel hash
     // already spreads the 4096-byte row stride.)
     const int ldn = medgp_roundup(max_n, 64);
     c->ldn = ldn;
-    const size_t S = max_slots, B = max_batch, Q = c->Q, D = c->D, H = c->H;
+    const size_t S = max_slots, B = max_batch, Q = c->rules.Q, D = c->rules.D, H = c->H;
     int rc;
     // patient rows: [0, S) grouped by output (what the gradient kernels need); [S, 2S) the same patient in the CALLER's
     // observation order, filled only when that order is not already grouped (used for caller-order factors)
@@ -1233,7 +1005,7 @@ int medgp_reserve(medgp_ctx *c, int max_slots, int max_n, int max_batch) {
     c->lane_pending[0] = c->lane_pending[1] = false;
     c->d_prior_stage = nullptr; c->d_prior_slots = nullptr; c->prior_stage_rows = 0;   // freed by free_all above
     MedgpDev &L = c->dev;
-    L.kidx = c->kidx; L.Q = c->Q; L.D = c->D; L.R = c->R; L.H = c->H; L.nlik = c->nlik;
+    L.kidx = c->kidx; L.Q = c->rules.Q; L.D = c->rules.D; L.R = c->R; L.H = c->H; L.nlik = c->nlik;
     L.ldn = ldn; L.pld = ldn; L.max_slots = max_slots; L.max_batch = max_batch;
     L.bpos = nullptr;
     L.tpos = nullptr;
@@ -1241,16 +1013,15 @@ int medgp_reserve(medgp_ctx *c, int max_slots, int max_n, int max_batch) {
     L.pi = c->pi;
     L.dbg_fail = c->dbg_fail;
     double *hyp, *scal, *Sb, *SMb, *SVb;
-    L.slab_R = ldn / 16 + (int)D;
-    L.slab_C = ldn / 64 + (int)D;
-    L.slab_stride = (size_t)3 * Q * L.slab_R * L.slab_C;
+    const SlabGeom sg = slab_geom(ldn, c->rules.Q, c->rules.D);
+    L.slab_R = sg.R; L.slab_C = sg.C; L.slab_stride = sg.stride;
     c->full_mat = B * ldn * ldn; c->full_vec = B * ldn; c->full_tab = B * Q * ldn; c->full_slab = B * L.slab_stride;
     L.Kmat = L.Linv = L.z = L.alpha = L.wdiag = L.cs = L.sn = L.slab = nullptr;
     {   // a wave of a call never uses more than the budget, and the budget never more than 70 % of what the device has free now
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > 0) {
-            c->mem_budget = std::min(c->mem_budget, fr / 10 * 7);
-            c->screen_budget = std::min(c->screen_budget, c->mem_budget);
+            c->rules.mem_budget = std::min(c->rules.mem_budget, fr / 10 * 7);
+            c->rules.screen_budget = std::min(c->rules.screen_budget, c->rules.mem_budget);
         }
     }
     // every configuration whose capacities stay below 8 GB of matrices (all of BASELINE.json's) is allocated in full here; beyond that
@@ -1301,33 +1072,23 @@ int medgp_reserve_plan(medgp_ctx *c, int count, const int32_t *n, int ninit) {
     // largest first, as medgp_screen walks them and as the lock-step trainer admits them
     std::vector<int> ns(n, n + count);
     std::stable_sort(ns.begin(), ns.end(), [](int a, int b) { return a > b; });
-    size_t nk = 0, nu = 0, nvec = 0, ntab = 0, nslab = 0, npart = 0, nsmall = 0;
     BatchPlan P;
     std::vector<LaNeed> las;
     std::vector<int> la_of;
-    auto take = [&](const int *en, int nb, bool with_u) {
-        layout_plan(c, en, nb, with_u, P);
-        choose_routes(c, P, las, la_of);
-        size_t lp = 0, ls = 0;
-        la_needs(P, las, la_of, &lp, &ls);
-        nk = std::max(nk, P.need_mat); if (with_u) nu = std::max(nu, P.need_mat);
-        nvec = std::max(nvec, P.need_vec); ntab = std::max(ntab, P.need_tab); nslab = std::max(nslab, P.need_slab);
-        npart = std::max(npart, lp); nsmall = std::max(nsmall, ls);
-    };
     // (a) one nlml + gradient call over the announced patients (the largest max_batch of them)
-    take(ns.data(), std::min(count, c->max_batch), true);
+    layout_plan(c->rules, ns.data(), std::min(count, c->rules.max_batch), true, P);
+    PlanNeeds nd = plan_needs(c->rules, P, las, la_of);
+    const size_t nu = nd.mat;   // (Linv: the screening chunks below are nlml-only plans and never touch it)
     // (b) the chunks medgp_screen forms of them (two lanes: twice the largest chunk)
     if (ninit > 0) {
         ScreenCut SC;
-        screen_cut(c, ns, ninit, SC);
-        const size_t f = SC.two ? 2 : 1;
-        nk = std::max(nk, f * SC.cap_mat); nvec = std::max(nvec, f * SC.cap_vec); ntab = std::max(ntab, f * SC.cap_tab);
-        npart = std::max(npart, f * SC.cap_part); nsmall = std::max(nsmall, f * SC.cap_small);
+        screen_cut(c->rules, ns, ninit, SC);
+        nd.raise(PlanNeeds{SC.cap_mat, SC.cap_vec, SC.cap_tab, 0, SC.cap_part, SC.cap_small}, SC.two ? 2 : 1);
     }
     int rc;
-    if ((rc = ensure_arena(c, nk, nu, nvec, ntab, nslab, true))) return rc;
-    if (npart && (rc = arena_ensure(c, AR_LA_PART, npart * sizeof(double), 0, true, nullptr))) return rc;
-    if (nsmall && (rc = arena_ensure(c, AR_LA_SMALL, nsmall * sizeof(double), 0, true, nullptr))) return rc;
+    if ((rc = ensure_arena(c, nd.mat, nu, nd.vec, nd.tab, nd.slab, true))) return rc;
+    if (nd.la_part && (rc = arena_ensure(c, AR_LA_PART, nd.la_part * sizeof(double), 0, true, nullptr))) return rc;
+    if (nd.la_small && (rc = arena_ensure(c, AR_LA_SMALL, nd.la_small * sizeof(double), 0, true, nullptr))) return rc;
     // a set-up call: wait for the context's streams once and give the replaced blocks back now, so that the loop that follows starts with
     // nothing left to release
     if (!c->retired.empty()) { if ((rc = sync_ctx_streams(c))) return rc; free_retired(c); }
@@ -1351,7 +1112,7 @@ struct UpEntry { int slot, n; const int32_t *meta; const float *t, *y; };
 inline size_t up_payload_bytes(int n, int D) { return ((size_t)n * 20 + (size_t)(D + 1) * 12 + 7) & ~(size_t)7; }
 
 int upload_patients(medgp_ctx *c, const std::vector<UpEntry> &ents) {
-    const int D = c->D, S = c->max_slots, ldn = c->ldn;
+    const int D = c->rules.D, S = c->max_slots, ldn = c->ldn;
     const bool use_meta = (c->kidx == MEDGP_KERNEL_LMC_SM);
     // validate everything before touching any state
     std::vector<uint8_t> seen(ents.size() > 1 ? (size_t)S : 0, 0);
@@ -1560,11 +1321,11 @@ int medgp_nlml_grad_device(medgp_ctx *c, int nbatch, const int32_t *slots, const
     if (grad && !grad_dev) return fail(c, MEDGP_ERR_ARG, "grad is NULL with flag_grad set");
     if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
     HIPCHK(c, hipSetDevice(c->device));
-    int max_n = 0, rc;
+    int rc;
     // factor wanted but no gradient: patients that were not uploaded grouped by output are evaluated in the CALLER's order,
     // so that L^-1 is the factor the reference would hand to GP_Regression::predict (ref: core/gp_regression.cpp:181-196)
-    if ((rc = set_batch(c, nbatch, slots, &max_n, keep && !grad, grad || keep))) return rc;
-    return run_pipeline(c, nbatch, max_n, theta_dev, grad, keep, 3, nlml_dev, grad_dev, status_dev, false, keep);
+    if ((rc = set_batch(c, nbatch, slots, keep && !grad, grad || keep))) return rc;
+    return run_pipeline(c, theta_dev, grad, keep, 3, nlml_dev, grad_dev, status_dev, false, keep);
 }
 
 int medgp_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int flag_grad, double *nlml,
@@ -1573,7 +1334,7 @@ int medgp_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     if (!slots || !theta || !nlml) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if ((flag_grad & MEDGP_FLAG_GRAD) && !grad) return fail(c, MEDGP_ERR_ARG, "grad is NULL with flag_grad set");
     if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
-    if (nbatch < 1 || nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
+    if (nbatch < 1 || nbatch > c->rules.max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->rules.max_batch);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t H = c->H;
     const bool want_grad = (flag_grad & MEDGP_FLAG_GRAD) != 0;
@@ -1666,7 +1427,7 @@ int medgp_screen(medgp_ctx *c, int nslots, const int32_t *slots, int ninit, cons
     // screening the same patient at once: 2.24 against 2.48 ms per 1000 evaluations at N = 512 (scratch/screen_two_ctx.py).  A chunk of a
     // two-lane call holds at most max_batch / 2 entries (its rows of the buffers).
     ScreenCut SC;
-    screen_cut(c, walk_n, ninit, SC);
+    screen_cut(c->rules, walk_n, ninit, SC);
     const bool two = SC.two;
     const std::vector<ScreenChunk> &chunks = SC.chunks;
     const int lane_rows = SC.lane_rows;
@@ -1702,8 +1463,7 @@ int medgp_screen(medgp_ctx *c, int nslots, const int32_t *slots, int ninit, cons
         for (size_t x = e0; x < e1; x++) { cs.push_back(slots[perm[x / ninit]]); tp.push_back((int)(x % ninit)); }
         hipError_t he = hipSuccess;
         if (!two) {
-            int max_n = 0;
-            if ((rc = set_batch(c, nb, cs.data(), &max_n, false, false))) break;
+            if ((rc = set_batch(c, nb, cs.data(), false, false))) break;
             {   // theta rows in the plan's internal order
                 void *pin = nullptr;
                 if ((rc = pin_stage(c, sizeof(int) * nb, &pin))) break;
@@ -1712,7 +1472,7 @@ int medgp_screen(medgp_ctx *c, int nslots, const int32_t *slots, int ninit, cons
                 he = hipMemcpyAsync(c->d_tpos, hp, sizeof(int) * nb, hipMemcpyHostToDevice, c->stream);
                 if (he != hipSuccess) { rc = fail(c, MEDGP_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(he)); break; }
             }
-            if ((rc = run_pipeline(c, nb, max_n, c->d_screen_theta, 0, false, 3, c->d_nlml, nullptr, c->d_status_out))) break;
+            if ((rc = run_pipeline(c, c->d_screen_theta, 0, false, 3, c->d_nlml, nullptr, c->d_status_out))) break;
             he = hipMemcpyAsync(hn + e0, c->d_nlml, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream);
             if (he == hipSuccess) he = hipMemcpyAsync(hs + e0, c->d_status_out, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, c->stream);
         } else {
@@ -1721,7 +1481,7 @@ int medgp_screen(medgp_ctx *c, int nslots, const int32_t *slots, int ninit, cons
             BatchPlan &P = lane_plan[lane];
             en.resize(nb);
             for (int i = 0; i < nb; i++) en[i] = c->h_n[cs[i]];
-            layout_plan(c, en.data(), nb, false, P);
+            layout_plan(c->rules, en.data(), nb, false, P);
             P.row0 = lane * lane_rows;
             P.mat0 = lane * cap_mat; P.vec0 = lane * cap_vec; P.tab0 = lane * cap_tab; P.la_part0 = lane * cap_part; P.la_small0 = lane * cap_small;
             int *hb = (int *)c->h_screen_tab + 3 * e0, *hpz = hb + nb, *ht = hpz + nb;
@@ -1730,7 +1490,7 @@ int medgp_screen(medgp_ctx *c, int nslots, const int32_t *slots, int ninit, cons
             if (he == hipSuccess) he = hipMemcpyAsync(c->d_bpos + P.row0, hpz, sizeof(int) * nb, hipMemcpyHostToDevice, st);
             if (he == hipSuccess) he = hipMemcpyAsync(c->d_tpos + P.row0, ht, sizeof(int) * nb, hipMemcpyHostToDevice, st);
             if (he != hipSuccess) { rc = fail(c, MEDGP_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(he)); break; }
-            if ((rc = run_pipeline(c, nb, 0, c->d_screen_theta, 0, false, 3, c->d_nlml + P.row0, nullptr, c->d_status_out + P.row0, false, false,
+            if ((rc = run_pipeline(c, c->d_screen_theta, 0, false, 3, c->d_nlml + P.row0, nullptr, c->d_status_out + P.row0, false, false,
                                    &P, st, lane * (kAuxStreams / 2), kAuxStreams / 2, lane ? c->ev_fork1 : c->ev_fork))) break;
             he = hipMemcpyAsync(hn + e0, c->d_nlml + P.row0, sizeof(double) * nb, hipMemcpyDeviceToHost, st);
             if (he == hipSuccess) he = hipMemcpyAsync(hs + e0, c->d_status_out + P.row0, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st);
@@ -1768,7 +1528,7 @@ int medgp_nlml_grad_async(medgp_ctx *c, int lane, int nbatch, const int32_t *slo
     if (!slots || !theta || !nlml) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if ((flag_grad & MEDGP_FLAG_GRAD) && !grad) return fail(c, MEDGP_ERR_ARG, "grad is NULL with flag_grad set");
     if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
-    if (nbatch < 1 || nbatch > c->max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->max_batch);
+    if (nbatch < 1 || nbatch > c->rules.max_batch) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d outside [1, %d]", nbatch, c->rules.max_batch);
     if (c->lane_pending[lane]) return fail(c, MEDGP_ERR_ARG, "lane %d still holds a call: medgp_wait it first", lane);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t H = c->H;
@@ -1834,13 +1594,20 @@ int medgp_get_factor(medgp_ctx *c, int b, float *alpha, float *linv, float *beta
         V.bpos = nullptr;
         const bool prof = c->profiling;
         c->profiling = false;   // not part of the evaluation being measured
-        // (one entry: the route rule of run_pipeline for a uniform call of one)
-        const int nb1 = blocks64(n);
-        const bool la1 = !c->use_v0 && !c->pin_route && nb1 >= 2 && (c->force_mc > 0 || (c->force_mc == 0 && nb1 >= 3));
+        // its route: that of a call of this one entry (choose_routes on a one-entry plan)
+        BatchPlan P1;
         std::vector<LaNeed> las;
-        if (la1) { las.push_back({1, nb1, ld, LaArgs{}}); int rcl = ensure_la(c, las, true); if (rcl) return rcl; }
-        const int route1 = la1 ? ROUTE_LA : (c->pin_route ? ROUTE_WG84 : (c->cholinv_nw ? (c->cholinv_nw == 44 ? ROUTE_WG44 : ROUTE_WG84) : (nb1 <= 4 ? ROUTE_WG44 : ROUTE_WG84)));
-        int rc = run_pipeline_one(c, c->stream, V, 1, nb1, nullptr, 0, true, 1, nullptr, nullptr, nullptr, false, &n, route1, la1 ? &las[0].A : nullptr);
+        std::vector<int> la_of;
+        std::vector<LaArgs> la;
+        layout_plan(c->rules, &n, 1, true, P1);
+        choose_routes(c->rules, P1, las, la_of);
+        if (!las.empty()) {
+            las[0].ld = ld;   // (the entry keeps the view of its class in the last call: the Y row block has that leading dimension)
+            int rcl = ensure_la(c, las, true, la);
+            if (rcl) return rcl;
+        }
+        const SizeClass &k1 = P1.cls[0];
+        int rc = run_pipeline_one(c, c->stream, V, 1, k1.nbmax, nullptr, 0, true, 1, nullptr, nullptr, nullptr, false, &n, k1.route, la.empty() ? nullptr : &la[0]);
         c->profiling = prof;
         if (rc) return rc;
         HIPCHK(c, hipMemcpyAsync((int *)E.bslot, c->d_one_slot, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
@@ -1877,7 +1644,7 @@ static int fit_predict_impl(medgp_ctx *c, int nbatch, const int32_t *slots, cons
                             const int32_t *meta2, const float *t2, float *mean, float *var, int32_t *status) {
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !t2 || !mean || !var || nstar < 1 || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
-    int max_n = 0, rc;
+    int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     if (c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
     HIPCHK(c, hipSetDevice(c->device));
@@ -1892,11 +1659,11 @@ static int fit_predict_impl(medgp_ctx *c, int nbatch, const int32_t *slots, cons
     if ((rc = buf_ensure(c, BUF_WORK, (size_t)ntot * c->ldn * sizeof(double)))) return rc;   // k* -> v = L^-1 k* work rows
     // patients are used in the caller's order when that differs from the grouped one?  No: mean / var are permutation
     // invariant, the grouped copy serves.
-    if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;   // (the diagonal blocks U_kk live in Linv)
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;   // (the diagonal blocks U_kk live in Linv)
     HIPCHK(c, hipMemcpyAsync(buf<double>(c, BUF_T2), ht2.data(), sizeof(double) * ntot, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(buf<int>(c, BUF_META2), hm2.data(), sizeof(int) * ntot, hipMemcpyHostToDevice, c->stream));
     // factor + z = L^-1 y only (no inverse): k* rides along as one more right-hand side in k_predict
-    if ((rc = factor_run(c, nbatch, max_n, theta, false, true))) return rc;
+    if ((rc = factor_run(c, nbatch, theta, false, true))) return rc;
     for (const SizeClass &k : c->plan.cls) {   // (behind the join of the classes' chains: one launch per class view)
         Launcher l(c, KID_PREDICT);
         hipLaunchKernelGGL(k_predict, dim3(nstar, k.count), dim3(256), 0, c->stream, class_view(c, c->plan, k), nstar, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2),
@@ -1914,9 +1681,9 @@ int medgp_factor_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const dou
     if (!slots || !theta || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
     if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
     HIPCHK(c, hipSetDevice(c->device));
-    int max_n = 0, rc;
-    if ((rc = set_batch(c, nbatch, slots, &max_n, true, false))) return rc;       // the CALLER's observation order; size classes; L and z only: no Linv
-    if ((rc = factor_run(c, nbatch, max_n, theta, false, false))) return rc;
+    int rc;
+    if ((rc = set_batch(c, nbatch, slots, true, false))) return rc;       // the CALLER's observation order; size classes; L and z only: no Linv
+    if ((rc = factor_run(c, nbatch, theta, false, false))) return rc;
     std::vector<int32_t> st(nbatch, 0);
     if ((rc = read_status(c, nbatch, st.data()))) return rc;
     if (status) for (int b = 0; b < nbatch; b++) status[b] = st[b];
@@ -1976,7 +1743,7 @@ int medgp_factor(medgp_ctx *c, int slot, const double *theta, double *Lout, doub
 
 int medgp_pin_route(medgp_ctx *c, int pinned) {
     if (!c) return MEDGP_ERR_ARG;
-    c->pin_route = pinned ? 1 : 0;
+    c->rules.pin_route = pinned ? 1 : 0;
     return MEDGP_OK;
 }
 
@@ -2041,7 +1808,7 @@ int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
                    const int32_t *meta2, const float *t2, float *mean, float *var, float *parts, int32_t *status, const JointReq *jq) {
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
-    int max_n = 0, rc;
+    int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     if ((rc = check_points(c, nbatch, offsets, meta2, t2, mean, var))) return rc;
     const int64_t M = offsets[nbatch];
@@ -2052,7 +1819,7 @@ int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
         if (want_samp && M > 0 && (!jq->eps || !jq->samples)) return fail(c, MEDGP_ERR_ARG, "eps / samples is NULL with nsamp = %d", jq->nsamp);
         if (want_samp && M * (int64_t)jq->nsamp > (int64_t)INT32_MAX) return fail(c, MEDGP_ERR_ARG, "%lld x %d sample values in one call", (long long)M, jq->nsamp);
     }
-    const int D = c->D;
+    const int D = c->rules.D;
     std::vector<size_t> cov_off(want_cov ? nbatch : 0);   // start of patient b's block in cov (floats)
     if (want_cov) { size_t o = 0; for (int b = 0; b < nbatch; b++) { cov_off[b] = o; const size_t m = (size_t)(offsets[b + 1] - offsets[b]); o += m * m; } }
     std::vector<double> ht2;
@@ -2060,7 +1827,7 @@ int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     // the parts, like mean and var, are invariant under a permutation of the training observations: the grouped copy serves
-    if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const bool with_parts = parts != nullptr;
     const int parts_lds = D <= POST_PARTS_LDS_MAX_D;
     JointTables T;
@@ -2094,7 +1861,7 @@ int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
         }
     }
     // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
-    if ((rc = factor_run(c, nbatch, max_n, theta, false, true))) return rc;
+    if ((rc = factor_run(c, nbatch, theta, false, true))) return rc;
     if (with_parts && M > 0)
         for (const SizeClass &k : c->plan.cls) {   // (behind the join of the classes' chains)
             Launcher l(c, KID_ALPHA);
@@ -2151,7 +1918,7 @@ int forecast_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
     if ((y2 == nullptr) != (lpd == nullptr)) return fail(c, MEDGP_ERR_ARG, "y2 and lpd must both be given or both be NULL");
-    int max_n = 0, rc;
+    int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     if ((rc = check_points(c, nbatch, offsets, meta2, t2, mean, var))) return rc;
     const int64_t M = offsets[nbatch];
@@ -2175,7 +1942,7 @@ int forecast_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *
     for (int64_t k = 0; y2 && k < M; k++) hy2[k] = (double)y2[src[k]];
     HIPCHK(c, hipSetDevice(c->device));
     // "the first p observations" is the caller's order: a patient not uploaded grouped by output is factored on its caller-order copy
-    if ((rc = set_batch(c, nbatch, slots, &max_n, true, true))) return rc;
+    if ((rc = set_batch(c, nbatch, slots, true, true))) return rc;
     // tile table per size class and launch chunks within the budget, as the posterior call's -- and in its buffers
     static_assert(sizeof(ForeTile) == sizeof(PostTile), "the forecast tiles travel in the posterior call's tile buffer");
     PointTables<ForeTile> T;
@@ -2187,7 +1954,7 @@ int forecast_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *
     if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
     if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
     // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
-    if ((rc = factor_run(c, nbatch, max_n, theta, false, true))) return rc;
+    if ((rc = factor_run(c, nbatch, theta, false, true))) return rc;
     const double log2pi = std::log(2.0 * c->pi);
     for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
         Launcher l(c, KID_FORECAST);
@@ -2217,7 +1984,7 @@ int trend_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *the
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
     if (!dmean || !dvar) return fail(c, MEDGP_ERR_ARG, "dmean / dvar is NULL");
-    int max_n = 0, rc;
+    int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     if ((rc = check_points(c, nbatch, offsets, meta2, t2, mean, var))) return rc;
     const int64_t M = offsets[nbatch];
@@ -2227,7 +1994,7 @@ int trend_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *the
     if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     // the five outputs are invariant under a permutation of the training observations: the grouped copy serves, as for the posterior
-    if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     PointTables<PostTile> T;
     build_trend_tiles(table_classes(c->plan), c->plan.order.data(), offsets, c->posterior_budget, T);
     if ((rc = upload_points(c, M, ht2, hm2))) return rc;
@@ -2235,7 +2002,7 @@ int trend_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *the
     if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
     if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
     // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
-    if ((rc = factor_run(c, nbatch, max_n, theta, false, true))) return rc;
+    if ((rc = factor_run(c, nbatch, theta, false, true))) return rc;
     float *d_dmean = buf<float>(c, BUF_SLOPE), *d_dvar = d_dmean + Mz, *d_cross = d_dvar + Mz;
     for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
         Launcher l(c, KID_TREND);
@@ -2265,9 +2032,9 @@ int components_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
     if (!cmean || !cvar) return fail(c, MEDGP_ERR_ARG, "cmean / cvar is NULL");
-    const int Q = c->Q;
+    const int Q = c->rules.Q;
     if (Q > 64) return fail(c, MEDGP_ERR_ARG, "medgp_components_batch supports Q <= 64 (Q = %d): the component columns of a point share one 64-column tile", Q);
-    int max_n = 0, rc;
+    int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     if ((rc = check_points(c, nbatch, offsets, meta2, t2, cmean, cvar, "cmean / cvar"))) return rc;
     const int64_t M = offsets[nbatch];
@@ -2277,7 +2044,7 @@ int components_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     // the outputs are invariant under a permutation of the training observations: the grouped copy serves, as for the posterior
-    if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     PointTables<PostTile> T;
     build_components_tiles(table_classes(c->plan), c->plan.order.data(), offsets, Q, ccov != nullptr, c->posterior_budget, T);
     if ((rc = upload_points(c, M, ht2, hm2))) return rc;
@@ -2285,7 +2052,7 @@ int components_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
     if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
     // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
-    if ((rc = factor_run(c, nbatch, max_n, theta, false, true))) return rc;
+    if ((rc = factor_run(c, nbatch, theta, false, true))) return rc;
     float *d_cmean = buf<float>(c, BUF_COMP), *d_cvar = d_cmean + MQ, *d_ccov = d_cvar + MQ;
     for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
         Launcher l(c, KID_POSTERIOR);
@@ -2343,7 +2110,7 @@ int medgp_loo_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     if (!slots || !theta || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
     if (!mean && !var && !lpd && !total) return fail(c, MEDGP_ERR_ARG, "none of mean, var, lpd and total asked for");
     if (group && !ngroups) return fail(c, MEDGP_ERR_ARG, "ngroups is NULL with group ids");
-    int max_n = 0, rc;
+    int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     std::vector<int64_t> ooff(nbatch + 1, 0), goff(nbatch + 1, 0);   // first observation / first group of patient b in the call
     for (int b = 0; b < nbatch; b++) {
@@ -2359,7 +2126,7 @@ int medgp_loo_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double
                 if (group[i] < -1 || group[i] >= ngroups[b])
                     return fail(c, MEDGP_ERR_ARG, "group[%lld] = %d outside [-1, %d) (patient %d)", (long long)i, group[i], ngroups[b], b);
     HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const bool want_lpd = lpd || total;
     std::vector<const int *> perm(nbatch);   // internal row -> caller observation (null: the patient was uploaded grouped)
     for (int b = 0; b < nbatch; b++) perm[b] = c->h_perm_identity[slots[b]] ? nullptr : c->h_perm[slots[b]].data();
@@ -2392,7 +2159,7 @@ int medgp_loo_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     const JointPat *d_groups = buf<JointPat>(c, BUF_PATS);
     const JointTile *d_pairs = buf<JointTile>(c, BUF_PAIRS), *d_jobs = buf<JointTile>(c, BUF_BLKS);
     // factor, U = L^-T and alpha = K^-1 y of every entry: the ONE pipeline run of the call (medgp_get_factor is valid afterwards)
-    if ((rc = factor_run(c, nbatch, max_n, theta, true, false))) return rc;
+    if ((rc = factor_run(c, nbatch, theta, true, false))) return rc;
     const double log2pi = std::log(2.0 * c->pi);
     for (const LooClassSingles &s : T.csing) {
         if (s.ns == 0) continue;
@@ -2450,11 +2217,11 @@ int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     if (!slots || !theta || !obj) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
     if (flag_grad && !grad) return fail(c, MEDGP_ERR_ARG, "grad is NULL with flag_grad set");
-    if (c->Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_loo_grad supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds K^-1 here", c->Q);
-    int max_n = 0, rc;
+    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_loo_grad supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds K^-1 here", c->rules.Q);
+    int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = set_batch(c, nbatch, slots, &max_n, false, true))) return rc;
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const BatchPlan &P = c->plan;
     if ((rc = buf_ensure(c, BUF_GVEC, 4 * P.need_vec * sizeof(double)))) return rc;
     double *gvec = buf<double>(c, BUF_GVEC);
@@ -2462,10 +2229,10 @@ int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
     if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
     // the generic kernels (MEDGP_V0) keep W where P goes: this call always takes the templated ones
-    const bool v0 = c->use_v0;
-    c->use_v0 = false;
-    rc = factor_run(c, nbatch, max_n, theta, true, false);
-    c->use_v0 = v0;
+    const bool v0 = c->rules.use_v0;
+    c->rules.use_v0 = false;
+    rc = factor_run(c, nbatch, theta, true, false);
+    c->rules.use_v0 = v0;
     if (rc) return rc;
     const double log2pi = std::log(2.0 * c->pi);
     for (const SizeClass &k : P.cls) {
@@ -2478,7 +2245,7 @@ int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
             hipLaunchKernelGGL(k_loo_vec, dim3(1, nb), dim3(256), 0, c->stream, V, vec, 2, log2pi);
         } else {
             const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
-            const dim3 tg = wg.grid, tb(WG_THREADS);
+            const dim3 tg(wg.grid), tb(WG_THREADS);
             { Launcher l(c, KID_LOO_KINV); hipLaunchKernelGGL(k_loo_kinv, tg, tb, 0, c->stream, V, nb, wg.wg_tiles, wg.nbp); }
             { Launcher l(c, KID_LOO_VEC); hipLaunchKernelGGL(k_loo_vec, dim3(4 * nt64, nb), dim3(256), 0, c->stream, V, vec, 1, log2pi); }
             {
@@ -2492,7 +2259,7 @@ int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
             hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V);
         }
         Launcher l(c, KID_EPILOGUE);
-        const int nparts = (2 * nb >= c->num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
+        const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
         hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, c->d_theta, flag_grad, 1, c->d_nlml, c->d_grad, c->d_status_out, 1);
     }
     HIPCHK(c, hipGetLastError());
