@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 10: medgp_components_batch (9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 11: medgp_functional_batch (10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -433,6 +433,54 @@ int medgp_trend_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const do
 int medgp_components_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
                            const int32_t *meta2, const float *t2, float *cmean, float *cvar, float *ccov, int32_t *status);
 
+/* Posterior of LINEAR FUNCTIONALS of the latent function: the mean over a window, the change over an interval, the contrast of two
+ * covariates, a time-weighted exposure.  Each is g = sum_k a_k f_{m_k}(t_k) over a list of terms (m_k, t_k, a_k), and its posterior is
+ * a Gaussian in closed form from the factorisation the other calls make -- with ONE solve column per functional (linearity:
+ * V_g = L^-1 (K* a)), no m x m covariance block, and every difference formed in fp64.
+ *   ref: core/gp_regression.cpp:128-214 (GP_Regression::predict), kernel/c_kernel_LMC_SM.cpp:329-372 (cross Gram)
+ * The reference has no such output; the definition is the fp64 / long-double restatement of tests/functional_ref.py.
+ * Component q is k_q(tau) = cos(w_q tau) exp(-c_q tau^2), w_q = 2 pi mu_q, c_q = 2 (pi v_q)^2 (SE: Q = 1, w = 0, c = 1 / (2 l^2),
+ * B = sf^2; SM: B_q = the 1 x 1 weight).  For a training observation (m_i, t_i), tau = t_k - t_i, L and z = L^-1 y of the ONE factor of
+ * the call (after its jitter rounds):
+ *   K*_g[i]  = sum_k a_k sum_q B_q[m_i, m_k] k_q(tau)                      the terms in the caller's order
+ *   V_g      = L^-1 K*_g
+ *   fmean[f] = V_g^T z                                                     posterior mean of g
+ *   q_g      = sum_k sum_l a_k a_l sum_q B_q[m_k, m_l] k_q(t_k - t_l)      prior variance of g
+ *   fvar[f]  = q_g - sum_i V_g[i]^2                                        posterior variance of g; LATENT: no sigma^2 anywhere
+ * Layout: patient b owns the functionals [foffsets[b], foffsets[b + 1]) of the call (foffsets: nbatch + 1 values), functional f owns the
+ * terms [toffsets[f], toffsets[f + 1]) (toffsets: F + 1 values, F = foffsets[nbatch]) of meta2 / t2 / weight.  foffsets[0] == 0,
+ * toffsets[0] == 0, both non-decreasing.  A patient without functionals is allowed; a functional without terms is allowed and gets
+ * exactly 0.0f / 0.0f.  At most 2^31 - 65 functionals and 2^31 - 1 terms per call.
+ * nbatch, slots, theta and status mean exactly what they mean for medgp_posterior_batch: one factorisation per patient, no n > 2 guard,
+ * status[b] = jitter rounds or -1; after k jitter rounds every quantity is that of the matrix that was factored, K + k diag(sigma^2).
+ * meta2 may be NULL for SE / SM and is range-checked for LMC-SM, as the posterior call's.  MEDGP_ERR_ARG before any device work, with
+ * nothing written: fmean or fvar NULL; weight, t2, toffsets or foffsets NULL (whatever the counts); meta2 NULL for LMC-SM; offsets that
+ * do not start at 0 or decrease.  The functionals of a patient with status[b] < 0 get NaN in both outputs.  fvar is written as computed:
+ * no clamp (a functional the data determine to rounding, or a contrast of a point with itself, may come out as a tiny negative number).
+ * Supported range of the time stamps: |t| <= 2^14 h, of the training observations AND of the terms, as medgp_trend_batch: K*_g is formed
+ * from the tables cos / sin (w_q t_i) and cos / sin (w_q t_k) (one sincos per term and q, once per call).  q_g is formed from the time
+ * differences t_k - t_l themselves, in fp64: the small prior variance of a change score over a short interval does not inherit the
+ * |w t| eps of the tables.
+ * A functional's two outputs depend on the patient, theta and its own term list in the caller's order alone: not on the other
+ * functionals of the call or their order, the tile or column it lands in, the launch chunk, or -- with the route pinned -- the
+ * batch-mates.  Every sum has a fixed order that depends on the functional alone (terms in the caller's order, q inside; rows in
+ * order).  REORDERING the terms of a functional may move the last bits of its outputs.
+ * The functionals go in tiles of 64 per workgroup: the 64 columns of the forward solve on fp64 MFMA are 64 functionals
+ * (kernels_functional.h); the columns of a tile may have different term counts, the caller's order is kept.  Work memory per launch
+ * within MEDGP_POSTERIOR_BUDGET_GB; a call whose per-entry matrices exceed the memory budget fails with MEDGP_ERR_CAPACITY, like
+ * medgp_posterior_batch.  All three covariance families, any Q the context accepts.
+ * Out of scope: slope terms (f' inside a functional; medgp_trend_batch gives the slope at a point), the covariance BETWEEN two
+ * functionals (medgp_posterior_joint_batch on the nodes gives it), and observation noise (g is a functional of the latent f: add the
+ * noise of a future measurement on the caller's side).
+ * Accuracy: tests/test_functional_gpu.py holds fmean and fvar to the project's bar of 2 fp32 ulps of max(|ref|, 1e-3 S), S the
+ * patient's largest |ref| of the quantity over its functionals, and fvar <= q_g (1 + 2^-22).
+ * All pointers are HOST memory. */
+int medgp_functional_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta,
+                           const int64_t *foffsets,   /* nbatch + 1: functionals of patient b are [foffsets[b], foffsets[b+1]) */
+                           const int64_t *toffsets,   /* F + 1 (F = foffsets[nbatch]): terms of functional f are [toffsets[f], toffsets[f+1]) */
+                           const int32_t *meta2, const float *t2, const double *weight,   /* per term; meta2 may be NULL for SE / SM */
+                           float *fmean, float *fvar, int32_t *status);
+
 /* Cohort statistics, the step after training: for each of nseries independent sample series
  * (series s = data[off[s] .. off[s] + cnt[s])) the Gaussian kernel density estimate with Silverman's bandwidth evaluated AT the
  * samples, and its "mode": weighted != 0: sum x dens / sum dens; weighted == 0: the sample with the largest density (first one).
@@ -476,7 +524,8 @@ int medgp_synchronize(medgp_ctx *ctx);
    the events of all seven launches cost 1.6 % of a 512-patient step); enable = 0: off */
 int medgp_profile_enable(medgp_ctx *ctx, int enable);
 /* number of distinct kernels the library launches, and their names.  The table counts profile ENTRIES: the launches of k_components
-   (medgp_components_batch) are accounted under the entry "k_posterior", so the table and every kernel id in it stay what they were */
+   (medgp_components_batch) and of k_functional (medgp_functional_batch) are accounted under the entry "k_posterior", the one
+   k_functional_prep launch per size class of that call under "k_prep", so the table and every kernel id in it stay what they were */
 int medgp_profile_num_kernels(void);
 const char *medgp_profile_kernel_name(int k);
 /* synchronises, then returns accumulated milliseconds and launch count of kernel k since the

@@ -5,11 +5,12 @@ include/medgp_hip.h).  This package is the thin Python host layer used by the te
 bench.py: a ctypes binding (`capi`), the synthetic cohort generator (`synth`) and the
 cohort sharding helper (`shard`); `trend` reads the slope posterior of `Context.trend`
 (`prob_rising`, `rate_interval`, `grid`), `components` the per-component posterior of `Context.components`
-(`table`, `select`, `band`).  There is no CPU fallback: importing works anywhere,
+(`table`, `select`, `band`), `functionals` builds the linear functionals of `Context.functionals` (`point`, `change`, `contrast`,
+`window_mean`, `pack`, `prob_above`).  There is no CPU fallback: importing works anywhere,
 but every compute call needs the built library and a HIP device.
 """
-from . import capi, synth, shard, trend, components  # noqa: F401
+from . import capi, synth, shard, trend, components, functionals  # noqa: F401
 from .capi import Context, MedgpError, lib_path, load  # noqa: F401
 from .trend import grid, prob_rising, rate_interval  # noqa: F401
 
-__all__ = ["capi", "synth", "shard", "trend", "components", "Context", "MedgpError", "lib_path", "load", "grid", "prob_rising", "rate_interval"]
+__all__ = ["capi", "synth", "shard", "trend", "components", "functionals", "Context", "MedgpError", "lib_path", "load", "grid", "prob_rising", "rate_interval"]

@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_trend_batch", "medgp_components_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at",
 ]
 
@@ -99,6 +99,7 @@ def load():
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
     lib.medgp_trend_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, fp, fp, i32p]
     lib.medgp_components_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, i32p]
+    lib.medgp_functional_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32p, fp, dp, fp, fp, i32p]
     lib.medgp_synchronize.argtypes = [vp]
     lib.medgp_profile_enable.argtypes = [vp, C.c_int]
     lib.medgp_profile_num_kernels.restype = C.c_int
@@ -522,6 +523,65 @@ class Context:
         for b in range(nb):
             a, e = int(offsets[b]), int(offsets[b + 1])
             out.append((cmean[a:e].copy(), cvar[a:e].copy(), cc[a:e].copy() if cov else None))
+        return out, st
+
+    def functionals(self, slots, theta, packed_list):
+        """medgp_functional_batch: the posterior of linear functionals g = sum_k a_k f_{m_k}(t_k) of the latent function -- window
+        means, change scores, contrasts (medgp_amd.functionals builds and packs them).  slots [nbatch], theta [nbatch, H];
+        packed_list: per patient (toffsets [F + 1], meta2 [T] or None for SE / SM, t2 [T], weight [T]) as functionals.pack returns
+        it; a patient may have no functionals, a functional no terms.  Returns ([(fmean[F], fvar[F]) per patient], status): the
+        posterior mean and the LATENT posterior variance (no noise term, no clamp) of every functional."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        nb = slots.shape[0]
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.size != nb * self.H:
+            raise ValueError(f"theta has {theta.size} values, expected {nb} x {self.H}")
+        theta = theta.reshape(nb, self.H)
+        if len(packed_list) != nb:
+            raise ValueError(f"{len(packed_list)} packed functional lists for {nb} patients")
+        multi = self.kernel_index == KERNEL_LMC_SM
+        toffs, ms, ts, ws = [], [], [], []
+        for b, pk in enumerate(packed_list):
+            if len(pk) != 4:
+                raise ValueError(f"patient {b}: expected (toffsets, meta2, t2, weight)")
+            to = np.ascontiguousarray(pk[0], dtype=np.int64).ravel()
+            t = np.ascontiguousarray(pk[2], dtype=np.float32).ravel()
+            a = np.ascontiguousarray(pk[3], dtype=np.float64).ravel()
+            if pk[1] is None:
+                if multi:
+                    raise ValueError("meta2 is required for the multi-output kernel")
+                m = np.zeros(t.shape[0], dtype=np.int32)
+            else:
+                m = np.ascontiguousarray(pk[1], dtype=np.int32).ravel()
+            if to.shape[0] < 1 or to[0] != 0 or np.any(np.diff(to) < 0):
+                raise ValueError(f"patient {b}: toffsets must start at 0 and not decrease")
+            if not (m.shape[0] == t.shape[0] == a.shape[0] == int(to[-1])):
+                raise ValueError(f"patient {b}: {m.shape[0]} covariates, {t.shape[0]} times and {a.shape[0]} weights for {int(to[-1])} terms")
+            if multi and m.size and (m.min() < 0 or m.max() >= self.D):
+                raise ValueError(f"patient {b}: meta2 outside [0, {self.D})")
+            toffs.append(to)
+            ms.append(m)
+            ts.append(t)
+            ws.append(a)
+        foffsets = np.zeros(nb + 1, dtype=np.int64)
+        foffsets[1:] = np.cumsum([x.shape[0] - 1 for x in toffs])
+        tbase = np.concatenate([[0], np.cumsum([int(x[-1]) for x in toffs])]).astype(np.int64)
+        toffsets = np.ascontiguousarray(np.concatenate([[0]] + [x[1:] + tbase[b] for b, x in enumerate(toffs)]), dtype=np.int64)
+        F, T = int(foffsets[-1]), int(tbase[-1])
+        t2 = np.ascontiguousarray(np.concatenate(ts) if T else np.zeros(1), dtype=np.float32)
+        m2 = np.ascontiguousarray(np.concatenate(ms) if T else np.zeros(1), dtype=np.int32)
+        wt = np.ascontiguousarray(np.concatenate(ws) if T else np.zeros(1), dtype=np.float64)
+        fmean, fvar = (np.empty(max(F, 1), dtype=np.float32) for _ in range(2))
+        st = np.empty(nb, dtype=np.int32)
+        i64p = C.POINTER(C.c_int64)
+        self._chk(self._lib.medgp_functional_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
+                                                   foffsets.ctypes.data_as(i64p), toffsets.ctypes.data_as(i64p), _ptr(m2, C.c_int32),
+                                                   _ptr(t2, C.c_float), _ptr(wt, C.c_double), _ptr(fmean, C.c_float), _ptr(fvar, C.c_float),
+                                                   _ptr(st, C.c_int32)))
+        out = []
+        for b in range(nb):
+            a, e = int(foffsets[b]), int(foffsets[b + 1])
+            out.append((fmean[a:e].copy(), fvar[a:e].copy()))
         return out, st
 
     def posterior_joint(self, slots, theta, meta2_list, t2_list, eps_list=None, cov=True):

@@ -115,6 +115,70 @@ inline void build_components_tiles(const std::vector<TableClass> &cls, const int
     build_point_tiles(cls, order, offsets, nullptr, components_extra(Q, with_cov), budget, T, components_tw(Q));
 }
 
+// medgp_functional_batch: the two-level CSR of a call -- patient b owns functionals [foffsets[b], foffsets[b + 1]), functional f owns
+// terms [toffsets[f], toffsets[f + 1]) -- checked before anything is read through it.  The error kinds, in the order they are looked for:
+enum FunctionalCsrError {
+    FUNC_CSR_OK = 0,
+    FUNC_CSR_NULL,          // foffsets or toffsets is null (toffsets is required even for a call without functionals: toffsets[0])
+    FUNC_CSR_FIRST,         // foffsets[0] != 0                                (at = 0)
+    FUNC_CSR_DECREASE,      // foffsets[at + 1] < foffsets[at]
+    FUNC_CSR_COUNT,         // more than FUNC_MAX_FUNCTIONALS functionals
+    FUNC_CSR_TERM_FIRST,    // toffsets[0] != 0                                (at = 0)
+    FUNC_CSR_TERM_DECREASE, // toffsets[at + 1] < toffsets[at]
+    FUNC_CSR_TERM_COUNT     // more than FUNC_MAX_TERMS terms                  (at = the functional that passes it)
+};
+#define FUNC_TW 64                                        // functionals per tile of k_functional: one solve column each
+#define FUNC_MAX_FUNCTIONALS ((int64_t)INT32_MAX - FUNC_TW)   // a tile's p0 + cnt and the offset table of F + 1 ints stay in int
+#define FUNC_MAX_TERMS ((int64_t)INT32_MAX)
+// what the entry point stages of a checked call: F functionals, T terms, toff [F + 1] the term offsets as the device's ints, fun [T]
+// the functional of every term
+struct FunctionalCsr {
+    int64_t F = 0, T = 0, at = -1;   // at: where the error was found (FunctionalCsrError)
+    std::vector<int> toff, fun;
+};
+// Nothing behind a broken place is read: foffsets is walked first (nbatch + 1 values), toffsets only up to foffsets[nbatch] + 1 values
+// of a foffsets found sound, and the walk stops at the first violation.
+inline FunctionalCsrError check_functional_csr(const int64_t *foffsets, const int64_t *toffsets, int nbatch, FunctionalCsr &out) {
+    out = FunctionalCsr{};
+    if (!foffsets || !toffsets) return FUNC_CSR_NULL;
+    if (foffsets[0] != 0) { out.at = 0; return FUNC_CSR_FIRST; }
+    for (int b = 0; b < nbatch; b++)
+        if (foffsets[b + 1] < foffsets[b]) { out.at = b; return FUNC_CSR_DECREASE; }
+    const int64_t F = foffsets[nbatch];
+    if (F > FUNC_MAX_FUNCTIONALS) { out.at = nbatch; return FUNC_CSR_COUNT; }
+    if (toffsets[0] != 0) { out.at = 0; return FUNC_CSR_TERM_FIRST; }
+    for (int64_t f = 0; f < F; f++) {
+        if (toffsets[f + 1] < toffsets[f]) { out.at = f; return FUNC_CSR_TERM_DECREASE; }
+        if (toffsets[f + 1] > FUNC_MAX_TERMS) { out.at = f; return FUNC_CSR_TERM_COUNT; }
+    }
+    out.F = F;
+    out.T = toffsets[F];
+    out.toff.resize((size_t)F + 1);
+    out.fun.resize((size_t)out.T);
+    for (int64_t f = 0; f <= F; f++) out.toff[(size_t)f] = (int)toffsets[f];
+    for (int64_t f = 0; f < F; f++)
+        for (int64_t x = toffsets[f]; x < toffsets[f + 1]; x++) out.fun[(size_t)x] = (int)f;
+    return FUNC_CSR_OK;
+}
+// The internal position of every functional after the plan's reordering of the entries: pos[f] = the rank of functional f when the
+// classes are walked in order, their entries in internal order and each patient's functionals in the caller's.  The tile table walks
+// the functionals in exactly this order (tile k of build_functional_tiles owns FUNC_TW consecutive positions of one patient), while
+// its p0 keeps the caller's numbering: the outputs need no scatter.
+inline void functional_positions(const std::vector<TableClass> &cls, const int *order, const int64_t *foffsets, std::vector<int64_t> &pos) {
+    int64_t F = 0, next = 0;
+    for (const TableClass &k : cls)
+        for (int i = k.b0; i < k.b0 + k.count; i++) F = std::max(F, foffsets[order[i] + 1]);
+    pos.assign((size_t)F, -1);
+    for (const TableClass &k : cls)
+        for (int i = k.b0; i < k.b0 + k.count; i++)
+            for (int64_t f = foffsets[order[i]]; f < foffsets[order[i] + 1]; f++) pos[(size_t)f] = next++;
+}
+// the posterior call's tables over the functionals: FUNC_TW per tile (kernels_functional.h), nothing behind a tile's ld x 64 work rows
+inline void build_functional_tiles(const std::vector<TableClass> &cls, const int *order, const int64_t *foffsets, size_t budget,
+                                   PointTables<PostTile> &T) {
+    build_point_tiles(cls, order, foffsets, nullptr, 0, budget, T, FUNC_TW);
+}
+
 struct JointTables : PointTables<PostTile> {
     std::vector<JointPat> pats;
     std::vector<JointTile> pairs, blks;

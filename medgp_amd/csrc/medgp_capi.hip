@@ -17,6 +17,7 @@
 #include "kernels_forecast.h"
 #include "kernels_trend.h"
 #include "kernels_components.h"
+#include "kernels_functional.h"
 #include "kernels_loo.h"
 #include "kernels_loo_grad.h"
 
@@ -75,10 +76,12 @@ struct Arena {
 //   call's eps and samples, cov_status -- LOO: its group / tile-pair / job tables, the blocks of one launch chunk, group_status;
 //   LOO: the singleton table and the index lists; BUF_GVEC: the per-entry vectors [u | s | v | log p] of medgp_loo_grad;
 //   BUF_SLOPE: the per-point outputs [dmean | dvar | cross] of medgp_trend_batch;
-//   BUF_COMP: the per-point outputs [cmean | cvar | ccov] of medgp_components_batch (Q, Q and Q^2 floats per point)
+//   BUF_COMP: the per-point outputs [cmean | cvar | ccov] of medgp_components_batch (Q, Q and Q^2 floats per point);
+//   medgp_functional_batch (T terms, F functionals; the terms' covariates and times travel as the posterior call's points, the outputs
+//   in its mean / var): BUF_FUNC_D the doubles [weight T | rsum T | q_g F | cos T Q | sin T Q], BUF_FUNC_I the ints [toff F + 1 | fun T]
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -847,7 +850,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 10; }
+int medgp_abi_version(void) { return 11; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2068,7 +2071,85 @@ int components_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     }
     return read_status(c, nbatch, status);
 }
+
+// medgp_functional_batch (kernels_functional.h): the posterior call's pipeline run, then per size class k_functional_prep (the term
+// tables and the prior variances, once per call; accounted under the profile entry of k_prep) and per launch chunk k_functional over
+// tiles of 64 functionals, one solve column each; those launches are accounted under the profile entry of k_posterior (the profile
+// table keeps its names).  The tile table indexes functionals in the caller's numbering: nothing is scattered.
+int functional_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *foffsets, const int64_t *toffsets,
+                    const int32_t *meta2, const float *t2, const double *weight, float *fmean, float *fvar, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
+    if (!fmean || !fvar) return fail(c, MEDGP_ERR_ARG, "fmean / fvar is NULL");
+    if (!foffsets || !toffsets || !t2 || !weight) return fail(c, MEDGP_ERR_ARG, "foffsets / toffsets / t2 / weight is NULL");
+    if (c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
+    int rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    FunctionalCsr S;
+    switch (check_functional_csr(foffsets, toffsets, nbatch, S)) {
+    case FUNC_CSR_OK: break;
+    case FUNC_CSR_FIRST: return fail(c, MEDGP_ERR_ARG, "foffsets[0] = %lld, expected 0", (long long)foffsets[0]);
+    case FUNC_CSR_DECREASE: return fail(c, MEDGP_ERR_ARG, "foffsets decrease at %lld", (long long)S.at);
+    case FUNC_CSR_COUNT: return fail(c, MEDGP_ERR_ARG, "%lld functionals in one call (at most %lld)", (long long)foffsets[nbatch], (long long)FUNC_MAX_FUNCTIONALS);
+    case FUNC_CSR_TERM_FIRST: return fail(c, MEDGP_ERR_ARG, "toffsets[0] = %lld, expected 0", (long long)toffsets[0]);
+    case FUNC_CSR_TERM_DECREASE: return fail(c, MEDGP_ERR_ARG, "toffsets decrease at %lld", (long long)S.at);
+    case FUNC_CSR_TERM_COUNT: return fail(c, MEDGP_ERR_ARG, "more than %lld terms in one call (functional %lld)", (long long)FUNC_MAX_TERMS, (long long)S.at);
+    default: return fail(c, MEDGP_ERR_ARG, "foffsets / toffsets is NULL");
+    }
+    const int64_t F = S.F, Tn = S.T;
+    const size_t Fz = (size_t)std::max<int64_t>(F, 1), Tz = (size_t)std::max<int64_t>(Tn, 1), Q = (size_t)c->rules.Q;
+    std::vector<double> ht2;
+    std::vector<int> hm2;
+    if ((rc = stage_points(c, Tn, meta2, t2, nullptr, ht2, hm2))) return rc;   // (the terms' covariates are range-checked as the posterior call's points)
+    HIPCHK(c, hipSetDevice(c->device));
+    // the outputs are invariant under a permutation of the training observations: the grouped copy serves, as for the posterior
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
+    const std::vector<TableClass> cls = table_classes(c->plan);
+    PointTables<PostTile> T;
+    build_functional_tiles(cls, c->plan.order.data(), foffsets, c->posterior_budget, T);
+    if ((rc = upload_points(c, Tn, ht2, hm2))) return rc;
+    if ((rc = buf_ensure(c, BUF_MEAN, Fz * sizeof(float)))) return rc;   // (per functional, not per term)
+    if ((rc = buf_ensure(c, BUF_VAR, Fz * sizeof(float)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FUNC_D, (2 * Tz + Fz + 2 * Tz * Q) * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FUNC_I, (Fz + 1 + Tz) * sizeof(int)))) return rc;
+    double *d_w = buf<double>(c, BUF_FUNC_D), *d_rsum = d_w + Tz, *d_qg = d_rsum + Tz, *d_cos = d_qg + Fz, *d_sin = d_cos + Tz * Q;
+    int *d_toff = buf<int>(c, BUF_FUNC_I), *d_fun = d_toff + Fz + 1;
+    HIPCHK(c, hipMemcpyAsync(d_toff, S.toff.data(), sizeof(int) * (F + 1), hipMemcpyHostToDevice, c->stream));
+    if (Tn > 0) {
+        HIPCHK(c, hipMemcpyAsync(d_w, weight, sizeof(double) * Tn, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_fun, S.fun.data(), sizeof(int) * Tn, hipMemcpyHostToDevice, c->stream));
+    }
+    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
+    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
+    // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
+    if ((rc = factor_run(c, nbatch, theta, false, true))) return rc;
+    const FuncTerms ft{d_toff, d_fun, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), d_w, d_cos, d_sin, d_rsum, d_qg};
+    for (size_t i = 0, k = 0; i < T.chunks.size(); i = k) {   // the chunks of a class are consecutive, and so are their tiles
+        int nt = 0;
+        for (k = i; k < T.chunks.size() && T.chunks[k].cls == T.chunks[i].cls; k++) nt += T.chunks[k].nt;
+        Launcher l(c, KID_PREP);
+        hipLaunchKernelGGL(k_functional_prep, dim3(nt), dim3(256), 0, c->stream, class_view(c, c->plan, c->plan.cls[T.chunks[i].cls]),
+                           buf<PostTile>(c, BUF_TILES) + T.chunks[i].t0, ft);
+    }
+    for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
+        Launcher l(c, KID_POSTERIOR);
+        hipLaunchKernelGGL(k_functional, dim3(ch.nt), dim3(256), 0, c->stream, class_view(c, c->plan, c->plan.cls[ch.cls]), buf<PostTile>(c, BUF_TILES) + ch.t0,
+                           ft, buf<double>(c, BUF_WORK), ch.stride, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR));
+    }
+    HIPCHK(c, hipGetLastError());
+    if (F > 0) {
+        HIPCHK(c, hipMemcpyAsync(fmean, buf<float>(c, BUF_MEAN), sizeof(float) * F, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(fvar, buf<float>(c, BUF_VAR), sizeof(float) * F, hipMemcpyDeviceToHost, c->stream));
+    }
+    return read_status(c, nbatch, status);
+}
 }  // namespace
+
+int medgp_functional_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *foffsets,
+                           const int64_t *toffsets, const int32_t *meta2, const float *t2, const double *weight, float *fmean,
+                           float *fvar, int32_t *status) {
+    return functional_impl(c, nbatch, slots, theta, foffsets, toffsets, meta2, t2, weight, fmean, fvar, status);
+}
 
 int medgp_components_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
                            const int32_t *meta2, const float *t2, float *cmean, float *cvar, float *ccov, int32_t *status) {
