@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 11: medgp_functional_batch (10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 12: medgp_functional_joint_batch (11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -471,7 +471,8 @@ int medgp_components_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, con
  * medgp_posterior_batch.  All three covariance families, any Q the context accepts.
  * Out of scope: slope terms (f' inside a functional; medgp_trend_batch gives the slope at a point), the covariance BETWEEN two
  * functionals (medgp_posterior_joint_batch on the nodes gives it), and observation noise (g is a functional of the latent f: add the
- * noise of a future measurement on the caller's side).
+ * noise of a future measurement on the caller's side).  medgp_functional_joint_batch below gives that covariance from the same solve
+ * columns, without the m x m block of the nodes.
  * Accuracy: tests/test_functional_gpu.py holds fmean and fvar to the project's bar of 2 fp32 ulps of max(|ref|, 1e-3 S), S the
  * patient's largest |ref| of the quantity over its functionals, and fvar <= q_g (1 + 2^-22).
  * All pointers are HOST memory. */
@@ -480,6 +481,49 @@ int medgp_functional_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, con
                            const int64_t *toffsets,   /* F + 1 (F = foffsets[nbatch]): terms of functional f are [toffsets[f], toffsets[f+1]) */
                            const int32_t *meta2, const float *t2, const double *weight,   /* per term; meta2 may be NULL for SE / SM */
                            float *fmean, float *fvar, int32_t *status);
+
+/* JOINT posterior of a patient's linear functionals: medgp_functional_batch plus the posterior covariance BETWEEN the functionals of
+ * each patient -- what a joint statement about several summaries needs ("the 24 h mean of A is falling AND that of B"; the variance
+ * of the contrast g_A - g_B is v_A + v_B - 2 c_AB), what composes further functionals on the host without another call, and what
+ * experimental design needs: with single-term `point` functionals as candidate measurements among the targets, the block holds
+ * targets x candidates and candidates x candidates (medgp_amd/design.py: expected variance reduction, rank-1 conditioning, greedy
+ * picks).
+ *   ref: core/gp_regression.cpp:128-214 (GP_Regression::predict), kernel/c_kernel_LMC_SM.cpp:329-372 (cross Gram)
+ * The reference has no such output; the definition is tests/functional_joint_ref.py.  With V_f = L^-1 K*_f of medgp_functional_batch:
+ *   fcov[f, g] = q_fg - V_f^T V_g                                                  posterior covariance of (g_f, g_g)
+ *   q_fg       = sum_{k in f} sum_{l in g} a_k a_l sum_q B_q[m_k, m_l] k_q(t_k - t_l)      their prior covariance
+ * LATENT: no sigma^2 anywhere, and no clamp.  The arguments, the limits, the MEDGP_ERR_ARG cases, the jitter rule (after k rounds
+ * every quantity is that of K + k diag(sigma^2)) and the supported range of the time stamps are those of medgp_functional_batch.
+ * fmean and fvar are that call's outputs BIT FOR BIT (the same kernel launches on the same tiles).  fcov, fmean and fvar are all
+ * required: NULL is MEDGP_ERR_ARG before any device work.
+ * Layout of fcov: with F_b = foffsets[b + 1] - foffsets[b], patient b's block starts at fcov + sum_{a < b} F_a^2 and is F_b x F_b,
+ * row-major, both triangles written.  F_b == 0 is allowed.  Only the lower triangle is computed, the upper one is mirrored from the
+ * same float: fcov is exactly symmetric.  Its diagonal is not taken from the product: fcov[f, f] has the bits of fvar[f].  A functional
+ * without terms gives a row and a column of exact 0.0f.  A patient with status[b] < 0 gets NaN in all three outputs.
+ * q_fg is formed like q_g, from the time differences t_k - t_l themselves in fp64 (no cos / sin (w t) tables): the covariance of two
+ * short change scores is as small as their variances.  For f > g in the caller's numbering the terms of f run in the outer loop and
+ * those of g inside, both in the caller's order, q innermost; V_f^T V_g runs over the rows in order.
+ * An element depends on the patient, theta, the two term lists and WHICH OF THE TWO COMES FIRST in the call: not on the other
+ * functionals, the tile or column either lands in, the launch chunk, or -- with the route pinned -- the batch-mates.  REORDERING the
+ * terms of a functional may move the last bits of its outputs, and so may SWAPPING THE ORDER of two functionals those of their
+ * covariance (f > g decides which term list is the outer loop).
+ * Memory: the call is cut into launch chunks of WHOLE patients within MEDGP_POSTERIOR_BUDGET_GB; the V of all tiles of a patient
+ * (ceil(F_b / 64) x n_pad x 64 doubles) and its F_b^2 floats are resident together; no fp64 copy of the block is kept, because nothing
+ * is factored.  A single patient beyond the budget fails with MEDGP_ERR_CAPACITY, as the joint posterior's; so does a call whose
+ * per-entry matrices exceed the memory budget.
+ * fcov is positive semi-definite in exact arithmetic only (empty and degenerate functionals give zero eigenvalues, rounding makes them
+ * tiny negative ones): it is not factored here.
+ * Out of scope: slope terms inside functionals, sampling from (or factorising) fcov, and a rectangular targets x candidates form (put
+ * both lists into one call and slice the block).
+ * Accuracy: tests/test_functional_joint_gpu.py holds fmean, fvar and fcov to the project's bar of 2 fp32 ulps of max(|ref|, 1e-3 S),
+ * S the patient's largest |ref| of the quantity (for fcov over its whole F x F block).
+ * All pointers are HOST memory. */
+int medgp_functional_joint_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta,
+                                 const int64_t *foffsets, const int64_t *toffsets,
+                                 const int32_t *meta2, const float *t2, const double *weight,
+                                 float *fmean, float *fvar,
+                                 float *fcov,   /* sum_b F_b^2: patient b's F_b x F_b block, row-major */
+                                 int32_t *status);
 
 /* Cohort statistics, the step after training: for each of nseries independent sample series
  * (series s = data[off[s] .. off[s] + cnt[s])) the Gaussian kernel density estimate with Silverman's bandwidth evaluated AT the

@@ -6,11 +6,12 @@ bench.py: a ctypes binding (`capi`), the synthetic cohort generator (`synth`) an
 cohort sharding helper (`shard`); `trend` reads the slope posterior of `Context.trend`
 (`prob_rising`, `rate_interval`, `grid`), `components` the per-component posterior of `Context.components`
 (`table`, `select`, `band`), `functionals` builds the linear functionals of `Context.functionals` (`point`, `change`, `contrast`,
-`window_mean`, `pack`, `prob_above`).  There is no CPU fallback: importing works anywhere,
+`window_mean`, `pack`, `prob_above`), `design` reads the joint covariance of `Context.functionals_joint` (`variance_reduction`,
+`condition`, `greedy`: which measurement to take next).  There is no CPU fallback: importing works anywhere,
 but every compute call needs the built library and a HIP device.
 """
-from . import capi, synth, shard, trend, components, functionals  # noqa: F401
+from . import capi, synth, shard, trend, components, functionals, design  # noqa: F401
 from .capi import Context, MedgpError, lib_path, load  # noqa: F401
 from .trend import grid, prob_rising, rate_interval  # noqa: F401
 
-__all__ = ["capi", "synth", "shard", "trend", "components", "functionals", "Context", "MedgpError", "lib_path", "load", "grid", "prob_rising", "rate_interval"]
+__all__ = ["capi", "synth", "shard", "trend", "components", "functionals", "design", "Context", "MedgpError", "lib_path", "load", "grid", "prob_rising", "rate_interval"]

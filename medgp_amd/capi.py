@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at",
 ]
 
@@ -100,6 +100,7 @@ def load():
     lib.medgp_trend_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, fp, fp, i32p]
     lib.medgp_components_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, i32p]
     lib.medgp_functional_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32p, fp, dp, fp, fp, i32p]
+    lib.medgp_functional_joint_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32p, fp, dp, fp, fp, fp, i32p]
     lib.medgp_synchronize.argtypes = [vp]
     lib.medgp_profile_enable.argtypes = [vp, C.c_int]
     lib.medgp_profile_num_kernels.restype = C.c_int
@@ -531,6 +532,48 @@ class Context:
         packed_list: per patient (toffsets [F + 1], meta2 [T] or None for SE / SM, t2 [T], weight [T]) as functionals.pack returns
         it; a patient may have no functionals, a functional no terms.  Returns ([(fmean[F], fvar[F]) per patient], status): the
         posterior mean and the LATENT posterior variance (no noise term, no clamp) of every functional."""
+        slots, theta, foffsets, toffsets, m2, t2, wt = self._functional_args(slots, theta, packed_list)
+        nb, F = slots.shape[0], int(foffsets[-1])
+        fmean, fvar = (np.empty(max(F, 1), dtype=np.float32) for _ in range(2))
+        st = np.empty(nb, dtype=np.int32)
+        i64p = C.POINTER(C.c_int64)
+        self._chk(self._lib.medgp_functional_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
+                                                   foffsets.ctypes.data_as(i64p), toffsets.ctypes.data_as(i64p), _ptr(m2, C.c_int32),
+                                                   _ptr(t2, C.c_float), _ptr(wt, C.c_double), _ptr(fmean, C.c_float), _ptr(fvar, C.c_float),
+                                                   _ptr(st, C.c_int32)))
+        out = []
+        for b in range(nb):
+            a, e = int(foffsets[b]), int(foffsets[b + 1])
+            out.append((fmean[a:e].copy(), fvar[a:e].copy()))
+        return out, st
+
+    def functionals_joint(self, slots, theta, packed_list):
+        """medgp_functional_joint_batch: functionals() plus the posterior covariance between the functionals of each patient.
+        Arguments and argument checks as functionals().  Returns ([(fmean[F], fvar[F], fcov[F, F]) per patient], status): fmean and
+        fvar are functionals()' outputs bit for bit; fcov is LATENT (no noise term, no clamp), exactly symmetric, and its diagonal has
+        the bits of fvar.  medgp_amd.design works on fcov (expected variance reduction of a measurement, greedy picks)."""
+        slots, theta, foffsets, toffsets, m2, t2, wt = self._functional_args(slots, theta, packed_list)
+        nb, F = slots.shape[0], int(foffsets[-1])
+        cnt = np.diff(foffsets)
+        coff = np.zeros(nb + 1, dtype=np.int64)
+        coff[1:] = np.cumsum(cnt * cnt)
+        fmean, fvar = (np.empty(max(F, 1), dtype=np.float32) for _ in range(2))
+        fcov = np.empty(max(int(coff[-1]), 1), dtype=np.float32)
+        st = np.empty(nb, dtype=np.int32)
+        i64p = C.POINTER(C.c_int64)
+        self._chk(self._lib.medgp_functional_joint_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
+                                                         foffsets.ctypes.data_as(i64p), toffsets.ctypes.data_as(i64p), _ptr(m2, C.c_int32),
+                                                         _ptr(t2, C.c_float), _ptr(wt, C.c_double), _ptr(fmean, C.c_float),
+                                                         _ptr(fvar, C.c_float), _ptr(fcov, C.c_float), _ptr(st, C.c_int32)))
+        out = []
+        for b in range(nb):
+            a, e, k = int(foffsets[b]), int(foffsets[b + 1]), int(cnt[b])
+            out.append((fmean[a:e].copy(), fvar[a:e].copy(), fcov[int(coff[b]):int(coff[b + 1])].reshape(k, k).copy()))
+        return out, st
+
+    def _functional_args(self, slots, theta, packed_list):
+        """the argument checks of functionals() / functionals_joint(), raised before the library is reached: (slots, theta [nbatch, H],
+        foffsets [nbatch + 1], toffsets [F + 1], meta2, t2, weight per term) as the calls take them"""
         slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
         nb = slots.shape[0]
         theta = np.ascontiguousarray(theta, dtype=np.float64)
@@ -567,22 +610,11 @@ class Context:
         foffsets[1:] = np.cumsum([x.shape[0] - 1 for x in toffs])
         tbase = np.concatenate([[0], np.cumsum([int(x[-1]) for x in toffs])]).astype(np.int64)
         toffsets = np.ascontiguousarray(np.concatenate([[0]] + [x[1:] + tbase[b] for b, x in enumerate(toffs)]), dtype=np.int64)
-        F, T = int(foffsets[-1]), int(tbase[-1])
+        T = int(tbase[-1])
         t2 = np.ascontiguousarray(np.concatenate(ts) if T else np.zeros(1), dtype=np.float32)
         m2 = np.ascontiguousarray(np.concatenate(ms) if T else np.zeros(1), dtype=np.int32)
         wt = np.ascontiguousarray(np.concatenate(ws) if T else np.zeros(1), dtype=np.float64)
-        fmean, fvar = (np.empty(max(F, 1), dtype=np.float32) for _ in range(2))
-        st = np.empty(nb, dtype=np.int32)
-        i64p = C.POINTER(C.c_int64)
-        self._chk(self._lib.medgp_functional_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
-                                                   foffsets.ctypes.data_as(i64p), toffsets.ctypes.data_as(i64p), _ptr(m2, C.c_int32),
-                                                   _ptr(t2, C.c_float), _ptr(wt, C.c_double), _ptr(fmean, C.c_float), _ptr(fvar, C.c_float),
-                                                   _ptr(st, C.c_int32)))
-        out = []
-        for b in range(nb):
-            a, e = int(foffsets[b]), int(foffsets[b + 1])
-            out.append((fmean[a:e].copy(), fvar[a:e].copy()))
-        return out, st
+        return slots, theta, foffsets, toffsets, m2, t2, wt
 
     def posterior_joint(self, slots, theta, meta2_list, t2_list, eps_list=None, cov=True):
         """medgp_posterior_joint_batch: the joint predictive distribution of every patient's test points.  Arguments as

@@ -226,6 +226,47 @@ inline bool build_joint_chunks(const std::vector<TableClass> &cls, const int *or
     return true;
 }
 
+// medgp_functional_joint_batch: the joint call's chunks over the FUNCTIONALS of a patient -- whole patients per chunk (the work rows of
+// all its tiles of FUNC_TW functionals and its F x F float block of fcov are resident at once; no fp64 C: nothing is factored), with the
+// patient table (JointPat: p0 = its first functional of the call, m = F, coff unused) and the lower tile pairs of k_funccov; no row
+// blocks.  The tiles are those of build_functional_tiles, in its order; a patient without functionals has no tile, no pair and no
+// JointPat.  false: one patient alone exceeds the budget (err).
+inline bool build_functional_joint_chunks(const std::vector<TableClass> &cls, const int *order, const int64_t *foffsets, size_t budget,
+                                          JointTables &T, TableError &err) {
+    for (size_t ci = 0; ci < cls.size(); ci++) {
+        const TableClass &k = cls[ci];
+        const size_t stride = (size_t)k.ld * 64;
+        TileChunk ch{(int)ci, (int)T.tiles.size(), 0, stride, (int)T.pats.size(), 0, (int)T.pairs.size(), 0, 0, 0};
+        size_t wbytes = 0, cflt = 0;
+        auto close = [&]() {
+            if (ch.npat == 0) return;
+            T.chunks.push_back(ch);
+            T.work_need = std::max(T.work_need, wbytes); T.cov_need = std::max(T.cov_need, cflt * sizeof(float));
+            ch.t0 += ch.nt; ch.nt = 0; ch.pat0 += ch.npat; ch.npat = 0; ch.pair0 += ch.npair; ch.npair = 0;
+            wbytes = cflt = 0;
+        };
+        for (int i = k.b0; i < k.b0 + k.count; i++) {
+            const int b = order[i];
+            const int64_t F = foffsets[b + 1] - foffsets[b];
+            if (F == 0) continue;
+            const int nt = (int)((F + FUNC_TW - 1) / FUNC_TW);
+            // V of all its tiles and its float block of fcov (F <= FUNC_MAX_FUNCTIONALS: F^2 floats stay in size_t)
+            const size_t vbytes = (size_t)nt * stride * sizeof(double), fbytes = (size_t)F * (size_t)F * sizeof(float);
+            if (fbytes > budget || vbytes > budget - fbytes) { err = {b, i, -1, (long long)F, vbytes + fbytes}; return false; }
+            if (wbytes + cflt * sizeof(float) + vbytes + fbytes > budget) close();
+            const int pidx = (int)T.pats.size();
+            T.pats.push_back({i - k.b0, b, (int)foffsets[b], (int)F, ch.nt, 0, 0, (long long)cflt});
+            push_point_tiles(T.tiles, i - k.b0, foffsets[b], foffsets[b + 1], nullptr, FUNC_TW);
+            for (int I = 0; I < nt; I++)
+                for (int J = 0; J <= I; J++) T.pairs.push_back({pidx, I, J, 0});
+            ch.nt += nt; ch.npat++; ch.npair += nt * (nt + 1) / 2;
+            wbytes += vbytes; cflt += (size_t)F * (size_t)F;
+        }
+        close();
+    }
+    return true;
+}
+
 // a launch chunk of medgp_loo_batch: groups [g0, g0 + ng) of class cls with their tile pairs and solve jobs
 struct LooChunk { int cls, g0, ng, pair0, npair, job0, njob; };
 struct LooClassSingles { int cls, s0, ns; };

@@ -20,6 +20,31 @@
 
 // JointPat (one patient of a joint call) and JointTile (one workgroup of k_postcov / k_postdraw): inference_tables.h
 
+// acc = V_I^T V_J over the rows [0, npad) of two tiles' work rows ([npad][64] each) on fp64 MFMA, rows in order: the rows of V_J staged
+// through Vs (PJ_KC x POST_LS doubles of LDS) PJ_KC at a time, those of V_I streamed from memory.  Wave w owns output rows
+// 16 w .. 16 w + 15 and all four 16-column strips (acc[cs][r]: row 16 w + 4 r + g, column 16 cs + li).  Shared by k_postcov and
+// k_funccov (kernels_functional_joint.h).  Ends without a barrier: the caller synchronises before it reuses Vs.
+__device__ __forceinline__ void pj_vtv(v4d (&acc)[4], const double *__restrict__ VI, const double *__restrict__ VJ, int npad, double *Vs,
+                                       int tid, int w, int li, int g) {
+#pragma unroll
+    for (int cs = 0; cs < 4; cs++) acc[cs] = v4d{0.0, 0.0, 0.0, 0.0};
+    const double *Ar = VI + 16 * w + li;
+    for (int kk = 0; kk < npad; kk += PJ_KC) {
+        __syncthreads();   // Vs is free
+#pragma unroll
+        for (int x = tid; x < PJ_KC * 64; x += 256) Vs[(x >> 6) * POST_LS + (x & 63)] = VJ[(size_t)(kk + (x >> 6)) * 64 + (x & 63)];
+        double a[PJ_KC / 4];
+#pragma unroll
+        for (int s = 0; s < PJ_KC / 4; s++) a[s] = Ar[(size_t)(kk + 4 * s + g) * 64];
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < PJ_KC / 4; s++)
+#pragma unroll
+            for (int cs = 0; cs < 4; cs++)
+                acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], Vs[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, 0);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // C_IJ = K**_IJ - V_I^T V_J (+ sigma^2 on the diagonal; identity on rows / columns [m, mpad)).  acc = V_I^T V_J over the
 // rows of V on fp64 MFMA: the rows of V_J staged through LDS PJ_KC at a time, those of V_I streamed from memory (wave w
@@ -59,23 +84,7 @@ __global__ void __launch_bounds__(256) k_postcov(MedgpDev L, const JointPat *__r
     const int *m2 = meta2 + P.p0;
     const double *tt = t2 + P.p0;
     v4d acc[4];
-#pragma unroll
-    for (int cs = 0; cs < 4; cs++) acc[cs] = v4d{0.0, 0.0, 0.0, 0.0};
-    const double *Ar = VI + 16 * w + li;
-    for (int kk = 0; kk < npad; kk += PJ_KC) {
-        __syncthreads();   // Vs is free
-#pragma unroll
-        for (int x = tid; x < PJ_KC * 64; x += 256) Vs[(x >> 6) * POST_LS + (x & 63)] = VJ[(size_t)(kk + (x >> 6)) * 64 + (x & 63)];
-        double a[PJ_KC / 4];
-#pragma unroll
-        for (int s = 0; s < PJ_KC / 4; s++) a[s] = Ar[(size_t)(kk + 4 * s + g) * 64];
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < PJ_KC / 4; s++)
-#pragma unroll
-            for (int cs = 0; cs < 4; cs++)
-                acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], Vs[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, 0);
-    }
+    pj_vtv(acc, VI, VJ, npad, Vs, tid, w, li, g);
     // this lane's four columns
     int mc[4];
     double tc[4];

@@ -18,6 +18,7 @@
 #include "kernels_trend.h"
 #include "kernels_components.h"
 #include "kernels_functional.h"
+#include "kernels_functional_joint.h"
 #include "kernels_loo.h"
 #include "kernels_loo_grad.h"
 
@@ -78,7 +79,8 @@ struct Arena {
 //   BUF_SLOPE: the per-point outputs [dmean | dvar | cross] of medgp_trend_batch;
 //   BUF_COMP: the per-point outputs [cmean | cvar | ccov] of medgp_components_batch (Q, Q and Q^2 floats per point);
 //   medgp_functional_batch (T terms, F functionals; the terms' covariates and times travel as the posterior call's points, the outputs
-//   in its mean / var): BUF_FUNC_D the doubles [weight T | rsum T | q_g F | cos T Q | sin T Q], BUF_FUNC_I the ints [toff F + 1 | fun T]
+//   in its mean / var): BUF_FUNC_D the doubles [weight T | rsum T | q_g F | cos T Q | sin T Q], BUF_FUNC_I the ints [toff F + 1 | fun T];
+//   medgp_functional_joint_batch: besides, the joint posterior's patient and tile-pair tables and its float covariance blocks (fcov)
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
              BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_COUNT };
@@ -850,7 +852,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 11; }
+int medgp_abi_version(void) { return 12; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2076,11 +2078,17 @@ int components_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
 // tables and the prior variances, once per call; accounted under the profile entry of k_prep) and per launch chunk k_functional over
 // tiles of 64 functionals, one solve column each; those launches are accounted under the profile entry of k_posterior (the profile
 // table keeps its names).  The tile table indexes functionals in the caller's numbering: nothing is scattered.
+// medgp_functional_joint_batch (joint; kernels_functional_joint.h) is the SAME code path for fmean / fvar (same pipeline run, same
+// k_functional_prep and k_functional launches per tile: the bits of a functional do not depend on the launch chunk).  It cuts its
+// launch chunks at patient boundaries and runs k_funccov behind k_functional on each chunk, while the chunk's work rows are resident;
+// those launches are accounted under the profile entry of k_postcov.
 int functional_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *foffsets, const int64_t *toffsets,
-                    const int32_t *meta2, const float *t2, const double *weight, float *fmean, float *fvar, int32_t *status) {
+                    const int32_t *meta2, const float *t2, const double *weight, float *fmean, float *fvar, bool joint, float *fcov,
+                    int32_t *status) {
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
     if (!fmean || !fvar) return fail(c, MEDGP_ERR_ARG, "fmean / fvar is NULL");
+    if (joint && !fcov) return fail(c, MEDGP_ERR_ARG, "fcov is NULL");
     if (!foffsets || !toffsets || !t2 || !weight) return fail(c, MEDGP_ERR_ARG, "foffsets / toffsets / t2 / weight is NULL");
     if (c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
     int rc;
@@ -2105,8 +2113,16 @@ int functional_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     // the outputs are invariant under a permutation of the training observations: the grouped copy serves, as for the posterior
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const std::vector<TableClass> cls = table_classes(c->plan);
-    PointTables<PostTile> T;
-    build_functional_tiles(cls, c->plan.order.data(), foffsets, c->posterior_budget, T);
+    JointTables T;
+    if (!joint) build_functional_tiles(cls, c->plan.order.data(), foffsets, c->posterior_budget, T);
+    else {
+        TableError e;
+        if (!build_functional_joint_chunks(cls, c->plan.order.data(), foffsets, c->posterior_budget, T, e))
+            return fail(c, MEDGP_ERR_CAPACITY, "patient %d: the joint posterior of %lld functionals on %d observations needs %zu MB at once, the budget is %zu MB (MEDGP_POSTERIOR_BUDGET_GB)",
+                        e.b, e.m, c->plan.en[e.entry], e.need >> 20, c->posterior_budget >> 20);
+    }
+    std::vector<size_t> cov_off(joint ? nbatch : 0);   // start of patient b's block in fcov (floats)
+    if (joint) { size_t o = 0; for (int b = 0; b < nbatch; b++) { cov_off[b] = o; const size_t Fb = (size_t)(foffsets[b + 1] - foffsets[b]); o += Fb * Fb; } }
     if ((rc = upload_points(c, Tn, ht2, hm2))) return rc;
     if ((rc = buf_ensure(c, BUF_MEAN, Fz * sizeof(float)))) return rc;   // (per functional, not per term)
     if ((rc = buf_ensure(c, BUF_VAR, Fz * sizeof(float)))) return rc;
@@ -2121,6 +2137,11 @@ int functional_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     }
     if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
     if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
+    if (joint && !T.pats.empty()) {
+        if ((rc = upload_table(c, BUF_PATS, T.pats))) return rc;
+        if ((rc = upload_table(c, BUF_PAIRS, T.pairs))) return rc;
+        if ((rc = buf_ensure(c, BUF_COV, T.cov_need))) return rc;
+    }
     // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
     if ((rc = factor_run(c, nbatch, theta, false, true))) return rc;
     const FuncTerms ft{d_toff, d_fun, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), d_w, d_cos, d_sin, d_rsum, d_qg};
@@ -2133,8 +2154,20 @@ int functional_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     }
     for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
         Launcher l(c, KID_POSTERIOR);
-        hipLaunchKernelGGL(k_functional, dim3(ch.nt), dim3(256), 0, c->stream, class_view(c, c->plan, c->plan.cls[ch.cls]), buf<PostTile>(c, BUF_TILES) + ch.t0,
+        const MedgpDev V = class_view(c, c->plan, c->plan.cls[ch.cls]);
+        hipLaunchKernelGGL(k_functional, dim3(ch.nt), dim3(256), 0, c->stream, V, buf<PostTile>(c, BUF_TILES) + ch.t0,
                            ft, buf<double>(c, BUF_WORK), ch.stride, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR));
+        if (!joint) continue;
+        l.finish();
+        {
+            Launcher lc(c, KID_POSTCOV);
+            hipLaunchKernelGGL(k_funccov, dim3(ch.npair), dim3(256), 0, c->stream, V, buf<JointPat>(c, BUF_PATS), buf<JointTile>(c, BUF_PAIRS) + ch.pair0, ft,
+                               buf<double>(c, BUF_WORK), ch.stride, buf<float>(c, BUF_VAR), buf<float>(c, BUF_COV));
+        }
+        for (int i = ch.pat0; i < ch.pat0 + ch.npat; i++) {   // the chunk's blocks go home before the next chunk reuses the buffer (stream order)
+            const JointPat &P = T.pats[i];
+            HIPCHK(c, hipMemcpyAsync(fcov + cov_off[P.b], buf<float>(c, BUF_COV) + P.voff, sizeof(float) * (size_t)P.m * P.m, hipMemcpyDeviceToHost, c->stream));
+        }
     }
     HIPCHK(c, hipGetLastError());
     if (F > 0) {
@@ -2148,7 +2181,13 @@ int functional_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
 int medgp_functional_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *foffsets,
                            const int64_t *toffsets, const int32_t *meta2, const float *t2, const double *weight, float *fmean,
                            float *fvar, int32_t *status) {
-    return functional_impl(c, nbatch, slots, theta, foffsets, toffsets, meta2, t2, weight, fmean, fvar, status);
+    return functional_impl(c, nbatch, slots, theta, foffsets, toffsets, meta2, t2, weight, fmean, fvar, false, nullptr, status);
+}
+
+int medgp_functional_joint_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *foffsets,
+                                 const int64_t *toffsets, const int32_t *meta2, const float *t2, const double *weight, float *fmean,
+                                 float *fvar, float *fcov, int32_t *status) {
+    return functional_impl(c, nbatch, slots, theta, foffsets, toffsets, meta2, t2, weight, fmean, fvar, true, fcov, status);
 }
 
 int medgp_components_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
