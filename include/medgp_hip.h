@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 12: medgp_functional_joint_batch (11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 13: medgp_gmm_fit (12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -542,6 +542,35 @@ int medgp_kde_mode(int device, int nseries, const int64_t *off, const int32_t *c
 int medgp_kde_mode_at(int device, int nseries, const int64_t *off, const int32_t *cnt, const double *data, const int64_t *toff,
                       const int32_t *tcnt, const double *test, int weighted, double *mode, double *bw, int32_t *status,
                       double *kernel_ms);
+
+/* Kernel clustering, the step between training and the mode kernel: EM for full-covariance Gaussian
+ * mixtures on n points of dimension d, nruns independent runs in one call, each from its own start.  Replaces what scikit-learn's
+ * GaussianMixture(covariance_type='full', n_init, max_iter) computes inside the reference's run_sklearn_gmm, ref:
+ * medgpc/clustering/cluster.py:23-46 -- the restarts of every K = 1 .. Q are the runs; the selection (largest lower bound per K,
+ * smallest BIC over K) is medgp_amd/clustering.py's.  There is no random generator on the device: run r starts from the hard labels
+ * label0[r, i] in [0, k[r]) (one-hot responsibilities, then one M-step; a class may be empty), where scikit-learn starts from an
+ * unseeded k-means.  The definition the kernels are held to is tests/gmm_ref.py:
+ *   M-step: n_k = sum_i r_ik + 10 eps, w_k = n_k / n, mu_k = sum r_ik x_i / n_k, S_k = sum r_ik (x_i - mu_k)(x_i - mu_k)^T / n_k +
+ *           reg_covar I, L_k = chol(S_k); a pivot <= 0 or NaN fails the run.
+ *   E-step: log p_ik = -1/2 (d log 2 pi + |L_k^-1 (x_i - mu_k)|^2) - sum log diag L_k + log w_k, lse_i = logsumexp_k,
+ *           r_ik = exp(log p_ik - lse_i), lb = mean_i lse_i.
+ *   Loop:   it = 1 .. max_iter: E-step, M-step, change = lb - previous lb (-inf at first); converged when |change| < tol.
+ *   After:  one E-step at the final parameters: assign = first arg max_k r_ik, bic = -2 n mean lse + (K d (d + 1) / 2 + K d + K - 1) log n.
+ * Limits: 2 <= n, 1 <= d <= 80, 1 <= k[r] <= min(16, n), 1 <= nruns <= 65535, max_iter >= 1, tol >= 0, reg_covar >= 0; anything else is
+ * MEDGP_ERR_ARG.  The call holds nruns * kmax * n responsibilities and at most 32 d x d partial sums per (run, component) on the
+ * device at once: beyond MEDGP_GMM_BUDGET_GB (default 8) it fails with MEDGP_ERR_CAPACITY before any device work.
+ * Outputs, kmax = max_r k[r]: lower_bound[r] the loop's last lb; status[r] 1 converged, 0 max_iter reached, -1 failed; n_iter[r] the
+ * iterations run; weights / means / covs of the components (entries beyond a run's K are zero), assign[r, i].  A failed run has NaN
+ * lower_bound, bic, weights, means and covs and assign -1; it does not fail the call.  weights, means, covs, assign and kernel_ms (HIP-event
+ * time from the first to the last launch) may be NULL.  A run's outputs are bit-identical whatever the other runs of the call are and
+ * however often the host polls the runs' flags (MEDGP_GMM_POLL iterations, default 8).  One-shot call on `device`, host arrays in and
+ * out, no context.  Errors: medgp_last_error(NULL). */
+int medgp_gmm_fit(int device, int n, int d, const double *x /* [n*d] row-major */,
+                  int nruns, const int32_t *k /* [nruns] */, const int32_t *label0 /* [nruns*n] */,
+                  int max_iter, double tol, double reg_covar,
+                  double *lower_bound, double *bic, int32_t *n_iter, int32_t *status /* [nruns] */,
+                  double *weights /* [nruns*kmax] */, double *means /* [nruns*kmax*d] */,
+                  double *covs /* [nruns*kmax*d*d] */, int32_t *assign /* [nruns*n] */, double *kernel_ms);
 
 /* Route pinning.  By default the library picks the factorisation schedule of a call from the batch it is given (one workgroup per
  * patient in two shapes, or the multi-CU look-ahead schedule for few large patients): fastest, and every schedule meets the parity

@@ -24,7 +24,7 @@ SYMBOLS = [
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
     "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
-    "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at",
+    "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at", "medgp_gmm_fit",
 ]
 
 
@@ -110,6 +110,8 @@ def load():
     lib.medgp_profile_reset.argtypes = [vp]
     lib.medgp_kde_mode.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int64), i32p, dp, C.c_int, dp, dp, i32p, dp]
     lib.medgp_kde_mode_at.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int64), i32p, dp, C.POINTER(C.c_int64), i32p, dp, C.c_int, dp, dp, i32p, dp]
+    lib.medgp_gmm_fit.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, i32p, i32p, C.c_int, C.c_double, C.c_double, dp, dp, i32p, i32p,
+                                  dp, dp, dp, i32p, dp]
     _lib = lib
     return lib
 
@@ -151,6 +153,43 @@ def kde_mode(series, weighted=True, device=0, full=False, test=None):
     if rc != 0:
         raise MedgpError(f"medgp_kde_mode failed ({rc}): {lib.medgp_last_error(None).decode()}")
     return (mode, bw, st, ms.value) if full else mode
+
+
+def gmm_fit(x, k, label0, max_iter=2000, tol=1e-3, reg_covar=1e-6, device=0, full=False):
+    """medgp_gmm_fit: EM for full-covariance Gaussian mixtures on the points x [n, d], len(k) independent runs in one call; run r has
+    k[r] components and starts from the hard labels label0[r] [n] (what scikit-learn's GaussianMixture.fit does from its k-means
+    start inside the reference's run_sklearn_gmm, ref: medgpc/clustering/cluster.py:23-46).  Returns (lower_bound, bic, n_iter,
+    status) per run -- status 1 converged, 0 max_iter reached, -1 failed (NaN lower_bound / bic) -- and with full=True also (weights
+    [nruns, kmax], means [nruns, kmax, d], covs [nruns, kmax, d, d], assign [nruns, n], kernel milliseconds)."""
+    lib = load()
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim == 1:
+        x = x[:, None]
+    if x.ndim != 2:
+        raise ValueError(f"x of shape {x.shape}, expected [n, d]")
+    n, d = x.shape
+    k = np.ascontiguousarray(np.atleast_1d(k), dtype=np.int32)
+    nr = k.shape[0]
+    label0 = np.ascontiguousarray(label0, dtype=np.int32)
+    if k.ndim != 1 or nr < 1 or label0.size != nr * n:
+        raise ValueError(f"{label0.size} start labels for {nr} runs of {n} points")
+    kmax = max(int(k.max()), 1)
+    lb, bic = np.full(nr, np.nan), np.full(nr, np.nan)
+    nit, st = np.zeros(nr, dtype=np.int32), np.zeros(nr, dtype=np.int32)
+    w = mu = cv = asg = None
+    ms = C.c_double(0.0)
+    if full:
+        w, mu, cv = np.zeros((nr, kmax)), np.zeros((nr, kmax, d)), np.zeros((nr, kmax, d, d))
+        asg = np.zeros((nr, n), dtype=np.int32)
+    rc = lib.medgp_gmm_fit(int(device), n, d, _ptr(x, C.c_double), nr, _ptr(k, C.c_int32), _ptr(label0, C.c_int32), int(max_iter),
+                           float(tol), float(reg_covar), _ptr(lb, C.c_double), _ptr(bic, C.c_double), _ptr(nit, C.c_int32),
+                           _ptr(st, C.c_int32), _ptr(w, C.c_double), _ptr(mu, C.c_double), _ptr(cv, C.c_double), _ptr(asg, C.c_int32),
+                           C.byref(ms))
+    if rc != 0:
+        err = MedgpError(f"medgp_gmm_fit failed ({rc}): {lib.medgp_last_error(None).decode()}")
+        err.code = rc
+        raise err
+    return (lb, bic, nit, st, w, mu, cv, asg, ms.value) if full else (lb, bic, nit, st)
 
 
 class Context:

@@ -12,6 +12,7 @@
 #include "kernels_wgrad.h"
 #include "kernels_io.h"
 #include "kernels_cohort.h"
+#include "kernels_gmm.h"
 #include "kernels_posterior.h"
 #include "kernels_posterior_joint.h"
 #include "kernels_forecast.h"
@@ -852,7 +853,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 12; }
+int medgp_abi_version(void) { return 13; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2527,6 +2528,132 @@ int medgp_kde_mode_at(int device, int nseries, const int64_t *off, const int32_t
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     for (void *q : {(void *)d_off, (void *)d_cnt, (void *)d_st, (void *)d_x, (void *)d_mode, (void *)d_bw, (void *)d_stats, (void *)d_part, (void *)d_toff, (void *)d_tcnt, (void *)d_test}) (void)hipFree(q);
+    return rc;
+}
+
+// ---- kernel clustering: batched EM for Gaussian mixtures (kernels_gmm.h; no context) ---------------------------------------
+int medgp_gmm_fit(int device, int n, int d, const double *x, int nruns, const int32_t *k, const int32_t *label0, int max_iter,
+                  double tol, double reg_covar, double *lower_bound, double *bic, int32_t *n_iter, int32_t *status,
+                  double *weights, double *means, double *covs, int32_t *assign, double *kernel_ms) {
+    medgp_ctx *none = nullptr;
+    if (!x || !k || !label0 || !lower_bound || !bic || !n_iter || !status) return fail(none, MEDGP_ERR_ARG, "medgp_gmm_fit: NULL argument");
+    if (n < 2 || n > INT32_MAX - GMM_BLOCK) return fail(none, MEDGP_ERR_ARG, "medgp_gmm_fit: n = %d, expected at least 2 points", n);
+    if (d < 1 || d > MEDGP_GMM_MAX_D) return fail(none, MEDGP_ERR_ARG, "medgp_gmm_fit: d = %d outside [1, %d] (MEDGP_GMM_MAX_D)", d, MEDGP_GMM_MAX_D);
+    if (nruns < 1 || nruns > 65535) return fail(none, MEDGP_ERR_ARG, "medgp_gmm_fit: nruns = %d outside [1, 65535]", nruns);
+    if (max_iter < 1) return fail(none, MEDGP_ERR_ARG, "medgp_gmm_fit: max_iter = %d, expected >= 1", max_iter);
+    if (!(tol >= 0.0) || !(reg_covar >= 0.0)) return fail(none, MEDGP_ERR_ARG, "medgp_gmm_fit: tol = %g / reg_covar = %g, expected >= 0", tol, reg_covar);
+    int kmax = 0;
+    for (int r = 0; r < nruns; r++) {
+        if (k[r] < 1 || k[r] > MEDGP_GMM_MAX_K || k[r] > n)
+            return fail(none, MEDGP_ERR_ARG, "medgp_gmm_fit: k[%d] = %d outside [1, min(%d (MEDGP_GMM_MAX_K), n = %d)]", r, k[r], MEDGP_GMM_MAX_K, n);
+        kmax = std::max(kmax, (int)k[r]);
+        for (int i = 0; i < n; i++) {
+            const int32_t l = label0[(size_t)r * n + i];
+            if (l < 0 || l >= k[r]) return fail(none, MEDGP_ERR_ARG, "medgp_gmm_fit: label0[%d, %d] = %d outside [0, %d)", r, i, l, k[r]);
+        }
+    }
+    GmmPlan pl;
+    if (!gmm_plan(n, d, nruns, kmax, &pl)) return fail(none, MEDGP_ERR_ARG, "medgp_gmm_fit: sizes outside the supported range");
+    double budget_gb = 8.0;
+    if (const char *e = getenv("MEDGP_GMM_BUDGET_GB")) { const double v = atof(e); if (v > 0.0) budget_gb = v; }
+    if ((double)pl.bytes > budget_gb * 1073741824.0)
+        return fail(none, MEDGP_ERR_CAPACITY, "medgp_gmm_fit: %d runs of up to %d components on %d x %d points need %.3f GB at once, the budget is %g GB (MEDGP_GMM_BUDGET_GB): split the runs over calls",
+                    nruns, kmax, n, d, (double)pl.bytes / 1073741824.0, budget_gb);
+    int poll = 8;
+    if (const char *e = getenv("MEDGP_GMM_POLL")) { const int v = atoi(e); if (v >= 1) poll = v; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(none, MEDGP_ERR_NODEVICE, "medgp_gmm_fit: no GPU (there is no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(none, MEDGP_ERR_ARG, "medgp_gmm_fit: device %d of %d", device, ndev);
+    HIPCHK(none, hipSetDevice(device));
+
+    // one block: the doubles first, then the ints
+    const int64_t rk = (int64_t)nruns * kmax;
+    const int64_t nd = pl.x_elems + pl.resp_elems + pl.par_elems + 2 * pl.mat_elems + 3 * rk + pl.blk_elems + pl.lse_elems + pl.sx_elems + pl.slab_elems + 3 * (int64_t)nruns;
+    const int64_t ni = pl.label_elems + rk + 3 * (int64_t)nruns;
+    char *blockp = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = MEDGP_OK;
+    auto chk = [&](hipError_t e, const char *what) { if (e != hipSuccess && rc == MEDGP_OK) rc = fail(none, MEDGP_ERR_HIP, "medgp_gmm_fit: %s failed: %s", what, hipGetErrorString(e)); return e == hipSuccess; };
+    std::vector<double> xp((size_t)pl.x_elems, 0.0);
+    for (int i = 0; i < n; i++) std::copy(x + (size_t)i * d, x + (size_t)(i + 1) * d, xp.begin() + (size_t)i * pl.dp);
+    if (chk(hipMalloc(&blockp, (size_t)(8 * nd + 4 * ni)), "hipMalloc") && chk(hipMemset(blockp, 0, (size_t)(8 * nd + 4 * ni)), "hipMemset") &&
+        chk(hipEventCreate(&e0), "hipEventCreate") && chk(hipEventCreate(&e1), "hipEventCreate")) {
+        GmmDev G{};
+        G.n = n; G.d = d; G.dp = pl.dp; G.nblk = pl.nblk; G.npad = pl.npad; G.bpc = pl.bpc; G.nchunk = pl.nchunk; G.nruns = nruns; G.kmax = kmax;
+        G.tol = tol; G.reg = reg_covar;
+        double *dptr = (double *)blockp;
+        auto take = [&](int64_t cnt) { double *q = dptr; dptr += cnt; return q; };
+        double *d_x = take(pl.x_elems);
+        G.x = d_x; G.resp = take(pl.resp_elems); G.mu = take(pl.par_elems); G.cov = take(pl.mat_elems); G.P = take(pl.mat_elems);
+        G.nk = take(rk); G.logw = take(rk); G.logdet = take(rk); G.blk_nk = take(pl.blk_elems); G.blk_lse = take(pl.lse_elems);
+        G.sx = take(pl.sx_elems); G.slab = take(pl.slab_elems); G.lb = take(nruns); G.prev = take(nruns); G.score = take(nruns);
+        int *iptr = (int *)dptr;
+        auto takei = [&](int64_t cnt) { int *q = iptr; iptr += cnt; return q; };
+        int *d_k = takei(nruns);
+        G.k = d_k; G.label = takei(pl.label_elems); G.cfail = takei(rk); G.niter = takei(nruns); G.status = takei(nruns);
+        std::vector<int32_t> hst(nruns, 0);
+        if (chk(hipMemcpy(d_x, xp.data(), sizeof(double) * pl.x_elems, hipMemcpyHostToDevice), "hipMemcpy") &&
+            chk(hipMemcpy(d_k, k, sizeof(int) * nruns, hipMemcpyHostToDevice), "hipMemcpy") &&
+            chk(hipMemcpy(G.label, label0, sizeof(int) * pl.label_elems, hipMemcpyHostToDevice), "hipMemcpy")) {
+            const dim3 g_pts(pl.nblk, kmax, nruns), g_resp(pl.nblk, nruns), g_chunk(pl.nchunk, kmax, nruns), g_comp(kmax, nruns), g_run((nruns + 63) / 64);
+            auto mstep = [&]() {
+                hipLaunchKernelGGL(k_gmm_msum, g_chunk, dim3(128), 0, nullptr, G);
+                hipLaunchKernelGGL(k_gmm_means, g_comp, dim3(128), 0, nullptr, G);
+                hipLaunchKernelGGL(k_gmm_cov, g_chunk, dim3(256), 0, nullptr, G);
+                hipLaunchKernelGGL(k_gmm_factor, g_comp, dim3(256), 0, nullptr, G);
+            };
+            chk(hipEventRecord(e0, nullptr), "hipEventRecord");
+            hipLaunchKernelGGL(k_gmm_resp, g_resp, dim3(64), 0, nullptr, G, (int)GMM_PHASE_INIT);
+            mstep();
+            hipLaunchKernelGGL(k_gmm_tail, g_run, dim3(64), 0, nullptr, G, (int)GMM_PHASE_INIT, 0);
+            for (int it = 1; it <= max_iter && rc == MEDGP_OK; it++) {
+                hipLaunchKernelGGL(k_gmm_estep, g_pts, dim3(256), 0, nullptr, G, (int)GMM_PHASE_ITER);
+                hipLaunchKernelGGL(k_gmm_resp, g_resp, dim3(64), 0, nullptr, G, (int)GMM_PHASE_ITER);
+                mstep();
+                hipLaunchKernelGGL(k_gmm_tail, g_run, dim3(64), 0, nullptr, G, (int)GMM_PHASE_ITER, it);
+                if (it % poll == 0 && it < max_iter) {   // the runs freeze on the device: this only decides when the host stops launching
+                    if (!chk(hipMemcpy(hst.data(), G.status, sizeof(int) * nruns, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+                    if (std::all_of(hst.begin(), hst.end(), [](int32_t s) { return s != GMM_RUNNING; })) break;
+                }
+            }
+            hipLaunchKernelGGL(k_gmm_estep, g_pts, dim3(256), 0, nullptr, G, (int)GMM_PHASE_FINAL);
+            hipLaunchKernelGGL(k_gmm_resp, g_resp, dim3(64), 0, nullptr, G, (int)GMM_PHASE_FINAL);
+            hipLaunchKernelGGL(k_gmm_tail, g_run, dim3(64), 0, nullptr, G, (int)GMM_PHASE_FINAL, 0);
+            chk(hipGetLastError(), "gmm kernel launch");
+            chk(hipEventRecord(e1, nullptr), "hipEventRecord");
+            std::vector<double> hscore(nruns), hnk((size_t)rk), hmu, hcov;
+            chk(hipMemcpy(lower_bound, G.lb, sizeof(double) * nruns, hipMemcpyDeviceToHost), "hipMemcpy");
+            chk(hipMemcpy(hscore.data(), G.score, sizeof(double) * nruns, hipMemcpyDeviceToHost), "hipMemcpy");
+            chk(hipMemcpy(n_iter, G.niter, sizeof(int) * nruns, hipMemcpyDeviceToHost), "hipMemcpy");
+            chk(hipMemcpy(status, G.status, sizeof(int) * nruns, hipMemcpyDeviceToHost), "hipMemcpy");
+            if (weights) chk(hipMemcpy(hnk.data(), G.nk, sizeof(double) * rk, hipMemcpyDeviceToHost), "hipMemcpy");
+            if (means) { hmu.resize((size_t)pl.par_elems); chk(hipMemcpy(hmu.data(), G.mu, sizeof(double) * pl.par_elems, hipMemcpyDeviceToHost), "hipMemcpy"); }
+            if (covs) { hcov.resize((size_t)pl.mat_elems); chk(hipMemcpy(hcov.data(), G.cov, sizeof(double) * pl.mat_elems, hipMemcpyDeviceToHost), "hipMemcpy"); }
+            if (assign) chk(hipMemcpy(assign, G.label, sizeof(int) * pl.label_elems, hipMemcpyDeviceToHost), "hipMemcpy");
+            if (kernel_ms && rc == MEDGP_OK) { float ms = 0.f; chk(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime"); *kernel_ms = ms; }
+            const double qnan = std::nan("");
+            for (int r = 0; rc == MEDGP_OK && r < nruns; r++) {
+                const bool ok = status[r] != GMM_FAILED;
+                const int K = k[r];
+                // free parameters of a full-covariance mixture: K d (d + 1) / 2 + K d + K - 1
+                const double npar = (double)K * d * (d + 1) / 2.0 + (double)K * d + K - 1;
+                if (!ok) lower_bound[r] = qnan;
+                bic[r] = ok ? -2.0 * hscore[r] * n + npar * std::log((double)n) : qnan;
+                for (int c = 0; c < kmax; c++) {
+                    const size_t q = (size_t)r * kmax + c;
+                    const bool in = c < K;
+                    if (weights) weights[q] = !in ? 0.0 : ok ? hnk[q] / n : qnan;
+                    for (int j = 0; means && j < d; j++) means[q * d + j] = !in ? 0.0 : ok ? hmu[q * pl.dp + j] : qnan;
+                    for (int i = 0; covs && i < d; i++)
+                        for (int j = 0; j < d; j++) covs[(q * d + i) * d + j] = !in ? 0.0 : ok ? hcov[(q * pl.dp + i) * pl.dp + j] : qnan;
+                }
+                for (int i = 0; assign && !ok && i < n; i++) assign[(size_t)r * n + i] = -1;
+            }
+        }
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(blockp);
     return rc;
 }
 
