@@ -3,8 +3,10 @@ comparisons honest) and tests/test_clustering_gpu.py (device against the definit
 
 73-dimensional inputs are component features (medgp_amd.clustering.extract_kernel_feature on synthetic LMC-SM hypers, the
 construction of tests/golden/clustering_ref.npz with more subjects); the others are Gaussian blobs.  Between them the cases use
-every n of {2, 5, 63, 64, 65, 130, 300}, every d of {1, 2, 15, 16, 17, 73, MAX_D}, every K of {1, 2, 5, MAX_K} and every stopping
-rule of {1, 3, 25 iterations, convergence at tol = 1e-3}."""
+every n of {2, 5, 63, 64, 65, 130, 300, 2049, 2112, 2113, 4100, 4161, 6200, 8257}, every d of {1, 2, 15, 16, 17, 33, 48, 49, 64, 73,
+MAX_D}, every K of {1, 2, 3, 4, 5, MAX_K} and every stopping rule of {1, 3, 25 iterations, convergence at tol = 1e-3}.  The n above
+2048 put more than one 64-point block into an M-step chunk (medgp_amd/csrc/gmm_tables.h: bpc = 2, 2, 2, 3, 3, 4, 5 in that
+order, with last chunks of 1, 1, 2, 2, 3, 1, 5 blocks); d = 33 ... 64 are the padded widths 48 and 64."""
 import os
 import sys
 
@@ -27,6 +29,11 @@ CASES = [
     (300, 73, 5, *CONV, 1e-6), (300, 73, 1, 3, 0.0, 1e-6), (300, MAX_D, 2, 3, 0.0, 1e-6), (300, MAX_D, 5, *CONV, 1e-3),
     (300, 2, MAX_K, 25, 0.0, 1e-6), (300, 15, MAX_K, 3, 0.0, 1e-3), (300, 1, 5, *CONV, 1e-6), (64, 2, MAX_K, *CONV, 1e-4),
     (63, 1, 1, *CONV, 1e-6),
+    # cohort sizes: more than one 64-point block per M-step chunk (bpc = ceil(ceil(n / 64) / 32) > 1, short last chunks), and the
+    # padded widths dp = 48 and 64
+    (2049, 17, 2, 3, 0.0, 1e-6), (2113, 73, 2, *CONV, 1e-6), (2112, MAX_D, 2, 3, 0.0, 1e-6), (4161, 2, MAX_K, 25, 0.0, 1e-6),
+    (8257, 33, 4, 3, 0.0, 1e-6), (300, 33, 2, 25, 0.0, 1e-6), (300, 48, 5, 3, 0.0, 1e-3), (130, 49, 2, 3, 0.0, 1e-6),
+    (300, 64, 5, *CONV, 1e-6), (4100, 64, 2, 3, 0.0, 1e-6), (6200, 16, 3, 25, 0.0, 1e-6), (2113, 73, 4, *CONV, 1e-6),
 ]
 
 
@@ -74,7 +81,7 @@ def case_data(i):
 
 
 E2E_SEED, E2E_SUBJECTS = 3, 40
-CALLS = ("mixed_call", "failing_call", "bits_call")     # the multi-run calls below
+CALLS = ("mixed_call", "failing_call", "bits_call", "many_runs_call", "chunked_bits_call", "late_failing_call")   # the multi-run calls below
 
 
 def make_clustering_experiment(root):
@@ -137,3 +144,45 @@ def bits_call():
     k = np.array([5, 1, 2, 3, 4, 5, 2, 3, 1, 4, 5, 2], dtype=np.int32)
     l0 = np.stack([clustering.init_labels(x, int(K), rng) for K in k])
     return x, k, l0, 2000, 1e-3, 1e-6
+
+
+def many_runs_call():
+    """70 runs in one call, K = 1 + r % 5, on mixed_call's kind of points with random starts (max_iter 6, tol 1e-3, reg 1e-6): more
+    runs than one workgroup of the per-run kernel holds (64) and than any other call's grid has in z.  The K = 1 runs stop at
+    iteration 2."""
+    rng = np.random.default_rng([SEED, 104])
+    x = blobs(rng, 130, 2, 4) * np.array([[1.0, 0.4]])
+    k = (1 + np.arange(70) % 5).astype(np.int32)
+    l0 = np.stack([rng.integers(0, K, 130).astype(np.int32) for K in k])
+    return x, k, l0, 6, 1e-3, 1e-6
+
+
+def chunked_bits_call():
+    """6 runs of mixed K on the 2049 points of the first case with two blocks per M-step chunk, to convergence: bits_call's
+    shape (runs stopping at different iterations, on both sides of the default polling interval) where a chunk is more than one
+    block.  The first two draws of the K = 3 start decide within 1.2 % of tol; the third is used."""
+    i = [c[:3] for c in CASES].index((2049, 17, 2))
+    x = case_data(i)[0]
+    rng = np.random.default_rng([SEED, 105])
+    k = np.array([2, 1, 4, 3, 2, 4], dtype=np.int32)
+    l0 = np.stack([clustering.init_labels(x, int(K), rng) for K in k])
+    for _ in range(2):
+        l0[3] = clustering.init_labels(x, 3, rng)
+    return x, k, l0, 2000, 1e-3, 1e-6
+
+
+LATE_FAILING_RUN = 2
+
+
+def late_failing_call():
+    """One call with reg_covar = 0 in which run LATE_FAILING_RUN fails AFTER the start: 130 standard-normal points in 2 dimensions
+    of which the first two are copies of (50, 50), K = 2, and a start with points 0 ... 4 in class 0.  The covariance of class 0
+    is regular at the start; EM then gives the far pair a class of its own, whose covariance is exactly 0.  Its mates, before
+    and after it, go on to max_iter = 5: K = 1, and K = 2 from starts that halve the bulk (by parity of the index, by the sign
+    of the first coordinate), which keep the pair inside a large class for those 5 iterations (they would isolate it later)."""
+    rng = np.random.default_rng([SEED, 106])
+    x = rng.normal(size=(130, 2))
+    x[0] = x[1] = 50.0
+    k = np.array([1, 2, 2, 2, 1], dtype=np.int32)
+    l0 = np.stack([np.zeros(130), np.arange(130) % 2, np.r_[np.zeros(5), np.ones(125)], x[:, 0] > np.median(x[:, 0]), np.zeros(130)]).astype(np.int32)
+    return x, k, l0, 5, 0.0, 0.0

@@ -27,7 +27,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 import gmm_cases as GC  # noqa: E402
 import gmm_ref as GR  # noqa: E402
 
-SKLEARN_CASES = [7, 9, 11, 14, 15, 18]    # indices into gmm_cases.CASES
+SKLEARN_CASES = [7, 9, 11, 14, 15, 18, 23, 27]    # indices into gmm_cases.CASES
 
 
 def load_reference(ref_root):

@@ -278,9 +278,10 @@ def test_end_to_end_experiment_meets_the_conditions(tmp_path):
 @pytest.mark.parametrize("call", GC.CALLS)
 def test_multi_run_calls_meet_the_conditions(call, spread):
     """The multi-run calls of the GPU test: every run that does not fail meets the conditions and enters the permutation spread;
-    the one planted failure fails at the start, and the shapes the calls were built for are there (a 2-iteration run beside runs
-    that use all of max_iter, an empty class, runs stopping at different iterations on both sides of the default polling
-    interval)."""
+    the two planted failures fail where they were planted (one at the start, one at a later iteration that is the same in every
+    order of the points), and the shapes the calls were built for are there (a 2-iteration run beside runs that use all of
+    max_iter, an empty class, runs stopping at different iterations on both sides of the default polling interval, more than 64
+    runs)."""
     x, k, l0, max_iter, tol, reg = getattr(GC, call)()
     outs = []
     for r in range(len(k)):
@@ -298,8 +299,24 @@ def test_multi_run_calls_meet_the_conditions(call, spread):
         assert (nit[1], st[1]) == (2, 1) and (nit[0], st[0]) == (max_iter, 0) and 1 not in l0[2] and k[2] == 3 and st[2] >= 0
     elif call == "failing_call":
         assert st == [0, -1, 0] and nit[1] == 0 and np.isnan(outs[1]["bic"])
-    else:
+    elif call == "bits_call":
         assert min(nit) == 2 and max(nit) > 8 and all(s == 1 for s in st)
+    elif call == "many_runs_call":
+        assert len(k) == 70 and all(s >= 0 for s in st) and set(k.tolist()) == {1, 2, 3, 4, 5}
+        assert all((nit[r], st[r]) == (2, 1) for r in range(70) if k[r] == 1) and all(nit[r] == max_iter for r in range(70) if k[r] >= 3)
+        assert (nit[69], st[69]) == (max_iter, 0) and (nit[65], st[65]) == (2, 1)      # the second workgroup of the per-run kernel holds both kinds
+    elif call == "chunked_bits_call":
+        assert x.shape[0] > 32 * 64 and all(s == 1 for s in st) and set(k.tolist()) == {1, 2, 3, 4}
+        assert min(nit) == 2 and sum(v < 8 for v in nit) >= 2 and sum(v > 8 for v in nit) >= 2 and len(set(nit)) >= 4
+    else:
+        f = GC.LATE_FAILING_RUN
+        assert reg == 0.0 and [s < 0 for s in st] == [r == f for r in range(len(k))] and 0 < f < len(k) - 1
+        assert 1 <= nit[f] < max_iter and np.isnan(outs[f]["bic"])
+        assert all(nit[r] == max_iter for r in range(len(k)) if r != f) and max(k[r] for r in range(len(k)) if r != f) >= 2
+        for s in range(8):                                  # the failure does not depend on the order of the points
+            perm = np.random.default_rng([GC.SEED, s, 3]).permutation(x.shape[0])
+            po = GR.gmm_fit_one(x[perm], int(k[f]), l0[f][perm], max_iter, tol, reg)
+            assert (po["status"], po["n_iter"]) == (-1, nit[f]), (s, po["status"], po["n_iter"])
 
 
 def test_spread_is_recorded(spread):

@@ -107,6 +107,55 @@ def test_bits_do_not_depend_on_call_mates_order_or_polling(built_lib, tmp_path):
         assert child[f"arr_{j}"].tobytes() == got[key].tobytes(), ("MEDGP_GMM_POLL=1", key)
 
 
+def same_bits(tag, a, b, runs_a, runs_b, k):
+    """runs runs_a of call a and runs runs_b of call b, the same runs in another company, agree to the bit; the calls may differ in
+    kmax, so a run's own K entries of weights, means and covs are compared"""
+    for ra, rb in zip(runs_a, runs_b):
+        K = int(k[ra])
+        for key in OUT:
+            u, v = a[key][ra], b[key][rb]
+            if key in ("weights", "means", "covs"):
+                u, v = u[:K], v[:K]
+            assert np.ascontiguousarray(u).tobytes() == np.ascontiguousarray(v).tobytes(), (tag, ra, key)
+
+
+def test_more_runs_than_one_workgroup_of_the_tail(built_lib):
+    """70 runs: the per-run kernel's second workgroup (runs 64 ... 69) and a grid of more than 64 in z"""
+    args = GC.many_runs_call()
+    x, k, l0, max_iter, tol, reg = args
+    got = device(args)
+    check_parity("70 runs", got, reference("many", args))
+    assert got["n_iter"][65] == 2 and got["n_iter"][69] == max_iter
+    same_bits("runs 64 ... 69 alone", got, device((x, k[64:], l0[64:], max_iter, tol, reg)), range(64, 70), range(6), k)
+    same_bits("reversed", got, device((x, k[::-1], l0[::-1], max_iter, tol, reg)), range(70), range(69, -1, -1), k)
+
+
+def test_bits_do_not_depend_on_call_mates_where_a_chunk_is_two_blocks(built_lib):
+    args = GC.chunked_bits_call()
+    x, k, l0, max_iter, tol, reg = args
+    got = device(args)
+    check_parity("6 runs on 2049 points", got, reference("chunked", args))
+    assert got["n_iter"].max() > 8 and got["n_iter"].min() == 2          # runs freeze on both sides of the default polling interval
+    same_bits("reversed", got, device((x, k[::-1], l0[::-1], max_iter, tol, reg)), range(6), range(5, -1, -1), k)
+    for r in (0, 2):                                                      # one that stops before the first poll, one after the second
+        same_bits("alone", got, device((x, k[r:r + 1], l0[r:r + 1], max_iter, tol, reg)), [r], [0], k)
+
+
+def test_a_run_that_fails_after_the_start_freezes_alone(built_lib):
+    args = GC.late_failing_call()
+    x, k, l0, max_iter, tol, reg = args
+    f = GC.LATE_FAILING_RUN
+    got, ref = device(args), reference("late failing", args)
+    mates = [r for r in range(len(k)) if r != f]
+    assert [s < 0 for s in ref["status"]] == [r == f for r in range(len(k))] and 1 <= ref["n_iter"][f] < max_iter
+    assert got["status"][f] == -1 and got["n_iter"][f] == ref["n_iter"][f]
+    for key in ("lower_bound", "bic", "weights", "means", "covs"):
+        assert np.all(np.isnan(got[key][f])), key
+    assert np.all(got["assign"][f] == -1)
+    check_parity("beside a run that fails at iteration %d" % ref["n_iter"][f], got, ref, runs=mates)
+    same_bits("without the failing run", got, device((x, k[mates], l0[mates], max_iter, tol, reg)), mates, range(len(mates)), k)
+
+
 def test_stored_scikit_learn_cases(built_lib):
     g = np.load(os.path.join(ROOT, "tests", "golden", "gmm_sklearn_cases.npz"))
     for i in (int(v) for v in g["cases"]):
