@@ -238,7 +238,12 @@ int medgp_fit_predict_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, co
  * per patient, then the points in tiles of 64 per workgroup (forward solve on fp64 MFMA).  A point's outputs do not depend on
  * the other points of the call, their order, or how the call is cut into launches (work memory per launch:
  * MEDGP_POSTERIOR_BUDGET_GB, default 2).  meta2 may be NULL for SE / SM.  Like medgp_fit_predict_batch, a call whose
- * per-entry matrices exceed the memory budget fails with MEDGP_ERR_CAPACITY.  All pointers are HOST memory. */
+ * per-entry matrices exceed the memory budget fails with MEDGP_ERR_CAPACITY.
+ * Supported range of the time stamps: |t| <= 2^14 h, of the training observations (medgp_set_patient) AND of the test points: for
+ * Q <= 8 K* is formed from tables cos / sin (w t_i) and cos / sin (w t*), cos(w (t_i - t*)) = cs_i cc + sn_i sc, whose error grows
+ * as |w t| eps.  Up to that limit, at periods down to one hour, mean, var and parts stay within the project's bar of 2 fp32 ulps
+ * of max(|ref|, 1e-3 S) of the posterior of the unshifted patient (tests/test_time_shift_gpu.py, at -2^14, 2^10 and 2^14 h).
+ * All pointers are HOST memory. */
 int medgp_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
                           const int32_t *meta2, const float *t2, float *mean, float *var, float *parts, int32_t *status);
 
@@ -264,6 +269,9 @@ int medgp_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, cons
  * resident together; the call is cut into launches of whole patients within MEDGP_POSTERIOR_BUDGET_GB (default 2), a single
  * patient beyond it fails with MEDGP_ERR_CAPACITY, as does a call whose per-entry matrices exceed the memory budget.  C is
  * factored by one workgroup per patient: made for cohorts of patients with up to a few thousand points each.
+ * Supported range of the time stamps: |t| <= 2^14 h, of the training observations AND of the test points, as medgp_posterior_batch:
+ * for Q <= 8 K** too is formed from cos / sin (w t*) tables of the test points.  cov and samples are held to the 2-ulp bar at that
+ * limit (tests/test_time_shift_gpu.py).
  * All pointers are HOST memory. */
 int medgp_posterior_joint_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
                                 const int32_t *meta2, const float *t2, int nsamp, const double *eps, float *mean, float *var,
@@ -296,7 +304,13 @@ int medgp_posterior_joint_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots
  * other groups, the batch-mates (route pinned) or the launch chunks.  The blocks of a launch chunk (2 m'^2 + 2 m' doubles per
  * group of more than one observation, m' = its size rounded up to 64) stay within MEDGP_POSTERIOR_BUDGET_GB; a single group
  * beyond it fails with MEDGP_ERR_CAPACITY, as does a call whose per-entry matrices exceed the memory budget.  M is factored by
- * one workgroup per group.  medgp_get_factor is valid afterwards (the call forms alpha and L^-1).  All pointers are HOST memory. */
+ * one workgroup per group.  medgp_get_factor is valid afterwards (the call forms alpha and L^-1).
+ * Supported range of the time stamps: |t| <= 2^14 h (medgp_set_patient).  mean and var keep the bar of 2 fp32 ulps over the whole
+ * range.  lpd and total are fp64 outputs of a K formed from the cos / sin (w t_i) tables, and lose |w t| eps like them: within
+ * 1e-10 max(1, |ref|) near the origin (tests/test_loo_gpu.py, |t| <= 200 h), but an fp64 program that forms K from such tables is
+ * itself off by 8.8e-11 at |t| = 2^14 h and a period of 1 h (1.3e-11 at 12 h, 8.5e-13 at 72 h; tests/golden/time_shift_spread.json),
+ * so away from the origin the bound is max(1e-10, 50 x that table error) max(1, |ref|): 4.4e-9 at 2^14 h and 1 h.  The device's worst
+ * there was 8.8e-11 (tests/test_time_shift_gpu.py prints it).  All pointers are HOST memory. */
 int medgp_loo_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int32_t *group,
                     const int32_t *ngroups, float *mean, float *var, double *lpd, double *total, int32_t *status,
                     int32_t *group_status);
@@ -323,7 +337,13 @@ int medgp_loo_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const doub
  * whose per-entry matrices exceed the memory budget fails with MEDGP_ERR_CAPACITY, as medgp_loo_batch does.  With the route
  * pinned a patient's obj and grad bits do not depend on its batch-mates or their order: no atomics, every sum in a fixed order.
  * medgp_get_factor is VALID afterwards: the call forms alpha and L^-1 and leaves both untouched (P overwrites the factor L,
- * which medgp_get_factor does not read).  All pointers are HOST memory. */
+ * which medgp_get_factor does not read).
+ * Supported range of the time stamps: |t| <= 2^14 h (medgp_set_patient).  obj and grad are held to the fp64 budget of
+ * tests/loo_grad_truth.py near the origin; K and the gradient factors come from the cos / sin (w t_i) tables, so at an offset the
+ * budget is the larger of that and M x the error of an fp64 table program there (M = 256 objective, 128 gradient): measured table
+ * errors at 2^14 h and a period of 1 h 2.0e-12 (objective) and 5.2e-11 (gradient), at 12 h 6.9e-14 and 1.0e-11
+ * (tests/golden/time_shift_spread.json); the device's were the same to two digits (tests/test_time_shift_gpu.py).
+ * All pointers are HOST memory. */
 int medgp_loo_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int flag_grad, double *obj,
                    double *grad, int32_t *status);
 
@@ -360,6 +380,14 @@ int medgp_loo_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const doubl
  * project's bar of 2 fp32 ulps of max(|ref|, 1e-3 S); lpd within B max(1, |ref|), B = 50 x the spread of the two fp64
  * restatements recorded in tests/golden/forecast_lpd_spread.json (2.8e-13, so B = 1.4e-11).  The tests print the worst
  * observed errors of every case (pytest -s).
+ * Supported range of the time stamps: |t| <= 2^14 h, of the training observations AND of the test points, as medgp_posterior_batch.
+ * mean and var keep the 2-ulp bar over the whole range.  B = 1.4e-11 holds NEAR THE ORIGIN (|t| <= 200 h, periods of 12 h and
+ * more) only: lpd is an fp64 output of K and K* formed from cos / sin (w t) tables and loses |w t| eps with them.  An fp64 program
+ * that forms its cosines from such tables is off, relative to max(1, |ref|), by 3.7e-13 (|t| <= 200 h), 2.7e-12 (2^10 h) and
+ * 4.4e-11 (2^14 h) at a period of 1 h, by 4.1e-12 at 2^14 h and 12 h, by 5.8e-13 at 2^14 h and 72 h; with 17 components of 1 h,
+ * 4.3e-12, 4.3e-11 and 2.4e-10 (tests/golden/time_shift_spread.json, tests/test_time_shift.py).  Away from the origin the bound is
+ * max(B, 50 x that table error); tests/test_time_shift_gpu.py holds the device to it at -2^14, 2^10 and 2^14 h (the device's
+ * errors there equal the table program's to two digits).
  * All pointers are HOST memory. */
 int medgp_forecast_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
                          const int32_t *meta2, const float *t2, const int32_t *prefix, const float *y2,
