@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 13: medgp_gmm_fit (12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 14: medgp_forecast_grad (13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -393,6 +393,45 @@ int medgp_forecast_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const
                          const int32_t *meta2, const float *t2, const int32_t *prefix, const float *y2,
                          float *mean, float *var, double *lpd, int32_t *status);
 
+/* The h-hours-ahead forecast score as a training objective, with its gradient in the hyper-parameters: what medgp_forecast_batch
+ * reports (the log predictive density of each observation given what was known some hours before it), made optimisable.  The
+ * reference evaluates on such forecasts (medgpc/evaluation/evals.py, main_one_test.cpp:269-300) but has no such output; the
+ * definition is the long-double restatement in tests/forecast_grad_truth.py.  Observations are in the caller's upload order,
+ * 0 .. n-1; K is the matrix that is factored, noise included.  Scored observation i has a history length p_i in [0, i]:
+ *   a_i = K[0:p,0:p]^-1 K[0:p,i],  mean_i = a_i^T y[0:p],  var_i = K[i,i] - K[0:p,i]^T a_i,  r_i = y_i - mean_i,
+ *   lpd_i = -1/2 log(2 pi var_i) - 1/2 r_i^2 / var_i,        J = - sum_{i scored} lpd_i,
+ * lpd_i being exactly medgp_forecast_batch's lpd of a test point placed at observation i (meta2 = meta_i, t2 = t_i, y2 = y_i,
+ * prefix = p_i).  With u_i = [-a_i on [0, p_i) | 1 at i | 0 elsewhere] and beta_i = [K[0:p,0:p]^-1 y[0:p] on [0, p_i) | 0],
+ *   dJ / d theta_h = 1/2 tr(W_fc dK / d theta_h),
+ *   W_fc = sum_i [ g_i u_i u_i^T - e_i (beta_i u_i^T + u_i beta_i^T) ],   g_i = (1 - r_i^2 / var_i) / var_i,   e_i = r_i / var_i:
+ * the marginal-likelihood gradient with W_fc in the place of W.  Everything comes from ONE factorisation per patient
+ * (kernels_forecast_grad.h).  p_i = i for every i is the chain rule of the likelihood: J is the nlml of medgp_nlml_grad without
+ * a prior and W_fc = K^-1 - alpha alpha^T.
+ * nbatch, slots, theta, status as medgp_loo_grad (no n > 2 guard; status[b] = jitter rounds or -1).
+ *   offsets[nbatch + 1] index prefix: patient b owns offsets[b + 1] - offsets[b] = n_b values, in the caller's observation order.
+ *   prefix[i] = -1: observation i is not scored; otherwise 0 <= prefix[i] <= i.  A value outside that range, offsets[0] != 0 or a
+ *     range length different from n_b: MEDGP_ERR_ARG before any device work.  prefix == NULL means prefix[i] = i, everything
+ *     scored (offsets may then be NULL too).  The library does not look at the time stamps to decide what is "earlier"
+ *     (medgp_forecast_batch's rule; medgp_amd.forecast.training_prefix builds the table from times and a horizon).  A patient not
+ *     uploaded grouped by output is factored on its caller-order copy; the gradient's tile reductions then run against the
+ *     grouped copy, which the operands were stored for.
+ *   obj[b] = J plus the prior term exactly as medgp_nlml_grad adds it for that slot; a patient without a scored observation has
+ *     J = 0 and the prior's gradient alone.  log 2 pi uses the context's pi (medgp_set_pi).
+ *   grad[b * H ..], flag_grad: as medgp_loo_grad (0 = the objective only, the same bits of obj; any other bit, or grad == NULL with
+ *     flag_grad = 1: MEDGP_ERR_ARG before any device work).
+ * After k jitter rounds every quantity is that of the matrix that was factored, K + k diag(sigma^2), and the noise gradient is
+ * not scaled by 1 + k.  A patient with status[b] < 0 gets NaN obj and grad.  All three covariance families; Q <= 16 only: Q > 16
+ * returns MEDGP_ERR_ARG, and MEDGP_V0 is not honoured by this call.  A call whose per-entry matrices exceed the memory budget
+ * fails with MEDGP_ERR_CAPACITY (no memory waves); a gradient call holds one more ldn^2 matrix per entry (T) in a buffer of its own.
+ * With the route pinned a patient's obj and grad bits do not depend on its batch-mates or their order: no atomics, every sum in a
+ * fixed order.  medgp_get_factor is REFUSED afterwards (MEDGP_ERR_ARG): the call overwrites L and L^-1 with its operands.
+ * Supported range of the time stamps: |t| <= 2^14 h (medgp_set_patient).  obj and grad are held to the fp64 budget of
+ * tests/forecast_grad_truth.py near the origin (|t| <= 200 h); K and the gradient factors come from the cos / sin (w t_i) tables
+ * and lose |w t| eps with them away from it, as medgp_loo_grad's.
+ * All pointers are HOST memory. */
+int medgp_forecast_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                        const int32_t *prefix, int flag_grad, double *obj, double *grad, int32_t *status);
+
 /* Posterior of the latent SLOPE at the test points, next to the posterior of the value: is the covariate rising or falling at t*,
  * how fast, and how sure is the model.  The derivative of a GP is a GP, and the SE / SM / LMC-SM covariances are differentiable
  * in closed form.
@@ -628,6 +667,11 @@ int medgp_profile_enable(medgp_ctx *ctx, int enable);
    (medgp_components_batch) and of k_functional (medgp_functional_batch) are accounted under the entry "k_posterior", the one
    k_functional_prep launch per size class of that call under "k_prep", so the table and every kernel id in it stay what they were */
 int medgp_profile_num_kernels(void);
+/* The table of medgp_profile_num_kernels is frozen at its 23 entries (callers index it).  Kernels that get entries of their own
+   since -- medgp_forecast_grad's k_fc_vec, k_fc_t, k_fc_scan, k_fc_qm, k_fc_tables, k_fc_wgrad -- are appended behind it: ids
+   [medgp_profile_num_kernels(), medgp_profile_num_kernels_all()) are valid for medgp_profile_kernel_name, medgp_profile_read and
+   medgp_profile_enable(2 + k) like the ids before them. */
+int medgp_profile_num_kernels_all(void);
 const char *medgp_profile_kernel_name(int k);
 /* synchronises, then returns accumulated milliseconds and launch count of kernel k since the
  * last medgp_profile_reset */

@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at", "medgp_gmm_fit",
 ]
 
@@ -96,6 +96,7 @@ def load():
     lib.medgp_posterior_joint_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, fp, fp, fp, fp, i32p, i32p]
     lib.medgp_loo_batch.argtypes = [vp, C.c_int, i32p, dp, i32p, i32p, fp, fp, dp, dp, i32p, i32p]
     lib.medgp_loo_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, i32p]
+    lib.medgp_forecast_grad.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, C.c_int, dp, dp, i32p]
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
     lib.medgp_trend_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, fp, fp, i32p]
     lib.medgp_components_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, i32p]
@@ -104,6 +105,7 @@ def load():
     lib.medgp_synchronize.argtypes = [vp]
     lib.medgp_profile_enable.argtypes = [vp, C.c_int]
     lib.medgp_profile_num_kernels.restype = C.c_int
+    lib.medgp_profile_num_kernels_all.restype = C.c_int
     lib.medgp_profile_kernel_name.argtypes = [C.c_int]
     lib.medgp_profile_kernel_name.restype = C.c_char_p
     lib.medgp_profile_read.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_int64)]
@@ -796,6 +798,34 @@ class Context:
                                            _ptr(obj, C.c_double), _ptr(grad, C.c_double), _ptr(status, C.c_int32)))
         return obj, grad, status
 
+    def forecast_grad(self, slots, theta, prefixes=None, flag_grad=1):
+        """medgp_forecast_grad: the negative forecast score J = - sum_i lpd_i (plus the prior term, as nlml_grad) and its gradient in
+        theta.  prefixes: one int array per patient, in the order the patient was uploaded: prefixes[b][i] = the number of leading
+        observations observation i is predicted from (0 <= p <= i), or -1 = not scored (medgp_amd.forecast.training_prefix builds it
+        from times and a horizon); None = every observation from all before it, the chain rule of the likelihood.
+        Returns (obj[nbatch], grad[nbatch, H] or None, status[nbatch])."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(slots.shape[0], self.H)
+        nb = slots.shape[0]
+        flag = int(flag_grad)
+        offsets = prefix = None
+        if prefixes is not None:
+            if len(prefixes) != nb:
+                raise ValueError(f"{len(prefixes)} prefix arrays for {nb} patients")
+            pl = [np.asarray(p, dtype=np.int32).ravel() for p in prefixes]
+            offsets = np.zeros(nb + 1, np.int64)
+            offsets[1:] = np.cumsum([p.shape[0] for p in pl])
+            prefix = np.ascontiguousarray(np.concatenate(pl) if pl else np.zeros(0, np.int32), dtype=np.int32)
+            if prefix.shape[0] == 0:
+                prefix = np.zeros(1, np.int32)   # (never read: every range is empty)
+        obj = np.empty(nb)
+        grad = np.empty((nb, self.H)) if flag & 1 else None
+        status = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_forecast_grad(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), _ptr(offsets, C.c_int64),
+                                                _ptr(prefix, C.c_int32), flag, _ptr(obj, C.c_double), _ptr(grad, C.c_double),
+                                                _ptr(status, C.c_int32)))
+        return obj, grad, status
+
     def synchronize(self):
         self._chk(self._lib.medgp_synchronize(self._h))
 
@@ -804,7 +834,7 @@ class Context:
         """on: bracket every launch with HIP events; only='k_cholinv': just the launches of that kernel."""
         mode = int(bool(on))
         if on and only is not None:
-            names = [self._lib.medgp_profile_kernel_name(k).decode() for k in range(self._lib.medgp_profile_num_kernels())]
+            names = [self._lib.medgp_profile_kernel_name(k).decode() for k in range(self._lib.medgp_profile_num_kernels_all())]
             mode = 2 + names.index(only)
         self._chk(self._lib.medgp_profile_enable(self._h, mode))
 
@@ -813,7 +843,7 @@ class Context:
 
     def profile_read(self):
         out = {}
-        for k in range(self._lib.medgp_profile_num_kernels()):
+        for k in range(self._lib.medgp_profile_num_kernels_all()):
             ms, cnt = C.c_double(), C.c_int64()
             self._chk(self._lib.medgp_profile_read(self._h, k, C.byref(ms), C.byref(cnt)))
             out[self._lib.medgp_profile_kernel_name(k).decode()] = (ms.value, cnt.value)

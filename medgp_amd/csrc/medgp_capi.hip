@@ -22,6 +22,7 @@
 #include "kernels_functional_joint.h"
 #include "kernels_loo.h"
 #include "kernels_loo_grad.h"
+#include "kernels_forecast_grad.h"
 
 #include <algorithm>
 #include <chrono>
@@ -36,8 +37,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -82,9 +83,11 @@ struct Arena {
 //   medgp_functional_batch (T terms, F functionals; the terms' covariates and times travel as the posterior call's points, the outputs
 //   in its mean / var): BUF_FUNC_D the doubles [weight T | rsum T | q_g F | cos T Q | sin T Q], BUF_FUNC_I the ints [toff F + 1 | fun T];
 //   medgp_functional_joint_batch: besides, the joint posterior's patient and tile-pair tables and its float covariance blocks (fcov)
+//   medgp_forecast_grad: BUF_GVEC holds its per-entry vectors [g / 2 | e | lpd | -], BUF_FC_TAB the per-entry integer tables
+//   (forecast_grad_tables.h), BUF_FC_T the matrix T = U Mbar of every entry, laid out like Kmat (gradient calls only)
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -853,7 +856,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 13; }
+int medgp_abi_version(void) { return 14; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2392,6 +2395,116 @@ int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     return MEDGP_OK;
 }
 
+// The negative forecast score and its gradient (kernels_forecast_grad.h).  ONE pipeline run in the CALLER's order (as
+// medgp_forecast_batch: the history of an observation is a leading block of that order) with U = L^-T, then per size class, in
+// stream order: k_fc_vec (var, r, g, e, lpd; then J -> scal[2]), and for a gradient k_fc_t (T = U Mbar into the call's own buffer),
+// k_fc_scan (running sums of U diag(z), in place), k_fc_qm (Qm into the dead Kmat block).  T and Qm have their rows at the positions of
+// the GROUPED order, so the gradient body runs against the grouped patient copy: once every class has stored its operands, bslot is
+// pointed at the grouped slots, and per class k_fc_tables redoes cos / sin for that copy, k_fc_wgrad forms the W_fc tiles -> slab,
+// wdiag, and the nlml gradient's own k_slabsum and k_epilogue finish, the latter told to report J instead of the nlml.
+// flag_grad = 0 runs k_fc_vec and k_epilogue only.  The cached batch selection is dropped at the end: the next call uploads its own
+// bslot, and medgp_get_factor is refused (L and U are overwritten).
+int medgp_forecast_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets, const int32_t *prefix,
+                        int flag_grad, double *obj, double *grad, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || !obj) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
+    if (flag_grad && !grad) return fail(c, MEDGP_ERR_ARG, "grad is NULL with flag_grad set");
+    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_forecast_grad supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds Qm here", c->rules.Q);
+    int rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    std::vector<int> hn(nbatch);
+    for (int b = 0; b < nbatch; b++) hn[b] = c->h_n[slots[b]];
+    FcError fe;
+    if (!fc_check(nbatch, hn.data(), offsets, prefix, &fe)) {
+        if (fe.b < 0) return fail(c, MEDGP_ERR_ARG, "offsets is NULL with a prefix table");
+        if (fe.i < 0) return fail(c, MEDGP_ERR_ARG, "patient %d: offsets give it %lld prefix values, it has %lld observations (offsets[0] must be 0)", fe.b, fe.value, fe.expect);
+        return fail(c, MEDGP_ERR_ARG, "prefix[%lld] = %lld outside [-1, %lld] (patient %d)", fe.i, fe.value, fe.expect, fe.b);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = set_batch(c, nbatch, slots, true, true))) return rc;
+    const BatchPlan &P = c->plan;
+    // the per-entry tables, laid out like the vectors of the plan (class offset, then entry by entry)
+    std::vector<int> htab((size_t)FC_TAB_INTS * P.need_vec, 0);
+    bool switched = false;   // some entry was factored on its caller-order copy
+    for (const SizeClass &k : P.cls)
+        for (int e = 0; e < k.count; e++) {
+            const int b = P.order[k.b0 + e], s = slots[b];
+            const bool ident = c->h_perm_identity[s] != 0;
+            switched = switched || !ident;
+            fc_fill_entry(hn[b], k.ld, prefix ? prefix + offsets[b] : nullptr, ident ? nullptr : c->h_perm[s].data(),
+                          htab.data() + (size_t)FC_TAB_INTS * (k.off_vec + (size_t)e * k.ld));
+        }
+    if ((rc = buf_ensure(c, BUF_GVEC, 4 * P.need_vec * sizeof(double)))) return rc;
+    if (flag_grad && (rc = buf_ensure(c, BUF_FC_T, P.need_mat * sizeof(double)))) return rc;
+    if ((rc = upload_table(c, BUF_FC_TAB, htab))) return rc;
+    double *gvec = buf<double>(c, BUF_GVEC), *tmat = buf<double>(c, BUF_FC_T);
+    const int *dtab = buf<int>(c, BUF_FC_TAB);
+    const size_t H = c->H;
+    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
+    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    // the generic kernels (MEDGP_V0) keep W where Qm goes: this call always takes the templated ones
+    const bool v0 = c->rules.use_v0;
+    c->rules.use_v0 = false;
+    rc = factor_run(c, nbatch, theta, true, false);
+    c->rules.use_v0 = v0;
+    // whatever happens from here on, the next call selects its batch afresh and no factor is on offer
+    c->last_nbatch = 0;
+    c->last_has_inverse = false;
+    if (rc) return rc;
+    const double log2pi = std::log(2.0 * c->pi);
+    for (const SizeClass &k : P.cls) {
+        const MedgpDev V = class_view(c, P, k);
+        double *vec = gvec + 4 * k.off_vec;
+        const int *tab = dtab + FC_TAB_INTS * k.off_vec;
+        const int nb = k.count, nt64 = k.nbmax;
+        { Launcher l(c, KID_FC_VEC); hipLaunchKernelGGL(k_fc_vec, dim3(4 * nt64, nb), dim3(256), 0, c->stream, V, vec, tab, 0, log2pi); }
+        { Launcher l(c, KID_FC_VEC); hipLaunchKernelGGL(k_fc_vec, dim3(1, nb), dim3(256), 0, c->stream, V, vec, tab, 1, log2pi); }
+        if (!flag_grad) continue;
+        double *Tm = tmat + k.off_mat;
+        { Launcher l(c, KID_FC_T); hipLaunchKernelGGL(k_fc_t, dim3(nt64 * nt64, nb), dim3(WG_THREADS), 0, c->stream, V, Tm, tab, nt64); }
+        { Launcher l(c, KID_FC_SCAN); hipLaunchKernelGGL(k_fc_scan, dim3(16 * nt64, nb), dim3(256), 0, c->stream, V, tab); }
+        { Launcher l(c, KID_FC_QM); hipLaunchKernelGGL(k_fc_qm, dim3(nt64, 16 * nt64, nb), dim3(256), 0, c->stream, V, Tm, vec, tab); }
+    }
+    if (flag_grad && switched) {   // every class has stored its operands: the gradient body sees the grouped copies
+        void *pin = nullptr;
+        if ((rc = pin_stage(c, sizeof(int) * nbatch, &pin))) return rc;
+        int *hp = (int *)pin;
+        for (int i = 0; i < nbatch; i++) hp[i] = slots[P.order[i]];
+        HIPCHK(c, hipMemcpyAsync(c->d_bslot, hp, sizeof(int) * nbatch, hipMemcpyHostToDevice, c->stream));
+    }
+    for (const SizeClass &k : P.cls) {
+        const MedgpDev V = class_view(c, P, k);
+        const int nb = k.count, nt64 = k.nbmax;
+        if (flag_grad) {
+            const int *tab = dtab + FC_TAB_INTS * k.off_vec;
+            const double *Tm = tmat + k.off_mat;
+            if (switched) { Launcher l(c, KID_FC_TABLES); hipLaunchKernelGGL(k_fc_tables, dim3(nb, (V.Q * V.ldn + PREP_CHUNK - 1) / PREP_CHUNK), dim3(256), 0, c->stream, V); }
+            const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
+            const dim3 tg(wg.grid), tb(WG_THREADS);
+            {
+                Launcher l(c, KID_FC_WGRAD);   // (Q <= 16 was checked)
+                with_q16(V.Q, [&](auto q, auto q0) {
+                    hipLaunchKernelGGL((k_fc_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, Tm, tab, nb, wg.wg_tiles, wg.nbp);
+                });
+            }
+            const int nbins3 = 3 * V.Q * tri(V.D);
+            Launcher l(c, KID_EPILOGUE);
+            hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V);
+        }
+        Launcher l(c, KID_EPILOGUE);
+        const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
+        hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, c->d_theta, flag_grad, 1, c->d_nlml, c->d_grad, c->d_status_out, 1);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(obj, c->d_nlml, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    if (flag_grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * H, hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_retired(c);
+    return MEDGP_OK;
+}
+
 #ifdef MEDGP_STAMPS
 // diagnostic build only: read (and clear) the phase counters of diag_factor_wave
 #ifdef MEDGP_DSTAMPS
@@ -2432,7 +2545,9 @@ int medgp_profile_enable(medgp_ctx *c, int enable) {
     c->profile_only = (enable >= 2 && enable - 2 < KID_COUNT) ? enable - 2 : -1;
     return MEDGP_OK;
 }
-int medgp_profile_num_kernels(void) { return KID_COUNT; }
+// the table existing callers index is frozen at its 23 entries (include/medgp_hip.h); entries added since are reached through the _all count
+int medgp_profile_num_kernels(void) { return KID_FORECAST + 1; }
+int medgp_profile_num_kernels_all(void) { return KID_COUNT; }
 const char *medgp_profile_kernel_name(int k) { return (k >= 0 && k < KID_COUNT) ? kKernelNames[k] : ""; }
 int medgp_profile_read(medgp_ctx *c, int k, double *ms_total, int64_t *launches) {
     if (!c || k < 0 || k >= KID_COUNT) return MEDGP_ERR_ARG;

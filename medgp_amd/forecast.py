@@ -4,7 +4,8 @@ from Context.forecast / medgp_forecast_batch).
 rolling_origin() builds the points and prefixes of "what does the model predict at time t from what was known h hours
 before t" (ref: main_one_test.cpp:269-300 builds such "past" sets one observation at a time).  score() restates the
 quantities of the reference's evaluation (ref: medgpc/evaluation/evals.py:7-51: per feature, the mean absolute error and the
-percentage of observations inside the 95 % interval) and adds the mean log predictive density.
+percentage of observations inside the 95 % interval) and adds the mean log predictive density.  training_prefix() builds the
+history table of Context.forecast_grad / medgp_forecast_grad, which trains on that log predictive density.
 """
 import numpy as np
 
@@ -38,6 +39,24 @@ def rolling_origin(meta, t, y, horizons):
     k = hs.shape[0]
     return (np.tile(m, k), np.tile(t, k), np.tile(y, k),
             (np.concatenate(prefix) if k else np.zeros(0)).astype(np.int32), np.repeat(np.arange(k, dtype=np.int32), n))
+
+
+def training_prefix(t, horizon, min_history=0):
+    """The prefix table of Context.forecast_grad / medgp_forecast_grad for ONE patient whose observations are sorted by time
+    (ValueError otherwise; ties are allowed): per observation i the history length #{k : t_k < t_i - horizon}, i.e. rolling_origin's
+    prefix for that horizon, and -1 (not scored) where that count is below min_history.  horizon in hours, >= 0; returns int32 [n]."""
+    t = np.asarray(t, np.float32).ravel()
+    if t.shape[0] > 1 and np.any(np.diff(t) < 0):
+        raise ValueError("training_prefix needs the observations sorted by time")
+    h = float(horizon)
+    if not np.isfinite(h) or h < 0:
+        raise ValueError("horizon must be finite and >= 0")
+    if int(min_history) < 0:
+        raise ValueError("min_history must be >= 0")
+    t64 = t.astype(np.float64)
+    p = np.searchsorted(t64, t64 - h, side="left").astype(np.int32)
+    p[p < int(min_history)] = -1
+    return p
 
 
 def score(meta2, y2, hidx, mean, var, lpd=None, D=None, nh=None):
