@@ -58,7 +58,7 @@ __global__ void __launch_bounds__(WG_THREADS) k_loo_kinv(MedgpDev L, int nbatch,
     const double *U = L.Linv + (size_t)T.b * ld * ld;
     double *P = L.Kmat + (size_t)T.b * ld * ld;
 
-    const WgAcc acc = wg_phase1(smem, T, U, 64 * I, LooMaskHook());
+    const WgAcc acc = wg_phase1<false>(smem, T, U, 64 * I, LooMaskHook());   // (the masked U would allow the skip of zero stretches; not taken up here)
     wg_phase2(acc, smem, T);   // diagonal tile: the column strips right of a wave's rows come from the mirror image
     for (int x = T.tid; x < 64 * 64; x += WG_THREADS) {
         const int r = x >> 6, cc = x & 63;
@@ -163,7 +163,7 @@ __global__ void __launch_bounds__(WG_THREADS, WG_MINWAVES) k_loo_wgrad(MedgpDev 
     const double *P = L.Kmat + (size_t)T.b * T.ld * T.ld;
     const double *svec = vec + (size_t)T.b * 4 * T.ld + T.ld, *vvec = svec + T.ld;
 
-    const WgAcc acc = wg_phase1(smem, T, P, 0, LooScaleHook{svec});   // G = P diag(s) P
+    const WgAcc acc = wg_phase1<false>(smem, T, P, 0, LooScaleHook{svec});   // G = P diag(s) P: full rows from column 0, no zero stretches
     wg_phase2(acc, smem, T);
     wg_phase3<QT, Q0>(L, T, smem, rowc, LooElem{vvec});
 }

@@ -9,7 +9,8 @@
 // One workgroup (4 waves) per lower 64x64 tile (I, J) of one patient:
 //   phase 1  W tile = U[I rows] U[J rows]^T on fp64 MFMA (U = L^-T from k_cholinv; k runs over columns >= 64 I);
 //            the J-row fragments are staged through LDS (shared by the 4 waves), the I-row fragments stream
-//            from HBM with 16-byte loads.
+//            from HBM with 16-byte loads.  The first 16 w columns are zero in all of wave w's rows (U is upper
+//            triangular): their MFMAs are not issued (WG_MFMA_SKIP_HALVES / _CHUNKS), same bits.
 //   phase 2  tile -> LDS (aliases the staging buffers).
 //   phase 3  lane = column j, wave = 16-row group: per element one fp64 exp per mixture component (cos/sin of the
 //            time difference come from the per-observation tables by the angle-difference identity).
@@ -103,8 +104,61 @@ struct WgAcc { v4d a[4]; };   // a[ct]: rows 16w.. of block I, cols 16ct.. of bl
             _Pragma("unroll") for (int s = 0; s < 2; s++) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[h][s], bf[s], acc[ct], 0, 0, 0); \
         }
 
+// The zero head of the streamed rows.  When M is upper triangular and the k range starts at the tile's own diagonal block (k0 = 64 I),
+// row 64 I + 16 w + r is zero left of column 64 I + 16 w: the first 16 w columns of the range are zero in ALL 16 streamed rows of wave
+// w.  Their products are exact zeros, and adding +-0 leaves an accumulator that started at +0 as it is, bit for bit (finite operands:
+// entries whose factorisation failed never get here), so their MFMAs are not issued at all; nothing else changes (the wave still
+// stages, streams and meets the barriers).  Two forms, both wave-uniform scalar branches:
+//   WG_MFMA_SKIP_CHUNKS  one guard around the whole block of a chunk: 16 w / WG_KC whole chunks, chunk 0 for the waves 2 and 3
+//                        (8 of the 12 zero stretches of 8 columns of a tile).  The diagonal tiles, whose block already has a guard per
+//                        column tile (ctmax), and the PF = 2 loop of k_wgrad take it: any second guard inside such a block -- per 8
+//                        columns, per half, nested, if / else -- made the compiler keep two copies of the 32 accumulator registers
+//                        and copy them inside the loop (k_wgrad<5, 0, 1> at 132 .. 168 VGPRs: three workgroups per CU).
+//   WG_MFMA_SKIP_HALVES  the off-diagonal tiles (all four column tiles in use, so no guard per column tile): one guard per 16-column
+//                        half of a chunk, all 12 zero stretches (wave 1: the first half of chunk 0, wave 2: chunk 0, wave 3: chunk 0
+//                        and the first half of chunk 1).  k_wgrad<5, 0, 1>: 128 VGPRs, no scratch, four workgroups per CU as before --
+//                        but with the guards' test written in columns (16 w - 32 c <= 0 / <= 16) the same loop took 156.
+// Registers of every form that was tried, and the ones to re-check after an edit here: profiles/wgrad_zero_work_resources.txt;
+// timings: profiles/wgrad_zero_work_timing.txt; the bits: tests/test_wgrad_zero_work_gpu.py.
+__device__ __forceinline__ int wg_zero_chunks(int w) { return 16 * w / WG_KC; }
+#define WG_MFMA_PLAIN(ac, buf, c) WG_CHUNK_MFMA(ac, buf)
+#define WG_MFMA_SKIP_CHUNKS(ac, buf, c) if ((c) >= wg_zero_chunks(T.w)) { WG_CHUNK_MFMA(ac, buf) }
+#define WG_HALF_MFMA(ac, buf, h0) \
+    _Pragma("unroll") for (int h = (h0); h < (h0) + 2; h++) \
+        _Pragma("unroll") for (int ct = 0; ct < 4; ct++) { \
+            const v2d bf = *(const v2d *)&Bs[buf][16 * ct + li][8 * h + 2 * g]; \
+            _Pragma("unroll") for (int s = 0; s < 2; s++) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[h][s], bf[s], acc[ct], 0, 0, 0); \
+        }
+#define WG_MFMA_SKIP_HALVES(ac, buf, c) \
+    { \
+        const int zs_ = 2 * T.w - (WG_KC / 8) * (c);   /* zero stretches of 8 columns left at the head of this chunk */ \
+        if (zs_ <= 0) { WG_HALF_MFMA(ac, buf, 0) } \
+        if (zs_ <= 2) { WG_HALF_MFMA(ac, buf, 2) } \
+    }
+
+// the chunk loop of wg_phase1, MFMA_BLOCK(ac, buf, c) = one of the three forms above
+#define WG_PHASE1_LOOP(MFMA_BLOCK) \
+    for (int c = 0; c < nch; c++) { \
+        const int buf = c & 1; \
+        v2d ac[4]; \
+        _Pragma("unroll") for (int h = 0; h < 4; h++) ac[h] = an[h]; \
+        if (c + 1 < nch) { \
+            const int kc = (c + 1) * WG_KC; \
+            _Pragma("unroll") for (int u = 0; u < 4; u++) bst[u] = hk.staged(*(const v2d *)(Bsrc + kc + 2 * u), c + 1, brow, k0 + kc + scg + 2 * u); \
+            _Pragma("unroll") for (int h = 0; h < 4; h++) an[h] = hk.streamed(*(const v2d *)(Arow + kc + 8 * h), c + 1, arow, k0 + kc + 2 * g + 8 * h); \
+        } \
+        MFMA_BLOCK(ac, buf, c) \
+        if (c + 1 < nch) { \
+            _Pragma("unroll") for (int u = 0; u < 4; u++) *(v2d *)&Bs[buf ^ 1][srow][scg + 2 * u] = bst[u]; \
+        } \
+        __syncthreads(); \
+    }
+
 // Phase 1: the tile  sum over the columns k >= k0 of M[I rows][k] M[J rows][k], one chunk of WG_KC columns prefetched ahead.
-template <class Hook>
+// UPPER: the caller's promise that M BEHIND THE HOOK is upper triangular with exact zeros below the diagonal of its diagonal blocks and
+// that k0 = 64 I; the MFMAs of the streamed rows' zero head are then skipped (above).  A hook that turns a structural zero into
+// something else, or another k range (k_loo_wgrad: rows of the full P from column 0), must leave it false: the loop is then the plain one.
+template <bool UPPER, class Hook>
 __device__ __forceinline__ WgAcc wg_phase1(double *smem, const WgTile T, const double *M, int k0, const Hook hk) {
     double (*Bs)[64][WG_KC + 2] = (double (*)[64][WG_KC + 2])smem;   // Bs[2][64][34]
     v4d acc[4];
@@ -125,24 +179,12 @@ __device__ __forceinline__ WgAcc wg_phase1(double *smem, const WgTile T, const d
 #pragma unroll
     for (int u = 0; u < 4; u++) *(v2d *)&Bs[0][srow][scg + 2 * u] = bst[u];
     __syncthreads();
-    for (int c = 0; c < nch; c++) {
-        const int buf = c & 1;
-        v2d ac[4];
-#pragma unroll
-        for (int h = 0; h < 4; h++) ac[h] = an[h];
-        if (c + 1 < nch) {
-            const int kc = (c + 1) * WG_KC;
-#pragma unroll
-            for (int u = 0; u < 4; u++) bst[u] = hk.staged(*(const v2d *)(Bsrc + kc + 2 * u), c + 1, brow, k0 + kc + scg + 2 * u);
-#pragma unroll
-            for (int h = 0; h < 4; h++) an[h] = hk.streamed(*(const v2d *)(Arow + kc + 8 * h), c + 1, arow, k0 + kc + 2 * g + 8 * h);
-        }
-        WG_CHUNK_MFMA(ac, buf);
-        if (c + 1 < nch) {
-#pragma unroll
-            for (int u = 0; u < 4; u++) *(v2d *)&Bs[buf ^ 1][srow][scg + 2 * u] = bst[u];
-        }
-        __syncthreads();
+    if constexpr (!UPPER) {
+        WG_PHASE1_LOOP(WG_MFMA_PLAIN)
+    } else if (T.I != T.J) {   // workgroup-uniform
+        WG_PHASE1_LOOP(WG_MFMA_SKIP_HALVES)
+    } else {
+        WG_PHASE1_LOOP(WG_MFMA_SKIP_CHUNKS)
     }
     return WgAcc{{acc[0], acc[1], acc[2], acc[3]}};
 }
@@ -321,7 +363,7 @@ __global__ void __launch_bounds__(WG_THREADS, WG_MINWAVES) k_wgrad(MedgpDev L, i
 #define WSTAMP(k) do {} while (0)
 #endif
     WgAcc A;
-    if constexpr (PF == 1) A = wg_phase1(smem, T, U, 64 * T.I, WgNoHook());
+    if constexpr (PF == 1) A = wg_phase1<true>(smem, T, U, 64 * T.I, WgNoHook());   // k_cholinv / the look-ahead chain zero U's diagonal blocks below the diagonal
     else {
         // PF register sets, set s carries the chunks c = s (mod PF): a set is refilled (chunk c + PF) as soon as its A fragment has been
         // copied out; its staged J rows go to LDS one iteration before they are used (the LDS stays double buffered)
@@ -360,7 +402,7 @@ __global__ void __launch_bounds__(WG_THREADS, WG_MINWAVES) k_wgrad(MedgpDev L, i
 #pragma unroll
                     for (int h = 0; h < 4; h++) an[st][h] = *(const v2d *)(Arow + (c + PF) * WG_KC + 8 * h);
                 }
-                WG_CHUNK_MFMA(ac, (st & 1));
+                WG_MFMA_SKIP_CHUNKS(ac, (st & 1), c)   // U from its diagonal block on, as wg_phase1<true>
                 if (c + 1 < nch) {
 #pragma unroll
                     for (int u = 0; u < 4; u++) *(v2d *)&Bs[(st + 1) & 1][srow][scg + 2 * u] = bst[(st + 1) % PF][u];
