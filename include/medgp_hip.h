@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 14: medgp_forecast_grad (13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 15: medgp_lgo_grad (14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -346,6 +346,47 @@ int medgp_loo_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const doub
  * All pointers are HOST memory. */
 int medgp_loo_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int flag_grad, double *obj,
                    double *grad, int32_t *status);
+
+/* The negative leave-group-out log pseudo-likelihood as a training objective, with its gradient in the hyper-parameters: what
+ * medgp_loo_batch reports for any partition of a patient's observations (a covariate from the other covariates, a time window from
+ * the rest of the stay), made optimisable.  medgp_loo_grad is its special case of singleton groups.  The reference has no such
+ * output; the definition is the long-double restatement in tests/lgo_grad_truth.py.  K is the matrix that was factored (noise
+ * included), P = K^-1, alpha = P y, and B_g the ascending index set of every non-empty group g >= 0:
+ *   M_g = P[B_g, B_g],   r_g = M_g^-1 alpha_{B_g},
+ *   lpd_g = -1/2 alpha_{B_g}^T r_g + 1/2 log det M_g - |B_g| / 2 log 2 pi                      (exactly medgp_loo_batch's lpd),
+ *   J = - sum_g lpd_g,
+ *   S = sum_g E_g (M_g^-1 + r_g r_g^T) E_g^T     (block-"diagonal" on the groups' index sets, zero on id -1),
+ *   r = sum_g E_g r_g,   v = P r,
+ *   dJ / d theta_h = 1/2 tr(W_lgo dK / d theta_h),     W_lgo = P S P - (alpha v^T + v alpha^T):
+ * the marginal-likelihood gradient with W_lgo in the place of W = K^-1 - alpha alpha^T.  All groups singletons: W_lgo = W_loo of
+ * medgp_loo_grad.  One group holding all n observations: J is the nlml of medgp_nlml_grad without a prior and W_lgo = W.
+ * nbatch, slots, theta, status as medgp_loo_grad (no n > 2 guard; status[b] = jitter rounds or -1).
+ *   group, ngroups: as medgp_loo_batch -- group[i] in [-1, ngroups[b]), concatenated by patient in call order, in the caller's
+ *     observation order; -1 = never held out.  An id outside the range, a negative ngroups[b], or ngroups == NULL with group ids:
+ *     MEDGP_ERR_ARG before any device work.  group == NULL is classic LOO: the call is medgp_loo_grad's, bit for bit (ngroups must
+ *     be NULL too; G_b = n_b).
+ *   obj[b] = J plus the prior term exactly as medgp_nlml_grad adds it for that slot; without a prior it is -total[b] of
+ *     medgp_loo_batch with the same groups.  An empty group contributes 0; a patient with no scored observation has J = 0 and the
+ *     prior's gradient alone.  log 2 pi uses the context's pi (medgp_set_pi).
+ *   grad[b * H ..], flag_grad: as medgp_loo_grad (0 = the objective only: neither P nor S is formed, the same bits of obj; any other
+ *     bit, or grad == NULL with flag_grad = 1: MEDGP_ERR_ARG before any device work).
+ *   group_status (may be NULL): laid out as medgp_loo_batch's; 0 ok, -1 when the factorisation of M_g met a pivot <= 0 or NaN: that
+ *     patient's obj and grad are NaN then, other patients are untouched.  A patient with status[b] < 0 gets NaN obj and grad and
+ *     group_status -1.
+ * After k jitter rounds every quantity is that of the matrix that was factored, K + k diag(sigma^2), and the noise gradient is not
+ * scaled by 1 + k.  All three covariance families; Q <= 16 only: Q > 16 returns MEDGP_ERR_ARG, and MEDGP_V0 is not honoured by this
+ * call.  A call whose per-entry matrices exceed the memory budget fails with MEDGP_ERR_CAPACITY (no memory waves), as does a single
+ * group whose block (2 m'^2 + 2 m' doubles, m' = its size rounded up to 64) exceeds MEDGP_POSTERIOR_BUDGET_GB; the blocks of a launch
+ * chunk stay within that budget, and a gradient call holds one more ldn^2 matrix per entry (P S) in a buffer of its own.
+ * No atomics, every sum in a fixed order over the patient's own operands: with the route pinned a patient's obj and grad bits do not
+ * depend on its batch-mates, their order, the labels of its groups or the launch chunks.  medgp_get_factor is VALID afterwards (P
+ * overwrites the factor L, which it does not read; L^-1, alpha and the log determinant are left untouched).
+ * Supported range of the time stamps: |t| <= 2^14 h (medgp_set_patient).  obj and grad are held to the fp64 budget of
+ * tests/lgo_grad_truth.py near the origin (|t| <= 200 h); K and the gradient factors come from the cos / sin (w t_i) tables and lose
+ * |w t| eps with them away from it, as medgp_loo_grad's.
+ * All pointers are HOST memory. */
+int medgp_lgo_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int32_t *group,
+                   const int32_t *ngroups, int flag_grad, double *obj, double *grad, int32_t *status, int32_t *group_status);
 
 /* Rolling-origin forecasts: every test point predicted from a LEADING block of its patient's observations, all from ONE
  * factorisation per patient -- what the model says at time t from what was known before t.
@@ -672,6 +713,11 @@ int medgp_profile_num_kernels(void);
    [medgp_profile_num_kernels(), medgp_profile_num_kernels_all()) are valid for medgp_profile_kernel_name, medgp_profile_read and
    medgp_profile_enable(2 + k) like the ids before them. */
 int medgp_profile_num_kernels_all(void);
+/* medgp_profile_num_kernels_all is pinned as well, at the 29 entries it had when medgp_forecast_grad added it (its callers compare
+   the whole list).  Entries added since -- medgp_lgo_grad's k_lgo_vec (k_lgo_mask, k_lgo_prep and k_lgo_obj), k_lgo_inv, k_lgo_s,
+   k_lgo_t, k_lgo_wgrad -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
+   in the same way.  A caller that wants every entry walks [0, medgp_profile_num_kernels_ext()) and does not assume its length. */
+int medgp_profile_num_kernels_ext(void);
 const char *medgp_profile_kernel_name(int k);
 /* synchronises, then returns accumulated milliseconds and launch count of kernel k since the
  * last medgp_profile_reset */

@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at", "medgp_gmm_fit",
 ]
 
@@ -96,6 +96,7 @@ def load():
     lib.medgp_posterior_joint_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, fp, fp, fp, fp, i32p, i32p]
     lib.medgp_loo_batch.argtypes = [vp, C.c_int, i32p, dp, i32p, i32p, fp, fp, dp, dp, i32p, i32p]
     lib.medgp_loo_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, i32p]
+    lib.medgp_lgo_grad.argtypes = [vp, C.c_int, i32p, dp, i32p, i32p, C.c_int, dp, dp, i32p, i32p]
     lib.medgp_forecast_grad.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, C.c_int, dp, dp, i32p]
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
     lib.medgp_trend_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, fp, fp, i32p]
@@ -106,6 +107,7 @@ def load():
     lib.medgp_profile_enable.argtypes = [vp, C.c_int]
     lib.medgp_profile_num_kernels.restype = C.c_int
     lib.medgp_profile_num_kernels_all.restype = C.c_int
+    lib.medgp_profile_num_kernels_ext.restype = C.c_int
     lib.medgp_profile_kernel_name.argtypes = [C.c_int]
     lib.medgp_profile_kernel_name.restype = C.c_char_p
     lib.medgp_profile_read.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_int64)]
@@ -798,6 +800,29 @@ class Context:
                                            _ptr(obj, C.c_double), _ptr(grad, C.c_double), _ptr(status, C.c_int32)))
         return obj, grad, status
 
+    def lgo_grad(self, slots, theta, groups, flag_grad=True):
+        """medgp_lgo_grad: the negative leave-group-out log pseudo-likelihood J = - sum_g lpd_g (plus the prior term, as nlml_grad)
+        and its gradient in theta -- the score Context.loo(groups=...) reports, as a training objective.  groups as Context.loo
+        takes them: a list of one int array of group ids per patient (-1: never held out; medgp_amd.crossval builds the usual
+        partitions), "covariate", or None (classic LOO: Context.loo_grad's bits).
+        Returns (obj[nbatch], grad[nbatch, H] or None, status[nbatch], [group_status[G] per patient])."""
+        slots, theta, ns, gs, ng = self._loo_args(slots, theta, groups)
+        nb = slots.shape[0]
+        flag = int(flag_grad)
+        Gs = np.array(ns if gs is None else ng, dtype=np.int64)
+        goff = np.zeros(nb + 1, dtype=np.int64)
+        goff[1:] = np.cumsum(Gs)
+        NO, NG = int(sum(ns)), int(goff[-1])
+        grp = None if gs is None else np.ascontiguousarray(np.concatenate(gs) if NO else np.zeros(1), dtype=np.int32)
+        obj = np.empty(nb)
+        grad = np.empty((nb, self.H)) if flag & 1 else None
+        status = np.empty(nb, dtype=np.int32)
+        gst = np.empty(max(NG, 1), dtype=np.int32)
+        self._chk(self._lib.medgp_lgo_grad(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), _ptr(grp, C.c_int32),
+                                           _ptr(ng, C.c_int32), flag, _ptr(obj, C.c_double), _ptr(grad, C.c_double),
+                                           _ptr(status, C.c_int32), _ptr(gst, C.c_int32)))
+        return obj, grad, status, [gst[int(goff[b]):int(goff[b + 1])].copy() for b in range(nb)]
+
     def forecast_grad(self, slots, theta, prefixes=None, flag_grad=1):
         """medgp_forecast_grad: the negative forecast score J = - sum_i lpd_i (plus the prior term, as nlml_grad) and its gradient in
         theta.  prefixes: one int array per patient, in the order the patient was uploaded: prefixes[b][i] = the number of leading
@@ -834,7 +859,7 @@ class Context:
         """on: bracket every launch with HIP events; only='k_cholinv': just the launches of that kernel."""
         mode = int(bool(on))
         if on and only is not None:
-            names = [self._lib.medgp_profile_kernel_name(k).decode() for k in range(self._lib.medgp_profile_num_kernels_all())]
+            names = [self._lib.medgp_profile_kernel_name(k).decode() for k in range(self._lib.medgp_profile_num_kernels_ext())]
             mode = 2 + names.index(only)
         self._chk(self._lib.medgp_profile_enable(self._h, mode))
 
@@ -843,7 +868,7 @@ class Context:
 
     def profile_read(self):
         out = {}
-        for k in range(self._lib.medgp_profile_num_kernels_all()):
+        for k in range(self._lib.medgp_profile_num_kernels_ext()):
             ms, cnt = C.c_double(), C.c_int64()
             self._chk(self._lib.medgp_profile_read(self._h, k, C.byref(ms), C.byref(cnt)))
             out[self._lib.medgp_profile_kernel_name(k).decode()] = (ms.value, cnt.value)

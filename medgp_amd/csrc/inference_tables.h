@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #if defined(__HIPCC__) || defined(__HIP__)
@@ -338,4 +339,60 @@ inline bool build_loo_tables(const std::vector<TableClass> &cls, const int *orde
         T.csing.push_back({(int)ci, s0, (int)T.singles.size() - s0});
     }
     return true;
+}
+
+// medgp_lgo_grad: what its own kernels need beyond the tables of build_loo_tables (T, built with want_var = false, want_vec = true).
+// Per launch chunk of T (chunks[i] belongs to T.chunks[i]) one workgroup per row:
+//   cols   (group, I = 64-column tile of R^-1)                          k_lgo_inv
+//   trows  (group, I = 64-row block of the group's ENTRY)               k_lgo_t: the rows of P that take part in P[:, B_g] S_g
+// `pat` of a row is the group's index in T.groups, as in T.pairs.  And per entry:
+//   sgl    ld ints per entry, class after class (sgl_off[ci] = first int of class ci), entry after entry: the group of the call that
+//          row r is as a singleton, -1 for every other row (a member of a larger group, id -1, padding)
+//   gord   the non-empty groups of the call, entry after entry (internal order), those of an entry by their FIRST member's row: the
+//          order in which J adds the lpd of an entry's groups -- it does not depend on the labels
+//   ent    two ints per internal entry i: its range [x0, x1) of gord
+struct LgoChunk { int col0, ncol, trow0, ntrow; };
+struct LgoTables {
+    std::vector<JointTile> cols, trows;
+    std::vector<LgoChunk> chunks;
+    std::vector<int> sgl, gord, ent;
+    std::vector<size_t> sgl_off;
+};
+inline void build_lgo_tables(const std::vector<TableClass> &cls, const int *en, const LooTables &T, LgoTables &G) {
+    size_t total = 0;
+    int nent = 0;
+    for (const TableClass &k : cls) { G.sgl_off.push_back(total); total += (size_t)k.count * k.ld; nent = std::max(nent, k.b0 + k.count); }
+    G.sgl.assign(total, -1);
+    G.ent.assign(2 * (size_t)nent, 0);
+    std::vector<std::vector<std::pair<int, int>>> first((size_t)nent);   // per internal entry (first row, group of the call)
+    for (const LooClassSingles &s : T.csing)
+        for (int x = s.s0; x < s.s0 + s.ns; x++) {
+            const LooSingle &S = T.singles[(size_t)x];
+            const TableClass &k = cls[(size_t)s.cls];
+            G.sgl[G.sgl_off[(size_t)s.cls] + (size_t)S.e * k.ld + S.r] = S.g;
+            first[(size_t)(k.b0 + S.e)].push_back({S.r, S.g});
+        }
+    for (const LooChunk &ch : T.chunks)
+        for (int gi = ch.g0; gi < ch.g0 + ch.ng; gi++) {
+            const JointPat &P = T.groups[(size_t)gi];
+            first[(size_t)(cls[(size_t)ch.cls].b0 + P.e)].push_back({T.rows[(size_t)P.p0].r, P.b});
+        }
+    for (int i = 0; i < nent; i++) {
+        std::sort(first[(size_t)i].begin(), first[(size_t)i].end());
+        G.ent[2 * (size_t)i] = (int)G.gord.size();
+        for (const auto &fg : first[(size_t)i]) G.gord.push_back(fg.second);
+        G.ent[2 * (size_t)i + 1] = (int)G.gord.size();
+    }
+    for (const LooChunk &ch : T.chunks) {
+        const TableClass &k = cls[(size_t)ch.cls];
+        LgoChunk c{(int)G.cols.size(), 0, (int)G.trows.size(), 0};
+        for (int gi = ch.g0; gi < ch.g0 + ch.ng; gi++) {
+            const JointPat &P = T.groups[(size_t)gi];
+            const int nt = (P.m + 63) / 64, nrb = (std::max(en[k.b0 + P.e], 1) + 63) / 64;
+            for (int I = 0; I < nt; I++) G.cols.push_back({gi, I, 0, 0});
+            for (int rb = 0; rb < nrb; rb++) G.trows.push_back({gi, rb, 0, 0});
+            c.ncol += nt; c.ntrow += nrb;
+        }
+        G.chunks.push_back(c);
+    }
 }

@@ -23,6 +23,7 @@
 #include "kernels_loo.h"
 #include "kernels_loo_grad.h"
 #include "kernels_forecast_grad.h"
+#include "kernels_lgo_grad.h"
 
 #include <algorithm>
 #include <chrono>
@@ -37,8 +38,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -85,9 +86,12 @@ struct Arena {
 //   medgp_functional_joint_batch: besides, the joint posterior's patient and tile-pair tables and its float covariance blocks (fcov)
 //   medgp_forecast_grad: BUF_GVEC holds its per-entry vectors [g / 2 | e | lpd | -], BUF_FC_TAB the per-entry integer tables
 //   (forecast_grad_tables.h), BUF_FC_T the matrix T = U Mbar of every entry, laid out like Kmat (gradient calls only)
+//   medgp_lgo_grad: BUF_GVEC holds its per-entry vectors [r | s | v | log p] (k_loo_vec's layout), the LOO call's group / tile-pair /
+//   job tables, index lists, blocks (BUF_C), lpd and group_status buffers; BUF_LGO_COLS / _TROWS / _SGL / _ENT / _GORD the tables of
+//   build_lgo_tables; BUF_LGO_T the matrix Tt = P S of every entry, laid out like Kmat (gradient calls only)
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -856,7 +860,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 14; }
+int medgp_abi_version(void) { return 15; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2395,6 +2399,166 @@ int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     return MEDGP_OK;
 }
 
+// The negative leave-group-out log pseudo-likelihood and its gradient (kernels_lgo_grad.h).  ONE pipeline run in the grouped order (as
+// medgp_loo_batch: the caller's group ids go through h_perm), then per size class, in stream order: k_loo_vec mode 0 and k_lgo_mask (the
+// singleton groups: u, s, lpd), for a gradient k_loo_kinv (P into the dead Kmat block) and k_lgo_prep (Tt = P diag(s)); per launch
+// chunk of the class's larger groups k_loo_gram / k_postfactor / k_loo_solve (R, w, lpd_g: medgp_loo_batch's kernels and bits) and, for
+// a gradient, k_lgo_inv (R^-1), k_lgo_s (S_g, r_g) and k_lgo_t (the group's columns of Tt) -- a chunk is finished before the next one
+// reuses the blocks; then k_loo_vec mode 1 (v = P r), k_lgo_obj (J -> scal[2]), k_lgo_wgrad and the nlml gradient's k_slabsum and
+// k_epilogue.  flag_grad = 0 runs k_loo_vec mode 0, k_lgo_mask, the three LOO kernels of every chunk, k_lgo_obj and k_epilogue.
+int medgp_lgo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int32_t *group, const int32_t *ngroups,
+                   int flag_grad, double *obj, double *grad, int32_t *status, int32_t *group_status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || !obj || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
+    if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
+    if (flag_grad && !grad) return fail(c, MEDGP_ERR_ARG, "grad is NULL with flag_grad set");
+    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_lgo_grad supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds K^-1 here", c->rules.Q);
+    int rc;
+    if (!group) {   // classic LOO: medgp_loo_grad's bits
+        if (ngroups) return fail(c, MEDGP_ERR_ARG, "ngroups without group ids");
+        std::vector<int32_t> st((size_t)nbatch, 0);
+        if ((rc = medgp_loo_grad(c, nbatch, slots, theta, flag_grad, obj, grad, st.data()))) return rc;
+        int64_t at = 0;
+        for (int b = 0; b < nbatch; b++) {
+            if (status) status[b] = st[b];
+            const int n = c->h_n[slots[b]];
+            if (group_status) for (int i = 0; i < n; i++) group_status[at + i] = st[b] < 0 ? -1 : 0;
+            at += n;
+        }
+        return MEDGP_OK;
+    }
+    if (!ngroups) return fail(c, MEDGP_ERR_ARG, "ngroups is NULL with group ids");
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    std::vector<int64_t> ooff(nbatch + 1, 0), goff(nbatch + 1, 0);   // first observation / first group of patient b in the call
+    for (int b = 0; b < nbatch; b++) {
+        if (ngroups[b] < 0) return fail(c, MEDGP_ERR_ARG, "ngroups[%d] = %d", b, ngroups[b]);
+        ooff[b + 1] = ooff[b] + c->h_n[slots[b]];
+        goff[b + 1] = goff[b] + ngroups[b];
+    }
+    const int64_t NO = ooff[nbatch], NG = goff[nbatch];
+    if (NO > (int64_t)INT32_MAX || NG > (int64_t)INT32_MAX) return fail(c, MEDGP_ERR_ARG, "%lld observations in %lld groups in one call", (long long)NO, (long long)NG);
+    for (int b = 0; b < nbatch; b++)
+        for (int64_t i = ooff[b]; i < ooff[b + 1]; i++)
+            if (group[i] < -1 || group[i] >= ngroups[b])
+                return fail(c, MEDGP_ERR_ARG, "group[%lld] = %d outside [-1, %d) (patient %d)", (long long)i, group[i], ngroups[b], b);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
+    const BatchPlan &P = c->plan;
+    std::vector<const int *> perm(nbatch);   // internal row -> caller observation (null: the patient was uploaded grouped)
+    for (int b = 0; b < nbatch; b++) perm[b] = c->h_perm_identity[slots[b]] ? nullptr : c->h_perm[slots[b]].data();
+    const std::vector<TableClass> tcls = table_classes(P);
+    LooTables T;
+    LgoTables G;
+    TableError e;
+    if (!build_loo_tables(tcls, P.order.data(), P.en.data(), ooff.data(), goff.data(), nbatch, group, perm.data(), false, true, c->posterior_budget, T, e))
+        return fail(c, MEDGP_ERR_CAPACITY, "patient %d: group %d of %d observations needs %zu MB at once, the budget is %zu MB (MEDGP_POSTERIOR_BUDGET_GB)",
+                    e.b, e.gid, (int)e.m, e.need >> 20, c->posterior_budget >> 20);
+    build_lgo_tables(tcls, P.en.data(), T, G);
+    const size_t NGz = (size_t)std::max<int64_t>(NG, 1), H = c->H;
+    std::vector<double> hl(NGz, (double)NAN);   // the fill of lpd: NaN where no kernel writes (a failed block; an empty group is never read)
+    if ((rc = buf_ensure(c, BUF_GVEC, 4 * P.need_vec * sizeof(double)))) return rc;
+    if (flag_grad && (rc = buf_ensure(c, BUF_LGO_T, P.need_mat * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_CSTAT, NGz * sizeof(int)))) return rc;
+    if ((rc = buf_ensure(c, BUF_C, T.blk_need))) return rc;
+    if ((rc = upload_table(c, BUF_LPD, hl))) return rc;
+    if ((rc = upload_table(c, BUF_ROWS, T.rows))) return rc;
+    if ((rc = upload_table(c, BUF_PATS, T.groups))) return rc;
+    if ((rc = upload_table(c, BUF_PAIRS, T.pairs))) return rc;
+    if ((rc = upload_table(c, BUF_BLKS, T.jobs))) return rc;
+    if ((rc = upload_table(c, BUF_LGO_COLS, G.cols))) return rc;
+    if ((rc = upload_table(c, BUF_LGO_TROWS, G.trows))) return rc;
+    if ((rc = upload_table(c, BUF_LGO_SGL, G.sgl))) return rc;
+    if ((rc = upload_table(c, BUF_LGO_ENT, G.ent))) return rc;
+    if ((rc = upload_table(c, BUF_LGO_GORD, G.gord))) return rc;
+    double *gvec = buf<double>(c, BUF_GVEC), *tmat = buf<double>(c, BUF_LGO_T), *d_lpd = buf<double>(c, BUF_LPD), *d_blocks = buf<double>(c, BUF_C);
+    int *d_gstat = buf<int>(c, BUF_CSTAT);
+    HIPCHK(c, hipMemsetAsync(d_gstat, 0, NGz * sizeof(int), c->stream));
+    const LooRow *d_rows = buf<LooRow>(c, BUF_ROWS);
+    const JointPat *d_groups = buf<JointPat>(c, BUF_PATS);
+    const JointTile *d_pairs = buf<JointTile>(c, BUF_PAIRS), *d_jobs = buf<JointTile>(c, BUF_BLKS);
+    const JointTile *d_cols = buf<JointTile>(c, BUF_LGO_COLS), *d_trows = buf<JointTile>(c, BUF_LGO_TROWS);
+    const int *d_sgl = buf<int>(c, BUF_LGO_SGL), *d_ent = buf<int>(c, BUF_LGO_ENT), *d_gord = buf<int>(c, BUF_LGO_GORD);
+    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
+    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    // the generic kernels (MEDGP_V0) keep W where P goes: this call always takes the templated ones
+    const bool v0 = c->rules.use_v0;
+    c->rules.use_v0 = false;
+    rc = factor_run(c, nbatch, theta, true, false);
+    c->rules.use_v0 = v0;
+    if (rc) return rc;
+    const double log2pi = std::log(2.0 * c->pi);
+    for (size_t ci = 0; ci < P.cls.size(); ci++) {
+        const SizeClass &k = P.cls[ci];
+        const MedgpDev V = class_view(c, P, k);
+        double *vec = gvec + 4 * k.off_vec;
+        double *Tm = flag_grad ? tmat + k.off_mat : nullptr;
+        const int nb = k.count, nt64 = k.nbmax;
+        const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
+        const dim3 tg(wg.grid), tb(WG_THREADS);
+        { Launcher l(c, KID_LOO_VEC); hipLaunchKernelGGL(k_loo_vec, dim3(4 * nt64, nb), dim3(256), 0, c->stream, V, vec, 0, log2pi); }
+        { Launcher l(c, KID_LGO_VEC); hipLaunchKernelGGL(k_lgo_mask, dim3((k.ld + 255) / 256, nb), dim3(256), 0, c->stream, V, vec, d_sgl + G.sgl_off[ci], d_lpd); }
+        if (flag_grad) {
+            { Launcher l(c, KID_LOO_KINV); hipLaunchKernelGGL(k_loo_kinv, tg, tb, 0, c->stream, V, nb, wg.wg_tiles, wg.nbp); }
+            { Launcher l(c, KID_LGO_VEC); hipLaunchKernelGGL(k_lgo_prep, dim3(nt64, 16 * nt64, nb), dim3(256), 0, c->stream, V, vec, Tm); }
+        }
+        for (size_t x = 0; x < T.chunks.size(); x++) {   // chunks reuse the blocks in stream order
+            const LooChunk &ch = T.chunks[x];
+            const LgoChunk &gc = G.chunks[x];
+            if (ch.cls != (int)ci) continue;
+            { Launcher l(c, KID_LOO_GRAM); hipLaunchKernelGGL(k_loo_gram, dim3(ch.npair), dim3(256), 0, c->stream, V, d_groups, d_pairs + ch.pair0, d_rows, d_blocks); }
+            { Launcher l(c, KID_POSTFACTOR); hipLaunchKernelGGL(k_postfactor, dim3(ch.ng), dim3(256), 0, c->stream, V, d_groups + ch.g0, d_blocks, d_gstat); }
+            {
+                Launcher l(c, KID_LOO_SOLVE);
+                hipLaunchKernelGGL(k_loo_solve, dim3(ch.njob), dim3(256), 0, c->stream, V, d_groups, d_jobs + ch.job0, d_rows, d_blocks, d_gstat, log2pi,
+                                   (float *)nullptr, (float *)nullptr, d_lpd);
+            }
+            if (!flag_grad) continue;
+            { Launcher l(c, KID_LGO_INV); hipLaunchKernelGGL(k_lgo_inv, dim3(gc.ncol), dim3(256), 0, c->stream, V, d_groups, d_cols + gc.col0, d_blocks, d_gstat); }
+            { Launcher l(c, KID_LGO_S); hipLaunchKernelGGL(k_lgo_s, dim3(ch.npair), dim3(256), 0, c->stream, V, d_groups, d_pairs + ch.pair0, d_rows, d_blocks, d_gstat, vec); }
+            { Launcher l(c, KID_LGO_T); hipLaunchKernelGGL(k_lgo_t, dim3(gc.ntrow), dim3(256), 0, c->stream, V, d_groups, d_trows + gc.trow0, d_rows, d_blocks, d_gstat, Tm); }
+        }
+        if (flag_grad) { Launcher l(c, KID_LOO_VEC); hipLaunchKernelGGL(k_loo_vec, dim3(4 * nt64, nb), dim3(256), 0, c->stream, V, vec, 1, log2pi); }
+        { Launcher l(c, KID_LGO_VEC); hipLaunchKernelGGL(k_lgo_obj, dim3(nb), dim3(64), 0, c->stream, V, d_ent + 2 * k.b0, d_gord, d_lpd); }
+        if (flag_grad) {
+            {
+                Launcher l(c, KID_LGO_WGRAD);   // (Q <= 16 was checked)
+                with_q16(V.Q, [&](auto q, auto q0) {
+                    hipLaunchKernelGGL((k_lgo_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, vec, Tm, nb, wg.wg_tiles, wg.nbp);
+                });
+            }
+            const int nbins3 = 3 * V.Q * tri(V.D);
+            Launcher l(c, KID_EPILOGUE);
+            hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V);
+        }
+        Launcher l(c, KID_EPILOGUE);
+        const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
+        hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, c->d_theta, flag_grad, 1, c->d_nlml, c->d_grad, c->d_status_out, 1);
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<int32_t> st((size_t)nbatch, 0);
+    std::vector<int> gst(NGz, 0);
+    HIPCHK(c, hipMemcpyAsync(obj, c->d_nlml, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    if (flag_grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * H, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    if (NG > 0) HIPCHK(c, hipMemcpyAsync(gst.data(), d_gstat, sizeof(int) * NG, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_retired(c);
+    for (int b = 0; b < nbatch; b++) {
+        if (status) status[b] = st[b];
+        bool bad = false;
+        for (int64_t g = goff[b]; g < goff[b + 1]; g++) {
+            const bool gb = st[b] < 0 || gst[(size_t)g] < 0;
+            if (group_status) group_status[g] = gb ? -1 : 0;
+            bad = bad || gb;
+        }
+        if (bad && st[b] >= 0) {   // a group whose block met a bad pivot: the patient's J and gradient are not defined
+            obj[b] = (double)NAN;
+            if (flag_grad) for (size_t h = 0; h < H; h++) grad[(size_t)b * H + h] = (double)NAN;
+        }
+    }
+    return MEDGP_OK;
+}
+
 // The negative forecast score and its gradient (kernels_forecast_grad.h).  ONE pipeline run in the CALLER's order (as
 // medgp_forecast_batch: the history of an observation is a leading block of that order) with U = L^-T, then per size class, in
 // stream order: k_fc_vec (var, r, g, e, lpd; then J -> scal[2]), and for a gradient k_fc_t (T = U Mbar into the call's own buffer),
@@ -2547,7 +2711,8 @@ int medgp_profile_enable(medgp_ctx *c, int enable) {
 }
 // the table existing callers index is frozen at its 23 entries (include/medgp_hip.h); entries added since are reached through the _all count
 int medgp_profile_num_kernels(void) { return KID_FORECAST + 1; }
-int medgp_profile_num_kernels_all(void) { return KID_COUNT; }
+int medgp_profile_num_kernels_all(void) { return KID_FC_WGRAD + 1; }
+int medgp_profile_num_kernels_ext(void) { return KID_COUNT; }
 const char *medgp_profile_kernel_name(int k) { return (k >= 0 && k < KID_COUNT) ? kKernelNames[k] : ""; }
 int medgp_profile_read(medgp_ctx *c, int k, double *ms_total, int64_t *launches) {
     if (!c || k < 0 || k >= KID_COUNT) return MEDGP_ERR_ARG;
