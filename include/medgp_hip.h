@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 15: medgp_lgo_grad (14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 16: medgp_fisher_vec (15: medgp_lgo_grad; 14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -388,6 +388,36 @@ int medgp_loo_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const doubl
 int medgp_lgo_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int32_t *group,
                    const int32_t *ngroups, int flag_grad, double *obj, double *grad, int32_t *status, int32_t *group_status);
 
+/* Products of the Fisher information of the Gaussian marginal likelihood with vectors: the curvature the four training objectives
+ * lack.  With K the matrix that was factored (noise included), P = K^-1 and dK/dtheta_h the derivative of the UN-jittered K the
+ * gradient calls use,
+ *   F_hk(theta) = 1/2 tr(P dK/dtheta_h P dK/dtheta_k),
+ *   (F v)_h = 1/2 tr(W_F dK/dtheta_h),     W_F = P Kdot P,     Kdot = sum_k v_k dK/dtheta_k:
+ * the marginal-likelihood gradient with W_F in the place of W.  F is the expected Hessian of the nlml: positive semi-definite,
+ * independent of y, first derivatives of the kernel only.  The reference has no such output; the definition is the long-double
+ * restatement in tests/fisher_truth.py (dgram_dir is Kdot, fisher_vec the product).  With it a host can run Fisher scoring or
+ * natural-gradient CG, form a patient's full F for small H, and report Cramer-Rao standard errors (medgp_amd.information).
+ * nbatch, slots, theta, status as medgp_loo_grad (one factorisation per patient, no n > 2 guard; status[b] = jitter rounds or -1).
+ *   nvec >= 1 directions per entry; vec[(b * nvec + j) * H ..] is direction j of entry b in theta order (v lives in theta space: a
+ *     patient not uploaded grouped by output gives the result of the grouped upload); fvec has the same layout and holds F(theta_b) v_bj.
+ *     nvec < 1, or NULL vec, fvec, theta or slots: MEDGP_ERR_ARG before any device work.
+ * After k jitter rounds P is the inverse of K + k diag(sigma^2); the noise hyper log sigma_d still contributes 2 sigma_d^2 on the
+ * diagonal entries of covariate d to Kdot, not scaled by 1 + k.  Priors play no part: F is the information of the likelihood, and a
+ * slot's prior descriptor does not change a bit of the output; neither does y.  A patient with status[b] < 0 gets NaN in all its
+ * nvec * H outputs, its batch-mates are untouched.
+ * All three covariance families; Q <= 16 only: Q > 16 returns MEDGP_ERR_ARG, and MEDGP_V0 is not honoured by this call.  The call
+ * holds two more ldn^2 matrices per entry (Kdot and T = P Kdot) in buffers of its own, reused by every direction; a call whose
+ * per-entry matrices -- all four -- exceed the memory budget fails with MEDGP_ERR_CAPACITY (no memory waves).
+ * No atomics, every sum in a fixed order over the entry's own operands: with the route pinned a direction's fvec bits depend on the
+ * patient, theta and that direction alone -- not on the batch-mates, on nvec, on the direction's position j or on the other
+ * directions.  medgp_get_factor is VALID afterwards (P overwrites the factor L, which it does not read; L^-1, alpha and the log
+ * determinant are left untouched).
+ * Out of scope: the exact (observed) Hessian, whose 1/2 tr(W d_h Kdot) term needs second derivatives of the kernel; curvature of the
+ * priors; curvature of the cross-validation objectives; Q > 16.
+ * All pointers are HOST memory. */
+int medgp_fisher_vec(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int nvec, const double *vec, double *fvec,
+                     int32_t *status);
+
 /* Rolling-origin forecasts: every test point predicted from a LEADING block of its patient's observations, all from ONE
  * factorisation per patient -- what the model says at time t from what was known before t.
  *   ref: core/gp_regression.cpp:128-214 (GP_Regression::predict), main_one_test.cpp:269-300 (the "past" training sets of the
@@ -715,7 +745,7 @@ int medgp_profile_num_kernels(void);
 int medgp_profile_num_kernels_all(void);
 /* medgp_profile_num_kernels_all is pinned as well, at the 29 entries it had when medgp_forecast_grad added it (its callers compare
    the whole list).  Entries added since -- medgp_lgo_grad's k_lgo_vec (k_lgo_mask, k_lgo_prep and k_lgo_obj), k_lgo_inv, k_lgo_s,
-   k_lgo_t, k_lgo_wgrad -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
+   k_lgo_t, k_lgo_wgrad, and medgp_fisher_vec's k_fisher_prep, k_fisher_kdot, k_fisher_t, k_fisher_wgrad -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
    in the same way.  A caller that wants every entry walks [0, medgp_profile_num_kernels_ext()) and does not assume its length. */
 int medgp_profile_num_kernels_ext(void);
 const char *medgp_profile_kernel_name(int k);

@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(256) k_epilogue(MedgpDev L, const double *__re
     double *g = grad_out ? grad_out + (size_t)pos * H : nullptr;
     if (tid == 0 && part == 0 && status_out) status_out[pos] = st;
     if (st < 0) {
-        if (tid == 0 && part == 0) nlml_out[pos] = __builtin_nan("");
+        if (tid == 0 && part == 0 && loo_objective != 2) nlml_out[pos] = __builtin_nan("");
         if (flag_grad && g) for (int h = h0 + tid; h < h1; h += nt) g[h] = __builtin_nan("");
         return;
     }
@@ -298,7 +298,8 @@ __global__ void __launch_bounds__(256) k_epilogue(MedgpDev L, const double *__re
     }
     // a caller-order copy of a patient (slot + max_slots, nlml-only evaluations) shares the prior of its patient
     const int pslot = slot >= L.max_slots ? slot - L.max_slots : slot;
-    const MedgpPrior *pr = L.prior_on[pslot] ? L.prior + (size_t)pslot * H : nullptr;
+    // loo_objective == 2 (medgp_fisher_vec): the gradient lines alone -- no prior stage, no scalar
+    const MedgpPrior *pr = (loo_objective != 2 && L.prior_on[pslot]) ? L.prior + (size_t)pslot * H : nullptr;
     double lp_part = 0.0;   // thread 0: sum of this part's chunk sums, in chunk order
   for (int ch = ch0; ch < ch1; ch++) {
     double lp_local = 0.0;
@@ -425,6 +426,6 @@ __global__ void __launch_bounds__(256) k_epilogue(MedgpDev L, const double *__re
         double logdet = L.scal[b * 4 + 0], quad = L.scal[b * 4 + 1];
         double nlml = quad / 2.0 + logdet + n * log(2. * L.pi) / 2.0;   // ref: c_inference_exact.cpp:149-152
         if (loo_objective) nlml = L.scal[b * 4 + 2];   // medgp_loo_grad: k_loo_vec left the negative LOO log pseudo-likelihood there
-        nlml_out[pos] = nlml - lp;
+        if (loo_objective != 2) nlml_out[pos] = nlml - lp;
     }
 }

@@ -24,6 +24,7 @@
 #include "kernels_loo_grad.h"
 #include "kernels_forecast_grad.h"
 #include "kernels_lgo_grad.h"
+#include "kernels_fisher.h"
 
 #include <algorithm>
 #include <chrono>
@@ -38,8 +39,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -89,9 +90,12 @@ struct Arena {
 //   medgp_lgo_grad: BUF_GVEC holds its per-entry vectors [r | s | v | log p] (k_loo_vec's layout), the LOO call's group / tile-pair /
 //   job tables, index lists, blocks (BUF_C), lpd and group_status buffers; BUF_LGO_COLS / _TROWS / _SGL / _ENT / _GORD the tables of
 //   build_lgo_tables; BUF_LGO_T the matrix Tt = P S of every entry, laid out like Kmat (gradient calls only)
+//   medgp_fisher_vec (fisher_tables.h): BUF_FI_KDOT / BUF_FI_T the matrices Kdot and T = P Kdot of every entry for the direction in
+//   hand, laid out like Kmat; BUF_FI_COEF the direction's coefficient blocks; BUF_FI_DIR the caller's directions [nbatch][nvec][H];
+//   BUF_FI_OUT the products, direction-major [nvec][nbatch][H] (k_epilogue's row stride is H)
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -860,7 +864,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 15; }
+int medgp_abi_version(void) { return 16; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2556,6 +2560,93 @@ int medgp_lgo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
             if (flag_grad) for (size_t h = 0; h < H; h++) grad[(size_t)b * H + h] = (double)NAN;
         }
     }
+    return MEDGP_OK;
+}
+
+// Products of the Fisher information with nvec directions per entry (kernels_fisher.h).  ONE pipeline run in the grouped order (as
+// medgp_loo_grad: factor, U = L^-T), then per size class k_loo_kinv (P = U U^T into the dead Kmat block).  Then, direction by
+// direction, per size class in stream order: k_fisher_prep (the direction's coefficients), k_fisher_kdot (Kdot), k_fisher_t
+// (T = P Kdot), k_fisher_wgrad (W_F tiles -> slab, wdiag) and the nlml gradient's own k_slabsum and k_epilogue, the latter told to
+// leave the prior and the scalar out.  Kdot and T are buffers of the call, reused by every direction; every direction runs the same
+// launches with the same geometry, so its bits depend neither on nvec nor on its position.  The four matrices of every entry are
+// alive at once: a call that needs more than the memory budget is refused (fisher_tables.h), there are no memory waves.
+int medgp_fisher_vec(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int nvec, const double *vec, double *fvec,
+                     int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || !vec || !fvec) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    if (nvec < 1) return fail(c, MEDGP_ERR_ARG, "nvec = %d", nvec);
+    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_fisher_vec supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds K^-1 here", c->rules.Q);
+    int rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
+    const BatchPlan &P = c->plan;
+    if (P.nwaves > 1 || !fisher_fits(P.need_mat, c->rules.mem_budget))
+        return fail(c, MEDGP_ERR_CAPACITY, "the call's per-entry matrices (%d of %zu MB) exceed the memory budget of %zu MB (MEDGP_MEM_BUDGET_GB): split the call",
+                    FISHER_MATS, (P.need_mat * sizeof(double)) >> 20, c->rules.mem_budget >> 20);
+    const size_t H = c->H;
+    const FisherBuffers fb = fisher_buffers(P.need_mat, nbatch, nvec, (int)H, c->rules.Q, c->rules.D);
+    if ((rc = buf_ensure(c, BUF_FI_KDOT, fb.mat_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FI_T, fb.mat_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FI_COEF, fb.coef_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FI_DIR, fb.dir_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FI_OUT, fb.dir_doubles * sizeof(double)))) return rc;
+    double *kdot = buf<double>(c, BUF_FI_KDOT), *tmat = buf<double>(c, BUF_FI_T), *coef = buf<double>(c, BUF_FI_COEF);
+    double *d_dir = buf<double>(c, BUF_FI_DIR), *d_out = buf<double>(c, BUF_FI_OUT);
+    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
+    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    HIPCHK(c, hipMemcpyAsync(d_dir, vec, fb.dir_doubles * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // the generic kernels (MEDGP_V0) keep W where P goes: this call always takes the templated ones
+    const bool v0 = c->rules.use_v0;
+    c->rules.use_v0 = false;
+    rc = factor_run(c, nbatch, theta, true, false);
+    c->rules.use_v0 = v0;
+    if (rc) return rc;
+    for (const SizeClass &k : P.cls) {
+        const MedgpDev V = class_view(c, P, k);
+        const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, k.count, k.nbmax);
+        Launcher l(c, KID_LOO_KINV);
+        hipLaunchKernelGGL(k_loo_kinv, dim3(wg.grid), dim3(WG_THREADS), 0, c->stream, V, k.count, wg.wg_tiles, wg.nbp);
+    }
+    for (int j = 0; j < nvec; j++)
+        for (const SizeClass &k : P.cls) {
+            const MedgpDev V = class_view(c, P, k);
+            const int nb = k.count, nt64 = k.nbmax;
+            double *Kd = kdot + k.off_mat, *Tm = tmat + k.off_mat, *cf = coef + (size_t)k.b0 * V.hyp_stride;
+            const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
+            const dim3 tg(wg.grid), tb(WG_THREADS);
+            {
+                Launcher l(c, KID_FI_PREP);
+                hipLaunchKernelGGL(k_fisher_prep, dim3(nb, 1 + (V.Q * V.D * V.D + 255) / 256), dim3(256), 0, c->stream, V, c->d_theta, d_dir, nvec, j, cf);
+            }
+            {
+                Launcher l(c, KID_FI_KDOT);   // (Q <= 16 was checked)
+                with_q16(V.Q, [&](auto q, auto q0) {
+                    hipLaunchKernelGGL((k_fisher_kdot<decltype(q)::value, decltype(q0)::value>), dim3(fisher_kdot_grid(nt64), nb), dim3(256), 0, c->stream, V, cf, Kd);
+                });
+            }
+            { Launcher l(c, KID_FI_T); hipLaunchKernelGGL(k_fisher_t, dim3(fisher_t_grid(nt64), nb), tb, 0, c->stream, V, Kd, Tm, nt64); }
+            {
+                Launcher l(c, KID_FI_WGRAD);
+                with_q16(V.Q, [&](auto q, auto q0) {
+                    hipLaunchKernelGGL((k_fisher_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, Tm, nb, wg.wg_tiles, wg.nbp);
+                });
+            }
+            const int nbins3 = 3 * V.Q * tri(V.D);
+            { Launcher l(c, KID_EPILOGUE); hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V); }
+            Launcher l(c, KID_EPILOGUE);
+            const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
+            hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, c->d_theta, 1, 1, c->d_nlml, d_out + (size_t)j * nbatch * H, c->d_status_out, 2);
+        }
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> out(fb.dir_doubles);
+    HIPCHK(c, hipMemcpyAsync(out.data(), d_out, fb.dir_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_retired(c);
+    for (int b = 0; b < nbatch; b++)
+        for (int j = 0; j < nvec; j++)
+            std::memcpy(fvec + ((size_t)b * nvec + j) * H, out.data() + ((size_t)j * nbatch + b) * H, H * sizeof(double));
     return MEDGP_OK;
 }
 
