@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 16: medgp_fisher_vec (15: medgp_lgo_grad; 14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 17: medgp_hess_vec (16: medgp_fisher_vec; 15: medgp_lgo_grad; 14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -412,11 +412,37 @@ int medgp_lgo_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const doubl
  * patient, theta and that direction alone -- not on the batch-mates, on nvec, on the direction's position j or on the other
  * directions.  medgp_get_factor is VALID afterwards (P overwrites the factor L, which it does not read; L^-1, alpha and the log
  * determinant are left untouched).
- * Out of scope: the exact (observed) Hessian, whose 1/2 tr(W d_h Kdot) term needs second derivatives of the kernel; curvature of the
- * priors; curvature of the cross-validation objectives; Q > 16.
+ * Out of scope: curvature of the priors; curvature of the cross-validation objectives; Q > 16.  (The exact Hessian: medgp_hess_vec.)
  * All pointers are HOST memory. */
 int medgp_fisher_vec(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int nvec, const double *vec, double *fvec,
                      int32_t *status);
+
+/* Products of the exact (observed) Hessian of the data term of the negative log marginal likelihood with vectors.  With
+ *   L(theta) = 1/2 y^T K^-1 y + 1/2 log det K + const     (medgp_nlml_grad's objective without the prior stage),
+ * K the matrix that was factored, P = K^-1, alpha = P y, W = P - alpha alpha^T (grad L_h = 1/2 tr(W dK/dtheta_h)) and
+ *   Kdot = sum_k v_k dK/dtheta_k,     beta = P Kdot alpha,     Wdot = -P Kdot P + beta alpha^T + alpha beta^T,
+ *   (grad^2 L v)_h = 1/2 tr(Wdot dK/dtheta_h) + 1/2 tr(W dKdot/dtheta_h):
+ * the first term is the gradient with Wdot in the place of W, the second needs the second derivatives of the kernel, which come from
+ * five block sums of W per mixture component formed once per call (two more than the gradient's).  Unlike the Fisher information the
+ * result depends on y and need not be positive semi-definite.  The reference has no such output; the definition is the long-double
+ * restatement in tests/hess_truth.py (hess_vec).  With it a host can take Newton-CG / trust-region steps, check that a trained theta
+ * is a minimum, and form a Laplace approximation of the hyper posterior (medgp_amd.curvature).
+ * nbatch, slots, theta, nvec, vec, status and the layout of hvec are exactly those of medgp_fisher_vec (one factorisation per patient,
+ * no n > 2 guard; status[b] = jitter rounds or -1; NULL slots, theta, vec or hvec, or nvec < 1: MEDGP_ERR_ARG before any device work).
+ *   grad: NULL, or [nbatch * H]: the gradient of L (no prior term), from the block sums the call forms anyway.
+ * Jitter convention, as medgp_fisher_vec: after k jitter rounds P and alpha belong to K + k diag(sigma^2); every kernel derivative,
+ * first and second, is that of the UN-jittered K and is not scaled by 1 + k (so the result is the Hessian of L at zero rounds only).
+ * Priors play no part: a slot's prior descriptor does not change a bit of any output.  A patient with status[b] < 0 gets NaN in all
+ * its nvec * H outputs (and its H gradient entries), its batch-mates are untouched.
+ * All three covariance families; Q <= 16 only: Q > 16 returns MEDGP_ERR_ARG, and MEDGP_V0 is not honoured by this call.  Memory as
+ * medgp_fisher_vec: Kdot and T = P Kdot in buffers of the call, MEDGP_ERR_CAPACITY when the four per-entry matrices exceed the memory
+ * budget (no memory waves).  No atomics, every sum in a fixed order over the entry's own operands: with the route pinned a direction's
+ * bits depend on the patient, theta and that direction alone.  medgp_get_factor is VALID afterwards, as after medgp_fisher_vec.
+ * Out of scope: curvature of the priors (medgp_amd.curvature.prior_curvature adds it on the host), of the cross-validation and
+ * forecast objectives; Q > 16.
+ * All pointers are HOST memory. */
+int medgp_hess_vec(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int nvec, const double *vec, double *hvec,
+                   double *grad, int32_t *status);
 
 /* Rolling-origin forecasts: every test point predicted from a LEADING block of its patient's observations, all from ONE
  * factorisation per patient -- what the model says at time t from what was known before t.
@@ -745,7 +771,8 @@ int medgp_profile_num_kernels(void);
 int medgp_profile_num_kernels_all(void);
 /* medgp_profile_num_kernels_all is pinned as well, at the 29 entries it had when medgp_forecast_grad added it (its callers compare
    the whole list).  Entries added since -- medgp_lgo_grad's k_lgo_vec (k_lgo_mask, k_lgo_prep and k_lgo_obj), k_lgo_inv, k_lgo_s,
-   k_lgo_t, k_lgo_wgrad, and medgp_fisher_vec's k_fisher_prep, k_fisher_kdot, k_fisher_t, k_fisher_wgrad -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
+   k_lgo_t, k_lgo_wgrad, medgp_fisher_vec's k_fisher_prep, k_fisher_kdot, k_fisher_t, k_fisher_wgrad, and medgp_hess_vec's k_hess_moments,
+   k_hess_slabsum, k_hess_beta, k_hess_wgrad, k_hess_epilogue -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
    in the same way.  A caller that wants every entry walks [0, medgp_profile_num_kernels_ext()) and does not assume its length. */
 int medgp_profile_num_kernels_ext(void);
 const char *medgp_profile_kernel_name(int k);

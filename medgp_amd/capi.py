@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at", "medgp_gmm_fit",
 ]
 
@@ -98,6 +98,7 @@ def load():
     lib.medgp_loo_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, i32p]
     lib.medgp_lgo_grad.argtypes = [vp, C.c_int, i32p, dp, i32p, i32p, C.c_int, dp, dp, i32p, i32p]
     lib.medgp_fisher_vec.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, i32p]
+    lib.medgp_hess_vec.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, dp, i32p]
     lib.medgp_forecast_grad.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, C.c_int, dp, dp, i32p]
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
     lib.medgp_trend_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, fp, fp, i32p]
@@ -840,6 +841,26 @@ class Context:
         self._chk(self._lib.medgp_fisher_vec(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), int(nvec),
                                              _ptr(v, C.c_double), _ptr(fvec, C.c_double), _ptr(status, C.c_int32)))
         return fvec, status
+
+    def hess_vec(self, slots, theta, vecs, want_grad=False):
+        """medgp_hess_vec: products of the exact Hessian of L = 1/2 y^T K^-1 y + 1/2 log det K (the nlml without the prior stage) with
+        directions in theta space.  slots [nbatch], theta [nbatch, H], vecs [nbatch, nvec, H] or [nbatch, H] (one direction each).
+        Returns (hvec of the shape of vecs, status[nbatch]), or with want_grad (hvec, grad[nbatch, H], status): grad is the gradient
+        of L.  A failed patient's rows are NaN."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        nb = slots.shape[0]
+        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
+        v = np.ascontiguousarray(vecs, dtype=np.float64)
+        if v.ndim not in (2, 3) or v.shape[0] != nb or v.shape[-1] != self.H:
+            raise ValueError(f"vecs of shape {v.shape} for {nb} patients of {self.H} hypers")
+        nvec = 1 if v.ndim == 2 else v.shape[1]
+        hvec = np.empty(v.shape)
+        grad = np.empty((nb, self.H)) if want_grad else None
+        status = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_hess_vec(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), int(nvec),
+                                           _ptr(v, C.c_double), _ptr(hvec, C.c_double), _ptr(grad, C.c_double) if want_grad else None,
+                                           _ptr(status, C.c_int32)))
+        return (hvec, grad, status) if want_grad else (hvec, status)
 
     def forecast_grad(self, slots, theta, prefixes=None, flag_grad=1):
         """medgp_forecast_grad: the negative forecast score J = - sum_i lpd_i (plus the prior term, as nlml_grad) and its gradient in

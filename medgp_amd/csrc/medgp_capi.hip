@@ -25,6 +25,7 @@
 #include "kernels_forecast_grad.h"
 #include "kernels_lgo_grad.h"
 #include "kernels_fisher.h"
+#include "kernels_hess.h"
 
 #include <algorithm>
 #include <chrono>
@@ -39,8 +40,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -93,9 +94,12 @@ struct Arena {
 //   medgp_fisher_vec (fisher_tables.h): BUF_FI_KDOT / BUF_FI_T the matrices Kdot and T = P Kdot of every entry for the direction in
 //   hand, laid out like Kmat; BUF_FI_COEF the direction's coefficient blocks; BUF_FI_DIR the caller's directions [nbatch][nvec][H];
 //   BUF_FI_OUT the products, direction-major [nvec][nbatch][H] (k_epilogue's row stride is H)
+//   medgp_hess_vec (hess_tables.h): the five Fisher buffers in the same roles; BUF_HE_SLAB the two-plane slab of the raw moments M3, M4;
+//   BUF_HE_SUMS the block sums [S | SM | SV | M3 | M4] of the W pass, each [nbatch][Q D D]; BUF_HE_VEC [beta | diag(W)], each laid out
+//   like alpha
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -864,7 +868,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 16; }
+int medgp_abi_version(void) { return 17; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2647,6 +2651,124 @@ int medgp_fisher_vec(medgp_ctx *c, int nbatch, const int32_t *slots, const doubl
     for (int b = 0; b < nbatch; b++)
         for (int j = 0; j < nvec; j++)
             std::memcpy(fvec + ((size_t)b * nvec + j) * H, out.data() + ((size_t)j * nbatch + b) * H, H * sizeof(double));
+    return MEDGP_OK;
+}
+
+// Products of the exact Hessian of the data term of the nlml with nvec directions per entry (kernels_hess.h).  ONE pipeline run as
+// medgp_fisher_vec (factor, U = L^-T, alpha), then per size class k_loo_kinv (P into the dead Kmat block) and the W pass: k_hess_moments
+// (S, SM, SV pieces -> the gradient slab, diag(W), M3 / M4 pieces -> the call's two-plane slab), k_slabsum on a view whose block sums
+// and wdiag are buffers of the call, k_hess_slabsum; with `grad`, k_epilogue's gradient lines on that view (no prior, no scalar).
+// Then, direction by direction, per size class in stream order: k_fisher_prep, k_fisher_kdot, k_fisher_t, k_hess_beta (beta = T alpha),
+// k_hess_wgrad (Wdot tiles -> slab, wdiag), k_slabsum and k_hess_epilogue.  Every direction runs the same launches with the same
+// geometry, so its bits depend neither on nvec nor on its position.  Capacity as the Fisher call (hess_tables.h): no memory waves.
+int medgp_hess_vec(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int nvec, const double *vec, double *hvec,
+                   double *grad, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || !vec || !hvec) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    if (nvec < 1) return fail(c, MEDGP_ERR_ARG, "nvec = %d", nvec);
+    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_hess_vec supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds K^-1 here", c->rules.Q);
+    int rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
+    const BatchPlan &P = c->plan;
+    if (P.nwaves > 1 || !hess_fits(P.need_mat, c->rules.mem_budget))
+        return fail(c, MEDGP_ERR_CAPACITY, "the call's per-entry matrices (%d of %zu MB) exceed the memory budget of %zu MB (MEDGP_MEM_BUDGET_GB): split the call",
+                    HESS_MATS, (P.need_mat * sizeof(double)) >> 20, c->rules.mem_budget >> 20);
+    const size_t H = c->H, QDD = (size_t)c->rules.Q * c->rules.D * c->rules.D;
+    const HessBuffers hb = hess_buffers(P.need_mat, P.need_vec, P.need_slab, nbatch, nvec, (int)H, c->rules.Q, c->rules.D);
+    if ((rc = buf_ensure(c, BUF_FI_KDOT, hb.mat_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FI_T, hb.mat_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FI_COEF, hb.coef_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FI_DIR, hb.dir_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FI_OUT, hb.dir_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_HE_SLAB, hb.hislab_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_HE_SUMS, hb.sums_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_HE_VEC, hb.vec_doubles * sizeof(double)))) return rc;
+    double *kdot = buf<double>(c, BUF_FI_KDOT), *tmat = buf<double>(c, BUF_FI_T), *coef = buf<double>(c, BUF_FI_COEF);
+    double *d_dir = buf<double>(c, BUF_FI_DIR), *d_out = buf<double>(c, BUF_FI_OUT);
+    double *hislab = buf<double>(c, BUF_HE_SLAB), *sums = buf<double>(c, BUF_HE_SUMS), *hvecs = buf<double>(c, BUF_HE_VEC);
+    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
+    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    HIPCHK(c, hipMemcpyAsync(d_dir, vec, hb.dir_doubles * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // the generic kernels (MEDGP_V0) keep W where P goes: this call always takes the templated ones
+    const bool v0 = c->rules.use_v0;
+    c->rules.use_v0 = false;
+    rc = factor_run(c, nbatch, theta, true, false);
+    c->rules.use_v0 = v0;
+    if (rc) return rc;
+    // the view of the W pass of a class: block sums and diag(W) in the call's own buffers, the direction's view keeps the context's
+    auto w_view = [&](const MedgpDev &V, const SizeClass &k) {
+        MedgpDev W = V;
+        W.S = sums + (size_t)k.b0 * QDD; W.SM = W.S + (size_t)nbatch * QDD; W.SV = W.SM + (size_t)nbatch * QDD;
+        W.wdiag = hvecs + P.need_vec + k.off_vec;
+        return W;
+    };
+    for (const SizeClass &k : P.cls) {
+        const MedgpDev V = class_view(c, P, k), W = w_view(V, k);
+        const int nb = k.count;
+        const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, k.nbmax);
+        const dim3 tg(wg.grid), tb(WG_THREADS);
+        double *hi = hislab + hess_hislab_of(k.off_slab), *M3 = sums + (3 * (size_t)nbatch + k.b0) * QDD, *M4 = M3 + (size_t)nbatch * QDD;
+        { Launcher l(c, KID_LOO_KINV); hipLaunchKernelGGL(k_loo_kinv, tg, tb, 0, c->stream, V, nb, wg.wg_tiles, wg.nbp); }
+        {
+            Launcher l(c, KID_HE_MOMENTS);   // (Q <= 16 was checked)
+            with_q16(V.Q, [&](auto q, auto q0) {
+                hipLaunchKernelGGL((k_hess_moments<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, W, hi, nb, wg.wg_tiles, wg.nbp);
+            });
+        }
+        const int nbins3 = 3 * V.Q * tri(V.D);
+        { Launcher l(c, KID_EPILOGUE); hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, W); }
+        { Launcher l(c, KID_HE_SLABSUM); hipLaunchKernelGGL(k_hess_slabsum, dim3(nb, hess_slabsum_grid(V.Q, V.D)), dim3(256), 0, c->stream, W, hi, M3, M4); }
+        if (grad) {
+            Launcher l(c, KID_EPILOGUE);
+            const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
+            hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, W, c->d_theta, 1, 1, c->d_nlml, c->d_grad, c->d_status_out, 2);
+        }
+    }
+    for (int j = 0; j < nvec; j++)
+        for (const SizeClass &k : P.cls) {
+            const MedgpDev V = class_view(c, P, k), W = w_view(V, k);
+            const int nb = k.count, nt64 = k.nbmax;
+            double *Kd = kdot + k.off_mat, *Tm = tmat + k.off_mat, *cf = coef + (size_t)k.b0 * V.hyp_stride, *beta = hvecs + k.off_vec;
+            const HessW hw{W.S, W.SM, W.SV, W.SV + (size_t)nbatch * QDD, W.SV + 2 * (size_t)nbatch * QDD, W.wdiag};
+            const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
+            const dim3 tg(wg.grid), tb(WG_THREADS);
+            {
+                Launcher l(c, KID_FI_PREP);
+                hipLaunchKernelGGL(k_fisher_prep, dim3(nb, 1 + (V.Q * V.D * V.D + 255) / 256), dim3(256), 0, c->stream, V, c->d_theta, d_dir, nvec, j, cf);
+            }
+            {
+                Launcher l(c, KID_FI_KDOT);
+                with_q16(V.Q, [&](auto q, auto q0) {
+                    hipLaunchKernelGGL((k_fisher_kdot<decltype(q)::value, decltype(q0)::value>), dim3(fisher_kdot_grid(nt64), nb), dim3(256), 0, c->stream, V, cf, Kd);
+                });
+            }
+            { Launcher l(c, KID_FI_T); hipLaunchKernelGGL(k_fisher_t, dim3(fisher_t_grid(nt64), nb), tb, 0, c->stream, V, Kd, Tm, nt64); }
+            { Launcher l(c, KID_HE_BETA); hipLaunchKernelGGL(k_hess_beta, dim3(hess_beta_grid(nt64), nb), dim3(256), 0, c->stream, V, Tm, beta); }
+            {
+                Launcher l(c, KID_HE_WGRAD);
+                with_q16(V.Q, [&](auto q, auto q0) {
+                    hipLaunchKernelGGL((k_hess_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, Tm, beta, nb, wg.wg_tiles, wg.nbp);
+                });
+            }
+            const int nbins3 = 3 * V.Q * tri(V.D);
+            { Launcher l(c, KID_EPILOGUE); hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V); }
+            Launcher l(c, KID_HE_EPILOGUE);
+            const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
+            hipLaunchKernelGGL(k_hess_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, hw, c->d_theta, d_dir, nvec, j, cf,
+                               d_out + (size_t)j * nbatch * H, c->d_status_out);
+        }
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> out(hb.dir_doubles);
+    HIPCHK(c, hipMemcpyAsync(out.data(), d_out, hb.dir_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * H, hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_retired(c);
+    for (int b = 0; b < nbatch; b++)
+        for (int j = 0; j < nvec; j++)
+            std::memcpy(hvec + ((size_t)b * nvec + j) * H, out.data() + ((size_t)j * nbatch + b) * H, H * sizeof(double));
     return MEDGP_OK;
 }
 
