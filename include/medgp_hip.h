@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 17: medgp_hess_vec (16: medgp_fisher_vec; 15: medgp_lgo_grad; 14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 18: medgp_posterior_jvp_batch (17: medgp_hess_vec; 16: medgp_fisher_vec; 15: medgp_lgo_grad; 14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -444,6 +444,48 @@ int medgp_fisher_vec(medgp_ctx *ctx, int nbatch, const int32_t *slots, const dou
 int medgp_hess_vec(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int nvec, const double *vec, double *hvec,
                    double *grad, int32_t *status);
 
+/* Hyper-sensitivity of predictions: the directional derivatives (JVP) of the posterior mean and variance at every test point along
+ * directions in theta space, all from ONE factorisation per patient.  With K the matrix that was factored, P = K^-1, alpha = P y,
+ * Kdot = sum_k v_k dK/dtheta_k of the UN-jittered K with its noise diagonal 2 sigma_d^2 v_sigma,d (medgp_fisher_vec's Kdot) and, for
+ * test point j with covariate m_j and time t*_j,
+ *   k_j       the column of K* (medgp_posterior_batch),     w_j = P k_j,     u = Kdot alpha,
+ *   kdot_j    = sum_q e ((Bdot_q[m_i,m_j] + cv_q dt^2 B_q[m_i,m_j]) cos(w_q dt) + cmu_q dt B_q[m_i,m_j] sin(w_q dt)),   dt = t_i - t*_j,
+ *               e = exp(-c_q dt^2): the Kdot element with the same coefficient block Bdot, cmu, cv, without a noise term,
+ *   kdot**_j  = sum_q Bdot_q[m_j,m_j],     sigdot_j = 2 sigma^2_{m_j} v_sigma,m_j:
+ *   mean_j = k_j^T alpha                        dmean_j = kdot_j^T alpha - w_j^T u
+ *   var_j  = k**_j - k_j^T P k_j + sigma^2      dvar_j  = kdot**_j + sigdot_j - 2 kdot_j^T w_j + w_j^T Kdot w_j
+ * dvar is the derivative of the unclamped predictive variance, noise included once, as var is.  The reference has no such output;
+ * the definition is the long-double restatement in tests/posterior_jvp_truth.py (jvp).  With it a host forms the delta-method
+ * (Laplace) predictive variance var + sum_r (dmean . s_r)^2 for a factor S S^T of the hyper covariance, and the sensitivity of a
+ * prediction to each hyper group (medgp_amd.sensitivity).
+ * nbatch, slots, theta, offsets, meta2, t2 and status mean exactly what they mean for medgp_posterior_batch: one factorisation per
+ * patient, no n > 2 guard, status[b] = jitter rounds or -1, an empty range of points is allowed, meta2 may be NULL for SE / SM.
+ *   nvec >= 1 directions per entry; vec[(b * nvec + k) * H ..] is direction k of entry b in theta order, exactly as medgp_fisher_vec.
+ *   dmean[j * nvec + k], dvar[j * nvec + k]   fp64, required; j counts the points of the call (offsets[b] + i).
+ *   mean[j], var[j]   may both be NULL.  When given: the plug-in posterior, held to medgp_posterior_batch's own bar (2 fp32 ulps of
+ *     tests/posterior_ref.py).  Bit identity with that call is NOT promised: this call holds the inverse factor, that one does not.
+ *   nvec < 1, or NULL slots, theta, offsets, vec, dmean or dvar, or only one of mean / var: MEDGP_ERR_ARG before any device work.
+ * Jitter convention, as medgp_fisher_vec: after k jitter rounds P and alpha belong to K + k diag(sigma^2); Kdot, kdot_j, kdot**_j and
+ * sigdot_j are those of the UN-jittered kernel and are not scaled by 1 + k, so the result is a true derivative at zero rounds only.
+ * A patient with status[b] < 0 gets NaN in all its outputs (mean, var and the nvec derivatives of each of its points); its
+ * batch-mates are untouched.
+ * All three covariance families; Q <= 16 only: Q > 16 returns MEDGP_ERR_ARG, and MEDGP_V0 is not honoured by this call.  Memory: one
+ * more ldn^2 matrix per entry (Kdot) in a buffer of the call, reused by every direction, and two ldn x 64 panels of work rows per tile
+ * of 64 points (W = P K* and V = L^-1 K*).  The points are cut into launches whose work rows stay within MEDGP_POSTERIOR_BUDGET_GB, as
+ * medgp_posterior_batch's are; a call whose per-entry matrices -- all three -- exceed the memory budget fails with
+ * MEDGP_ERR_CAPACITY (no memory waves).  Supported range of the time stamps: |t| <= 2^14 h, as the posterior call (K*, Kdot and kdot
+ * come from cos / sin tables of the observations and of the test points and lose |w t| eps away from the origin).
+ * Determinism: no atomics, every sum in a fixed order over the entry's own operands.  With the route pinned the bits of
+ * (point j, direction k) depend on the patient, theta, that point and that direction alone -- not on the batch-mates, on nvec, on the
+ * direction's position, on the other points or their order, on the tile a point lands in, or on how the call is cut into launches.
+ * medgp_get_factor is VALID afterwards: the call overwrites neither L nor L^-1, alpha or the log determinant.
+ * Out of scope: Q > 16; derivatives of parts, of the joint covariance, of trend, components and functionals; the second-order mean
+ * correction; the reverse mode.
+ * All pointers are HOST memory. */
+int medgp_posterior_jvp_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                              const int32_t *meta2, const float *t2, int nvec, const double *vec, float *mean, float *var, double *dmean,
+                              double *dvar, int32_t *status);
+
 /* Rolling-origin forecasts: every test point predicted from a LEADING block of its patient's observations, all from ONE
  * factorisation per patient -- what the model says at time t from what was known before t.
  *   ref: core/gp_regression.cpp:128-214 (GP_Regression::predict), main_one_test.cpp:269-300 (the "past" training sets of the
@@ -772,7 +814,7 @@ int medgp_profile_num_kernels_all(void);
 /* medgp_profile_num_kernels_all is pinned as well, at the 29 entries it had when medgp_forecast_grad added it (its callers compare
    the whole list).  Entries added since -- medgp_lgo_grad's k_lgo_vec (k_lgo_mask, k_lgo_prep and k_lgo_obj), k_lgo_inv, k_lgo_s,
    k_lgo_t, k_lgo_wgrad, medgp_fisher_vec's k_fisher_prep, k_fisher_kdot, k_fisher_t, k_fisher_wgrad, and medgp_hess_vec's k_hess_moments,
-   k_hess_slabsum, k_hess_beta, k_hess_wgrad, k_hess_epilogue -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
+   k_hess_slabsum, k_hess_beta, k_hess_wgrad, k_hess_epilogue, and medgp_posterior_jvp_batch's k_pjvp_solve, k_pjvp_u, k_pjvp_dir (ids 43 to 45) -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
    in the same way.  A caller that wants every entry walks [0, medgp_profile_num_kernels_ext()) and does not assume its length. */
 int medgp_profile_num_kernels_ext(void);
 const char *medgp_profile_kernel_name(int k);

@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_posterior_jvp_batch", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at", "medgp_gmm_fit",
 ]
 
@@ -99,6 +99,7 @@ def load():
     lib.medgp_lgo_grad.argtypes = [vp, C.c_int, i32p, dp, i32p, i32p, C.c_int, dp, dp, i32p, i32p]
     lib.medgp_fisher_vec.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, i32p]
     lib.medgp_hess_vec.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, dp, i32p]
+    lib.medgp_posterior_jvp_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, fp, fp, dp, dp, i32p]
     lib.medgp_forecast_grad.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, C.c_int, dp, dp, i32p]
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
     lib.medgp_trend_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, fp, fp, i32p]
@@ -861,6 +862,40 @@ class Context:
                                            _ptr(v, C.c_double), _ptr(hvec, C.c_double), _ptr(grad, C.c_double) if want_grad else None,
                                            _ptr(status, C.c_int32)))
         return (hvec, grad, status) if want_grad else (hvec, status)
+
+    def posterior_jvp(self, slots, theta, meta2_list, t2_list, vecs, want_posterior=True):
+        """medgp_posterior_jvp_batch: the directional derivatives of the posterior mean and variance at every test point along
+        directions in theta space, from one factorisation per patient.  slots, theta, meta2_list, t2_list as posterior(); vecs
+        [nbatch, nvec, H] or [nbatch, H] (one direction each), as fisher_vec takes it.
+        Returns ([(mean[m], var[m], dmean[m, nvec], dvar[m, nvec]) per patient], status); mean and var are None without
+        want_posterior.  A failed patient's rows are NaN."""
+        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
+        nb = slots.shape[0]
+        v = np.ascontiguousarray(vecs, dtype=np.float64)
+        if v.ndim not in (2, 3) or v.shape[0] != nb or v.shape[-1] != self.H:
+            raise ValueError(f"vecs of shape {v.shape} for {nb} patients of {self.H} hypers")
+        nvec = 1 if v.ndim == 2 else v.shape[1]
+        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum(cnt)
+        M = int(offsets[-1])
+        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
+        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+        mean = np.empty(max(M, 1), dtype=np.float32) if want_posterior else None
+        var = np.empty(max(M, 1), dtype=np.float32) if want_posterior else None
+        dmean = np.empty((max(M, 1), nvec))
+        dvar = np.empty((max(M, 1), nvec))
+        st = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_posterior_jvp_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
+                                                      offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
+                                                      int(nvec), _ptr(v, C.c_double), _ptr(mean, C.c_float), _ptr(var, C.c_float),
+                                                      _ptr(dmean, C.c_double), _ptr(dvar, C.c_double), _ptr(st, C.c_int32)))
+        out = []
+        for b in range(nb):
+            a, e = int(offsets[b]), int(offsets[b + 1])
+            out.append((mean[a:e].copy() if want_posterior else None, var[a:e].copy() if want_posterior else None,
+                        dmean[a:e].copy(), dvar[a:e].copy()))
+        return out, st
 
     def forecast_grad(self, slots, theta, prefixes=None, flag_grad=1):
         """medgp_forecast_grad: the negative forecast score J = - sum_i lpd_i (plus the prior term, as nlml_grad) and its gradient in

@@ -26,6 +26,7 @@
 #include "kernels_lgo_grad.h"
 #include "kernels_fisher.h"
 #include "kernels_hess.h"
+#include "kernels_posterior_jvp.h"
 
 #include <algorithm>
 #include <chrono>
@@ -40,8 +41,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_PJ_SOLVE, KID_PJ_U, KID_PJ_DIR, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue", "k_pjvp_solve", "k_pjvp_u", "k_pjvp_dir"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -97,9 +98,12 @@ struct Arena {
 //   medgp_hess_vec (hess_tables.h): the five Fisher buffers in the same roles; BUF_HE_SLAB the two-plane slab of the raw moments M3, M4;
 //   BUF_HE_SUMS the block sums [S | SM | SV | M3 | M4] of the W pass, each [nbatch][Q D D]; BUF_HE_VEC [beta | diag(W)], each laid out
 //   like alpha
+//   medgp_posterior_jvp_batch (pjvp_tables.h): BUF_FI_KDOT, BUF_FI_COEF, BUF_FI_DIR in the Fisher call's roles; BUF_PJ_U u = Kdot alpha,
+//   laid out like alpha; BUF_PJ_OUT [dmean | dvar], each [M][nvec]; the per-point buffers, the tile table and the work rows in the
+//   posterior call's roles
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_PJ_U, BUF_PJ_OUT, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -868,7 +872,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 17; }
+int medgp_abi_version(void) { return 18; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2770,6 +2774,97 @@ int medgp_hess_vec(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
         for (int j = 0; j < nvec; j++)
             std::memcpy(hvec + ((size_t)b * nvec + j) * H, out.data() + ((size_t)j * nbatch + b) * H, H * sizeof(double));
     return MEDGP_OK;
+}
+
+// Directional derivatives of the posterior in the hypers (kernels_posterior_jvp.h).  ONE pipeline run in the grouped order (factor,
+// U = L^-T, alpha), then per size class and launch chunk of its tiles, in stream order: k_pjvp_solve (W = P K* into the chunk's work
+// rows, mean, var) and, direction by direction, k_fisher_prep, k_fisher_kdot, k_pjvp_u (u = Kdot alpha) and k_pjvp_dir.  A class has one
+// chunk unless its work rows exceed MEDGP_POSTERIOR_BUDGET_GB; then every chunk forms the direction's Kdot again (the same bits).  Kdot,
+// the coefficient blocks and u are buffers of the call, reused by every direction; every direction runs the same launches with the
+// same geometry.  L is never overwritten.  The three matrices of every entry are alive at once: a call that needs more than the memory
+// budget is refused (pjvp_tables.h), there are no memory waves.
+int medgp_posterior_jvp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                              const int32_t *meta2, const float *t2, int nvec, const double *vec, float *mean, float *var, double *dmean,
+                              double *dvar, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || !offsets || !vec || !dmean || !dvar) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    if (nvec < 1) return fail(c, MEDGP_ERR_ARG, "nvec = %d", nvec);
+    if ((mean == nullptr) != (var == nullptr)) return fail(c, MEDGP_ERR_ARG, "mean and var: both or neither");
+    if (c->rules.Q > PJVP_MAX_Q) return fail(c, MEDGP_ERR_ARG, "medgp_posterior_jvp_batch supports Q <= 16 (Q = %d)", c->rules.Q);
+    int rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    // (mean / var are optional here: the per-point outputs the call requires are dmean / dvar, checked above)
+    if ((rc = check_points(c, nbatch, offsets, meta2, t2, (const float *)dmean, (const float *)dvar, "dmean / dvar"))) return rc;
+    const int64_t M = offsets[nbatch];
+    std::vector<double> ht2;
+    std::vector<int> hm2;
+    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
+    const BatchPlan &P = c->plan;
+    if (P.nwaves > 1 || !pjvp_fits(P.need_mat, c->rules.mem_budget))
+        return fail(c, MEDGP_ERR_CAPACITY, "the call's per-entry matrices (%d of %zu MB) exceed the memory budget of %zu MB (MEDGP_MEM_BUDGET_GB): split the call",
+                    PJVP_MATS, (P.need_mat * sizeof(double)) >> 20, c->rules.mem_budget >> 20);
+    const size_t H = c->H;
+    const PjvpBuffers pb = pjvp_buffers(P.need_mat, P.need_vec, nbatch, nvec, (int)H, c->rules.Q, c->rules.D, M);
+    PointTables<PostTile> T;
+    build_pjvp_tiles(table_classes(P), P.order.data(), offsets, c->posterior_budget, T);
+    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
+    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
+    if ((rc = buf_ensure(c, BUF_FI_KDOT, pb.mat_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FI_COEF, pb.coef_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_FI_DIR, pb.dir_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_PJ_U, std::max<size_t>(pb.u_doubles, 1) * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_PJ_OUT, pb.out_doubles * sizeof(double)))) return rc;
+    double *kdot = buf<double>(c, BUF_FI_KDOT), *coef = buf<double>(c, BUF_FI_COEF), *d_dir = buf<double>(c, BUF_FI_DIR);
+    double *uvec = buf<double>(c, BUF_PJ_U), *d_dmean = buf<double>(c, BUF_PJ_OUT), *d_dvar = d_dmean + pjvp_dvar_offset(M, nvec);
+    HIPCHK(c, hipMemcpyAsync(d_dir, vec, pb.dir_doubles * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // the generic kernels (MEDGP_V0) are not honoured: this call always takes the templated ones, as the Fisher call
+    const bool v0 = c->rules.use_v0;
+    c->rules.use_v0 = false;
+    rc = factor_run(c, nbatch, theta, true, false);
+    c->rules.use_v0 = v0;
+    if (rc) return rc;
+    for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
+        const SizeClass &k = P.cls[ch.cls];
+        const MedgpDev V = class_view(c, P, k);
+        const int nb = k.count, nt64 = k.nbmax;
+        const PostTile *tiles = buf<PostTile>(c, BUF_TILES) + ch.t0;
+        double *Kd = kdot + k.off_mat, *cf = coef + (size_t)k.b0 * V.hyp_stride, *u = uvec + k.off_vec;
+        {
+            Launcher l(c, KID_PJ_SOLVE);
+            hipLaunchKernelGGL(k_pjvp_solve, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK),
+                               ch.stride, nvec, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), d_dmean, d_dvar);
+        }
+        for (int j = 0; j < nvec; j++) {
+            {
+                Launcher l(c, KID_FI_PREP);
+                hipLaunchKernelGGL(k_fisher_prep, dim3(nb, 1 + (V.Q * V.D * V.D + 255) / 256), dim3(256), 0, c->stream, V, c->d_theta, d_dir, nvec, j, cf);
+            }
+            {
+                Launcher l(c, KID_FI_KDOT);   // (Q <= 16 was checked)
+                with_q16(V.Q, [&](auto q, auto q0) {
+                    hipLaunchKernelGGL((k_fisher_kdot<decltype(q)::value, decltype(q0)::value>), dim3(fisher_kdot_grid(nt64), nb), dim3(256), 0, c->stream, V, cf, Kd);
+                });
+            }
+            { Launcher l(c, KID_PJ_U); hipLaunchKernelGGL(k_pjvp_u, dim3(pjvp_u_grid(nt64), nb), dim3(256), 0, c->stream, V, Kd, u); }
+            Launcher l(c, KID_PJ_DIR);
+            hipLaunchKernelGGL(k_pjvp_dir, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK),
+                               ch.stride, cf, Kd, u, nvec, j, d_dmean, d_dvar);
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    if (M > 0) {
+        const size_t nout = (size_t)M * nvec;
+        HIPCHK(c, hipMemcpyAsync(dmean, d_dmean, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dvar, d_dvar, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
+        if (mean) {
+            HIPCHK(c, hipMemcpyAsync(mean, buf<float>(c, BUF_MEAN), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(var, buf<float>(c, BUF_VAR), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    return read_status(c, nbatch, status);
 }
 
 // The negative forecast score and its gradient (kernels_forecast_grad.h).  ONE pipeline run in the CALLER's order (as
