@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 18: medgp_posterior_jvp_batch (17: medgp_hess_vec; 16: medgp_fisher_vec; 15: medgp_lgo_grad; 14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 19: medgp_posterior_vjp_batch, medgp_posterior_vjp_moments (18: medgp_posterior_jvp_batch; 17: medgp_hess_vec; 16: medgp_fisher_vec; 15: medgp_lgo_grad; 14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -480,11 +480,70 @@ int medgp_hess_vec(medgp_ctx *ctx, int nbatch, const int32_t *slots, const doubl
  * direction's position, on the other points or their order, on the tile a point lands in, or on how the call is cut into launches.
  * medgp_get_factor is VALID afterwards: the call overwrites neither L nor L^-1, alpha or the log determinant.
  * Out of scope: Q > 16; derivatives of parts, of the joint covariance, of trend, components and functionals; the second-order mean
- * correction; the reverse mode.
+ * correction.  The reverse mode is medgp_posterior_vjp_batch.
  * All pointers are HOST memory. */
 int medgp_posterior_jvp_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
                               const int32_t *meta2, const float *t2, int nvec, const double *vec, float *mean, float *var, double *dmean,
                               double *dvar, int32_t *status);
+
+/* The reverse mode of medgp_posterior_jvp_batch: the gradient over ALL hypers of any scalar loss of the predictions, from ONE
+ * factorisation per patient and one weighted gradient pass (about the work of one medgp_nlml_grad plus the W = K^-1 K* solve the JVP
+ * call has), instead of one JVP direction per hyper.  For cotangents cm_j = dloss/dmean_j, cv_j = dloss/dvar_j at the test points,
+ *   grad_h = sum_j cm_j dmean_j/dtheta_h + cv_j dvar_j/dtheta_h,
+ * with mean, var, dmean and dvar exactly those of medgp_posterior_jvp_batch.  The definition is the identity with the JVP: for every
+ * direction v, grad . v = sum_j cm_j dmean_j(v) + cv_j dvar_j(v); its long-double restatement is tests/posterior_vjp_truth.py.  With
+ * c = W cm and Wc = W diag(cv) the device evaluates  1/2 tr(G dK/dtheta_h),  G = 2 Wc W^T - (c alpha^T + alpha c^T)  (the nlml gradient's
+ * reduction with G in the place of K^-1 - alpha alpha^T; G never reaches memory),  sum_ij R_ij dk*_ij/dtheta_h,  R = alpha cm^T - 2 Wc,
+ * and the test-diagonal terms  sum_j cv_j (sum_q dB_q[m_j,m_j]/dtheta_h + 2 sigma^2_{m_j} [h = sigma_{m_j}]).
+ * nbatch, slots, theta, offsets, meta2, t2, mean, var and status mean exactly what they mean for medgp_posterior_jvp_batch: one
+ * factorisation per patient, no n > 2 guard, status[b] = jitter rounds or -1, an empty range of points is allowed (its gradient is
+ * zero, its built-in loss 0), meta2 may be NULL for SE / SM, mean / var are both given or both NULL and held to tests/posterior_ref.py's
+ * 2-ulp bar.
+ *   loss_kind = MEDGP_PLOSS_CUSTOM (0): cot_mean[j * ncot + k], cot_var[j * ncot + k] are the caller's cotangents of point j (counting
+ *     the points of the call) in set k, ncot >= 1; grad[(b * ncot + k) * H ..] is the gradient of set k over the points of entry b.
+ *     loss, y2 and wt must be NULL.  ncot > 1 serves Jacobian rows of a few points: cheaper than H JVP directions when m < H.
+ *   Built-in kinds: the device forms the cotangents in fp64 from its own fp64 mean_j, var_j (the float outputs are roundings of
+ *     the same quantities, not their source), so a held-out score and its gradient cost one factorisation.  ncot must be 1, cot_mean
+ *     and cot_var NULL, y2[j] and loss are required, wt[j] is optional (NULL = 1; it multiplies l_j).  loss[b] = sum_j wt_j l_j, summed
+ *     in the caller's point order; grad[b * H ..] its gradient.
+ *       MEDGP_PLOSS_NLPD (1)   l = 1/2 log(2 pi var) + (y - mean)^2 / (2 var), with the true pi (medgp_set_pi plays no part)
+ *       MEDGP_PLOSS_SQERR (2)  l = (y - mean)^2
+ *       MEDGP_PLOSS_CRPS (3)   s = sqrt(var), z = (y - mean) / s:  l = s (z (2 Phi(z) - 1) + 2 phi(z) - 1 / sqrt(pi));
+ *                              dl/dmean = -(2 Phi(z) - 1),  dl/dvar = (2 phi(z) - 1 / sqrt(pi)) / (2 s)
+ *     var is the unclamped predictive variance with the noise included once, as in the JVP call.  A non-positive (or NaN) var_j
+ *     under NLPD / CRPS makes that entry's loss and every line of its grad NaN; its batch-mates are untouched.
+ *   An unknown kind, ncot < 1, ncot != 1 with a built-in kind, missing or superfluous cot_mean / cot_var / y2 / loss / wt, only one
+ *     of mean / var, NULL slots, theta, offsets or grad: MEDGP_ERR_ARG before any device work.
+ * Conventions of the JVP call, unchanged.  Jitter: after k rounds P and alpha belong to K + k diag(sigma^2) while the derivatives are
+ * those of the UN-jittered kernel and are not scaled by 1 + k.  Priors play no part: a prior descriptor changes no bit.  A patient with
+ * status[b] < 0 gets NaN in loss, grad, mean and var; its batch-mates are untouched.  All three covariance families; Q <= 16 only
+ * (Q > 16: MEDGP_ERR_ARG; 8 < Q <= 16 runs the tile kernel twice), MEDGP_V0 is not honoured.  |t| <= 2^14 h.  medgp_get_factor is VALID
+ * afterwards with the bits it has after medgp_nlml_grad: the call overwrites neither L nor L^-1, alpha or the log determinant.
+ * Memory: no matrix beyond the two of the factorisation; two ldn x 64 panels of work rows per tile of 64 points.  The work rows of all
+ * tiles of an entry are resident for its product, so the call is cut into launches BETWEEN entries, within MEDGP_POSTERIOR_BUDGET_GB;
+ * one entry alone beyond that budget, or per-entry matrices beyond the memory budget: MEDGP_ERR_CAPACITY (no memory waves).
+ * Determinism: no atomics, every sum in a fixed order over the entry's own operands.  The host sorts every patient's points by
+ * covariate (stable) before the upload.  With the route pinned the bits of (entry, set) depend on the patient, theta, its points and
+ * that set alone -- not on the batch-mates, on ncot or the set's position, on whether mean / var are asked for, or on how the call is
+ * cut into launches.  They DO depend on the order of the points that share a covariate (independence of the points' order is NOT
+ * promised); a built-in kind and the custom kind fed the same cotangents agree to rounding of the cotangents, not to bits.
+ * Out of scope: Q > 16; cotangents of parts, joint covariance, trend, components and functionals; the Hessian of a predictive loss;
+ * priors (add medgp_nlml_grad's prior lines on the host if wanted); device-resident theta / cotangents.
+ * All pointers are HOST memory. */
+#define MEDGP_PLOSS_CUSTOM 0
+#define MEDGP_PLOSS_NLPD   1
+#define MEDGP_PLOSS_SQERR  2
+#define MEDGP_PLOSS_CRPS   3
+int medgp_posterior_vjp_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                              const int32_t *meta2, const float *t2, int loss_kind, const double *y2, const double *wt, int ncot,
+                              const double *cot_mean, const double *cot_var, float *mean, float *var, double *loss, double *grad,
+                              int32_t *status);
+/* The fp64 plug-in mean and var the LAST medgp_posterior_vjp_batch of this context evaluated on the device -- the quantities its
+ * built-in kinds form their cotangents from; the float mean / var of that call are held to the posterior call's bar, these to the
+ * fp64 budget -- in the caller's point order (M = offsets[nbatch] of that call, else MEDGP_ERR_ARG; NaN for a patient with
+ * status < 0).  A caller that forms its own cotangents in fp64 (medgp_amd.predictive.TorchPosterior) reads them here.  Valid until
+ * the next medgp_posterior_vjp_batch of the context; without one before it: MEDGP_ERR_ARG.  Host pointers. */
+int medgp_posterior_vjp_moments(medgp_ctx *ctx, int64_t M, double *mean, double *var);
 
 /* Rolling-origin forecasts: every test point predicted from a LEADING block of its patient's observations, all from ONE
  * factorisation per patient -- what the model says at time t from what was known before t.
@@ -814,7 +873,9 @@ int medgp_profile_num_kernels_all(void);
 /* medgp_profile_num_kernels_all is pinned as well, at the 29 entries it had when medgp_forecast_grad added it (its callers compare
    the whole list).  Entries added since -- medgp_lgo_grad's k_lgo_vec (k_lgo_mask, k_lgo_prep and k_lgo_obj), k_lgo_inv, k_lgo_s,
    k_lgo_t, k_lgo_wgrad, medgp_fisher_vec's k_fisher_prep, k_fisher_kdot, k_fisher_t, k_fisher_wgrad, and medgp_hess_vec's k_hess_moments,
-   k_hess_slabsum, k_hess_beta, k_hess_wgrad, k_hess_epilogue, and medgp_posterior_jvp_batch's k_pjvp_solve, k_pjvp_u, k_pjvp_dir (ids 43 to 45) -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
+   k_hess_slabsum, k_hess_beta, k_hess_wgrad, k_hess_epilogue, and medgp_posterior_jvp_batch's k_pjvp_solve, k_pjvp_u, k_pjvp_dir (ids 43 to 45), and
+   medgp_posterior_vjp_batch's k_pvjp_cot, k_pvjp_wgrad, k_pvjp_cross, k_pvjp_finish (ids 46 to 49; its k_slabsum and k_epilogue launches are
+   accounted under "k_epilogue", its solve under "k_pjvp_solve") -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
    in the same way.  A caller that wants every entry walks [0, medgp_profile_num_kernels_ext()) and does not assume its length. */
 int medgp_profile_num_kernels_ext(void);
 const char *medgp_profile_kernel_name(int k);

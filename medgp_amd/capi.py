@@ -23,7 +23,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_posterior_jvp_batch", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_posterior_jvp_batch", "medgp_posterior_vjp_batch", "medgp_posterior_vjp_moments", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at", "medgp_gmm_fit",
 ]
 
@@ -100,6 +100,10 @@ def load():
     lib.medgp_fisher_vec.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, i32p]
     lib.medgp_hess_vec.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, dp, i32p]
     lib.medgp_posterior_jvp_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, fp, fp, dp, dp, i32p]
+    lib.medgp_posterior_vjp_batch.restype = C.c_int
+    lib.medgp_posterior_vjp_moments.restype = C.c_int
+    lib.medgp_posterior_vjp_moments.argtypes = [vp, C.c_int64, dp, dp]
+    lib.medgp_posterior_vjp_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, dp, C.c_int, dp, dp, fp, fp, dp, dp, i32p]
     lib.medgp_forecast_grad.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, C.c_int, dp, dp, i32p]
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
     lib.medgp_trend_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, fp, fp, fp, fp, i32p]
@@ -895,6 +899,78 @@ class Context:
             a, e = int(offsets[b]), int(offsets[b + 1])
             out.append((mean[a:e].copy() if want_posterior else None, var[a:e].copy() if want_posterior else None,
                         dmean[a:e].copy(), dvar[a:e].copy()))
+        return out, st
+
+    PLOSS = {"custom": 0, "nlpd": 1, "sqerr": 2, "crps": 3}
+
+    def posterior_vjp(self, slots, theta, meta2_list, t2_list, cot_mean=None, cot_var=None, loss=None, y2_list=None, wt_list=None,
+                      want_posterior=True, fp64_posterior=False):
+        """medgp_posterior_vjp_batch: the gradient in theta of a loss of the predictions, from one factorisation per patient.
+        slots, theta, meta2_list, t2_list as posterior().  Either
+          loss=None: cot_mean, cot_var are lists (one array per patient) of the cotangents of the patient's points, each [m] or
+            [m, ncot] (the same ncot for all); returns ([(mean[m], var[m], grad[ncot, H]) per patient], status);
+          loss="nlpd" | "sqerr" | "crps": y2_list (one array [m] per patient) and optionally wt_list; returns
+            ([(mean[m], var[m], grad[H], loss) per patient], status).
+        mean and var are None without want_posterior; with fp64_posterior they are the float64 values the device formed its
+        cotangents from (medgp_posterior_vjp_moments) instead of the float outputs.  A failed patient's rows are NaN."""
+        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
+        nb = slots.shape[0]
+        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum(cnt)
+        M = int(offsets[-1])
+        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
+        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+
+        def per_point(lst, what, width=None):
+            if len(lst) != nb:
+                raise ValueError(f"{what}: {len(lst)} arrays for {nb} patients")
+            rows = []
+            for b, x in enumerate(lst):
+                a = np.asarray(x, dtype=np.float64)
+                a = a.reshape(int(cnt[b]), -1) if cnt[b] else np.zeros((0, 0))
+                if width is not None and a.shape[1] != width and a.shape[0]:
+                    raise ValueError(f"{what}[{b}] of shape {a.shape}, expected [{int(cnt[b])}, {width}]")
+                rows.append(a)
+            w = width if width is not None else max([r.shape[1] for r in rows if r.shape[0]] or [1])
+            rows = [r if r.shape[0] else np.zeros((0, w)) for r in rows]
+            for b, r in enumerate(rows):
+                if r.shape[1] != w:
+                    raise ValueError(f"{what}[{b}] has {r.shape[1]} columns, others {w}")
+            return np.ascontiguousarray(np.concatenate(rows) if M else np.zeros((1, w))), w
+
+        if loss is None:
+            if cot_mean is None or cot_var is None or y2_list is not None or wt_list is not None:
+                raise ValueError("custom cotangents: cot_mean and cot_var are required, y2_list / wt_list are not taken")
+            cm, ncot = per_point(cot_mean, "cot_mean")
+            cv, _ = per_point(cot_var, "cot_var", ncot)
+            kind, y2, wt, lossv = 0, None, None, None
+        else:
+            if loss not in self.PLOSS or loss == "custom":
+                raise ValueError(f"loss {loss!r}: one of 'nlpd', 'sqerr', 'crps', or None for custom cotangents")
+            if y2_list is None or cot_mean is not None or cot_var is not None:
+                raise ValueError("a built-in loss takes y2_list and no cotangents")
+            kind, ncot, cm, cv = self.PLOSS[loss], 1, None, None
+            y2 = per_point(y2_list, "y2_list", 1)[0]
+            wt = per_point(wt_list, "wt_list", 1)[0] if wt_list is not None else None
+            lossv = np.empty(nb)
+        mean = np.empty(max(M, 1), dtype=np.float32) if want_posterior else None
+        var = np.empty(max(M, 1), dtype=np.float32) if want_posterior else None
+        grad = np.empty((nb, ncot, self.H))
+        st = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_posterior_vjp_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
+                                                      offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
+                                                      kind, _ptr(y2, C.c_double), _ptr(wt, C.c_double), int(ncot), _ptr(cm, C.c_double),
+                                                      _ptr(cv, C.c_double), _ptr(mean, C.c_float), _ptr(var, C.c_float),
+                                                      _ptr(lossv, C.c_double), _ptr(grad, C.c_double), _ptr(st, C.c_int32)))
+        if want_posterior and fp64_posterior:
+            mean, var = np.empty(max(M, 1)), np.empty(max(M, 1))
+            self._chk(self._lib.medgp_posterior_vjp_moments(self._h, M, _ptr(mean, C.c_double), _ptr(var, C.c_double)))
+        out = []
+        for b in range(nb):
+            a, e = int(offsets[b]), int(offsets[b + 1])
+            mv = (mean[a:e].copy(), var[a:e].copy()) if want_posterior else (None, None)
+            out.append(mv + ((grad[b].copy(),) if loss is None else (grad[b, 0].copy(), float(lossv[b]))))
         return out, st
 
     def forecast_grad(self, slots, theta, prefixes=None, flag_grad=1):

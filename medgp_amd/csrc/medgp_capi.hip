@@ -27,6 +27,7 @@
 #include "kernels_fisher.h"
 #include "kernels_hess.h"
 #include "kernels_posterior_jvp.h"
+#include "kernels_posterior_vjp.h"
 
 #include <algorithm>
 #include <chrono>
@@ -41,8 +42,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_PJ_SOLVE, KID_PJ_U, KID_PJ_DIR, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue", "k_pjvp_solve", "k_pjvp_u", "k_pjvp_dir"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_PJ_SOLVE, KID_PJ_U, KID_PJ_DIR, KID_PV_COT, KID_PV_WGRAD, KID_PV_CROSS, KID_PV_FINISH, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue", "k_pjvp_solve", "k_pjvp_u", "k_pjvp_dir", "k_pvjp_cot", "k_pvjp_wgrad", "k_pvjp_cross", "k_pvjp_finish"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -101,9 +102,13 @@ struct Arena {
 //   medgp_posterior_jvp_batch (pjvp_tables.h): BUF_FI_KDOT, BUF_FI_COEF, BUF_FI_DIR in the Fisher call's roles; BUF_PJ_U u = Kdot alpha,
 //   laid out like alpha; BUF_PJ_OUT [dmean | dvar], each [M][nvec]; the per-point buffers, the tile table and the work rows in the
 //   posterior call's roles
+//   medgp_posterior_vjp_batch (pvjp_tables.h): BUF_PV_ENT the per-entry records, BUF_PV_SEG the covariate ranges of every entry's
+//   points, BUF_PV_ORD caller point -> device point; BUF_PV_IN the caller's per-point inputs, BUF_PV_PTS the cotangents, loss terms and
+//   cos / sin tables of the points, BUF_PV_VEC c = W cm (laid out like alpha), BUF_PV_SMALL per entry [sum cv D | loss | -], BUF_PV_OUT
+//   the gradients, set-major [ncot][nbatch][H]; the per-point buffers, the tile table and the work rows in the posterior call's roles
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_PJ_U, BUF_PJ_OUT, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_PJ_U, BUF_PJ_OUT, BUF_PV_ENT, BUF_PV_SEG, BUF_PV_ORD, BUF_PV_IN, BUF_PV_PTS, BUF_PV_VEC, BUF_PV_SMALL, BUF_PV_OUT, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -183,6 +188,8 @@ struct medgp_ctx {
     size_t bounce_cap = 0;
     int *d_one_slot = nullptr;       // single-entry slot table for the caller-order re-factorisation of medgp_get_factor
     DevBuf buf[BUF_COUNT];          // the inference entry points' buffers (enum BufId)
+    std::vector<int64_t> pv_src;    // medgp_posterior_vjp_batch: device point -> caller point of the last call (medgp_posterior_vjp_moments)
+    bool pv_valid = false;          // ... and whether BUF_PV_PTS still holds that call's fp64 mean / var
     size_t posterior_budget = (size_t)2 << 30;   // MEDGP_POSTERIOR_BUDGET_GB
     // profiling
     bool profiling = false;
@@ -872,7 +879,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 18; }
+int medgp_abi_version(void) { return 19; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -2865,6 +2872,178 @@ int medgp_posterior_jvp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
         }
     }
     return read_status(c, nbatch, status);
+}
+
+// The gradient of a loss of the predictions in the hypers (kernels_posterior_vjp.h).  ONE pipeline run in the grouped order (factor,
+// U = L^-T, z, alpha), then per size class and launch chunk of whole entries, in stream order: k_pjvp_solve (W = P K* and V = L^-1 K*
+// into the chunk's work rows, mean, var) and, cotangent set by set, k_pvjp_cot, k_pvjp_wgrad (G tiles -> slab, wdiag), the nlml
+// gradient's own k_slabsum, k_pvjp_cross (rectangular sums and the test diagonal folded into S, SM, SV), k_epilogue told to leave the
+// prior and the scalar out, and k_pvjp_finish.  Every set runs the same launches with the same geometry.  The points travel sorted by
+// covariate inside every patient (pvjp_tables.h); mean and var go back in the caller's order.  L, U and alpha are never overwritten.
+int medgp_posterior_vjp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                              const int32_t *meta2, const float *t2, int loss_kind, const double *y2, const double *wt, int ncot,
+                              const double *cot_mean, const double *cot_var, float *mean, float *var, double *loss, double *grad,
+                              int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!slots || !theta || !offsets || !grad) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    c->pv_valid = false;
+    if (loss_kind < MEDGP_PLOSS_CUSTOM || loss_kind > MEDGP_PLOSS_CRPS) return fail(c, MEDGP_ERR_ARG, "unknown loss_kind %d", loss_kind);
+    if (ncot < 1) return fail(c, MEDGP_ERR_ARG, "ncot = %d", ncot);
+    if ((mean == nullptr) != (var == nullptr)) return fail(c, MEDGP_ERR_ARG, "mean and var: both or neither");
+    const bool builtin = loss_kind != MEDGP_PLOSS_CUSTOM;
+    if (builtin && ncot != 1) return fail(c, MEDGP_ERR_ARG, "ncot = %d with a built-in loss (1 expected)", ncot);
+    if (builtin && (cot_mean || cot_var)) return fail(c, MEDGP_ERR_ARG, "cot_mean / cot_var given with a built-in loss");
+    if (builtin && (!loss || !y2)) return fail(c, MEDGP_ERR_ARG, "loss / y2 is NULL with a built-in loss");
+    if (!builtin && (!cot_mean || !cot_var)) return fail(c, MEDGP_ERR_ARG, "cot_mean / cot_var is NULL with MEDGP_PLOSS_CUSTOM");
+    if (!builtin && (loss || y2 || wt)) return fail(c, MEDGP_ERR_ARG, "loss / y2 / wt given with MEDGP_PLOSS_CUSTOM");
+    if (c->rules.Q > PJVP_MAX_Q) return fail(c, MEDGP_ERR_ARG, "medgp_posterior_vjp_batch supports Q <= 16 (Q = %d)", c->rules.Q);
+    int rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    // (mean / var are optional here: the per-point inputs the call requires stand in their place)
+    const float *need_a = (const float *)(builtin ? y2 : cot_mean), *need_b = (const float *)(builtin ? y2 : cot_var);
+    if ((rc = check_points(c, nbatch, offsets, meta2, t2, need_a, need_b, builtin ? "y2" : "cot_mean / cot_var"))) return rc;
+    const int64_t M = offsets[nbatch];
+    const int D = c->rules.D, Q = c->rules.Q;
+    const bool lmc = c->kidx == MEDGP_KERNEL_LMC_SM;
+    if (lmc && meta2)
+        for (int64_t j = 0; j < M; j++)
+            if (meta2[j] < 0 || meta2[j] >= D) return fail(c, MEDGP_ERR_ARG, "meta2[%lld] = %d outside [0, %d)", (long long)j, meta2[j], D);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
+    const BatchPlan &P = c->plan;
+    if (P.nwaves > 1 || !pvjp_fits(P.need_mat, c->rules.mem_budget))
+        return fail(c, MEDGP_ERR_CAPACITY, "the call's per-entry matrices (%d of %zu MB) exceed the memory budget of %zu MB (MEDGP_MEM_BUDGET_GB): split the call",
+                    PVJP_MATS, (P.need_mat * sizeof(double)) >> 20, c->rules.mem_budget >> 20);
+    PvjpTables T;
+    TableError terr{};
+    if (!build_pvjp_tables(table_classes(P), P.order.data(), offsets, (lmc && M > 0) ? meta2 : nullptr, nbatch, D, c->posterior_budget, T, terr))
+        return fail(c, MEDGP_ERR_CAPACITY, "patient %d: the work rows of its %lld test points (%zu MB) exceed the budget of %zu MB (MEDGP_POSTERIOR_BUDGET_GB): split its points",
+                    terr.b, terr.m, terr.need >> 20, c->posterior_budget >> 20);
+    std::vector<double> ht2;
+    std::vector<int> hm2;
+    if ((rc = stage_points(c, M, meta2, t2, T.src.data(), ht2, hm2))) return rc;
+    const size_t H = c->H, Mz = pvjp_mz(M);
+    const PvjpBuffers pb = pvjp_buffers(P.need_vec, nbatch, ncot, (int)H, Q, D, M);
+    // the caller's per-point inputs in the device's point order, the cotangent sets set-major
+    std::vector<double> hin(pb.in_doubles, 0.0);
+    for (int64_t k = 0; k < M; k++) {
+        const int64_t j = T.src[(size_t)k];
+        if (builtin) {
+            hin[2 * Mz + (size_t)k] = y2[j];
+            hin[3 * Mz + (size_t)k] = wt ? wt[j] : 1.0;
+        } else
+            for (int s = 0; s < ncot; s++) {
+                hin[(size_t)s * Mz + (size_t)k] = cot_mean[(size_t)j * ncot + s];
+                hin[((size_t)ncot + s) * Mz + (size_t)k] = cot_var[(size_t)j * ncot + s];
+            }
+    }
+    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
+    if ((rc = upload_table(c, BUF_PV_ENT, T.ents))) return rc;
+    if ((rc = upload_table(c, BUF_PV_SEG, T.pseg))) return rc;
+    if ((rc = upload_table(c, BUF_PV_ORD, T.dev_of))) return rc;
+    if ((rc = upload_table(c, BUF_PV_IN, hin))) return rc;
+    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
+    if ((rc = buf_ensure(c, BUF_WORK, 256))) return rc;   // (a call without points: the kernels still take the pointer)
+    if ((rc = buf_ensure(c, BUF_PV_ORD, sizeof(int)))) return rc;
+    if ((rc = buf_ensure(c, BUF_PV_PTS, pb.pts_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_PV_VEC, pb.vec_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_PV_SMALL, pb.small_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_PV_OUT, pb.out_doubles * sizeof(double)))) return rc;
+    const PvjpEnt *d_ents = buf<PvjpEnt>(c, BUF_PV_ENT);
+    const int *d_pseg = buf<int>(c, BUF_PV_SEG), *d_ord = buf<int>(c, BUF_PV_ORD), *d_meta2 = buf<int>(c, BUF_META2);
+    const double *d_in = buf<double>(c, BUF_PV_IN), *d_t2 = buf<double>(c, BUF_T2);
+    double *d_pts = buf<double>(c, BUF_PV_PTS), *d_cvec = buf<double>(c, BUF_PV_VEC), *d_small = buf<double>(c, BUF_PV_SMALL);
+    double *d_out = buf<double>(c, BUF_PV_OUT), *d_work = buf<double>(c, BUF_WORK);
+    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
+    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    // the generic kernels (MEDGP_V0) are not honoured: this call always takes the templated ones, as the JVP call
+    const bool v0 = c->rules.use_v0;
+    c->rules.use_v0 = false;
+    rc = factor_run(c, nbatch, theta, true, false);
+    c->rules.use_v0 = v0;
+    if (rc) return rc;
+    for (const PvjpChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
+        const SizeClass &k = P.cls[ch.cls];
+        const MedgpDev V = class_view(c, P, k), Vc = shifted_view(V, ch.e0);
+        const int nb = ch.ne, nt64 = k.nbmax;
+        // a view without bpos takes the entry index as the caller's row: the rows of the shifted view then start ch.e0 further
+        const size_t row0 = Vc.bpos ? 0 : (size_t)ch.e0;
+        const PvjpEnt *ents = d_ents + k.b0 + ch.e0;
+        double *small = d_small + (size_t)(k.b0 + ch.e0) * (D + 2), *cvec = d_cvec + k.off_vec + (size_t)ch.e0 * k.ld;
+        if (ch.nt > 0) {
+            Launcher l(c, KID_PJ_SOLVE);   // (nvec = 0: no derivative output is touched)
+            hipLaunchKernelGGL(k_pjvp_solve, dim3(ch.nt), dim3(256), 0, c->stream, V, buf<PostTile>(c, BUF_TILES) + ch.t0, d_meta2, d_t2, d_work, ch.stride, 0,
+                               buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), (double *)nullptr, (double *)nullptr);
+        }
+        const WgradGrid wg = wgrad_grid(P.en.data() + k.b0 + ch.e0, nb, nt64);
+        for (int s = 0; s < ncot; s++) {
+            double *g = d_out + ((size_t)s * nbatch + row0) * H;
+            {
+                Launcher l(c, KID_PV_COT);
+                hipLaunchKernelGGL(k_pvjp_cot, dim3(nb), dim3(256), 0, c->stream, Vc, ents, d_meta2, d_t2, d_ord, d_work, ch.stride, d_in, d_pts, cvec, small,
+                                   Mz, loss_kind, ncot, s, wt ? 1 : 0);
+            }
+            {
+                Launcher l(c, KID_PV_WGRAD);   // (Q <= 16 was checked)
+                with_q16(Q, [&](auto q, auto q0) {
+                    hipLaunchKernelGGL((k_pvjp_wgrad<decltype(q)::value, decltype(q0)::value>), dim3(wg.grid), dim3(WG_THREADS), 0, c->stream, Vc, ents, d_work,
+                                       ch.stride, d_pts + Mz, cvec, nb, wg.wg_tiles, wg.nbp);
+                });
+            }
+            const int nbins3 = 3 * Q * tri(D);
+            { Launcher l(c, KID_EPILOGUE); hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, Vc); }
+            {
+                Launcher l(c, KID_PV_CROSS);
+                hipLaunchKernelGGL(k_pvjp_cross, dim3(pvjp_cross_grid(D), nb), dim3(256), 0, c->stream, Vc, ents, d_pseg, d_t2, d_work, ch.stride, d_pts, small, Mz);
+            }
+            {
+                Launcher l(c, KID_EPILOGUE);
+                const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
+                hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, Vc, c->d_theta + row0 * H, 1, 1, c->d_nlml, g, c->d_status_out + row0, 2);
+            }
+            Launcher l(c, KID_PV_FINISH);
+            hipLaunchKernelGGL(k_pvjp_finish, dim3(nb), dim3(256), 0, c->stream, Vc, small, g, builtin ? 1 : 0);
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> out(pb.out_doubles), hsmall(pb.small_doubles);
+    std::vector<float> hmean, hvar;
+    HIPCHK(c, hipMemcpyAsync(out.data(), d_out, pb.out_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (builtin) HIPCHK(c, hipMemcpyAsync(hsmall.data(), d_small, pb.small_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (M > 0 && mean) {
+        hmean.resize((size_t)M); hvar.resize((size_t)M);
+        HIPCHK(c, hipMemcpyAsync(hmean.data(), buf<float>(c, BUF_MEAN), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(hvar.data(), buf<float>(c, BUF_VAR), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
+    }
+    if ((rc = read_status(c, nbatch, status))) return rc;
+    free_retired(c);
+    for (int b = 0; b < nbatch; b++)
+        for (int s = 0; s < ncot; s++)
+            std::memcpy(grad + ((size_t)b * ncot + s) * H, out.data() + ((size_t)s * nbatch + b) * H, H * sizeof(double));
+    if (builtin)
+        for (int i = 0; i < nbatch; i++) loss[P.order[i]] = hsmall[(size_t)i * (D + 2) + D];
+    if (M > 0 && mean)
+        for (int64_t k = 0; k < M; k++) { mean[T.src[(size_t)k]] = hmean[(size_t)k]; var[T.src[(size_t)k]] = hvar[(size_t)k]; }
+    c->pv_src = std::move(T.src);
+    c->pv_valid = true;
+    return MEDGP_OK;
+}
+
+// the fp64 mean and var the last medgp_posterior_vjp_batch formed its cotangents from, in the caller's point order
+int medgp_posterior_vjp_moments(medgp_ctx *c, int64_t M, double *mean, double *var) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!c->pv_valid) return fail(c, MEDGP_ERR_ARG, "no medgp_posterior_vjp_batch before this call");
+    if (M != (int64_t)c->pv_src.size()) return fail(c, MEDGP_ERR_ARG, "M = %lld, the last call had %zu points", (long long)M, c->pv_src.size());
+    if (M == 0) return MEDGP_OK;
+    if (!mean || !var) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<double> h(2 * (size_t)M);
+    const double *d = buf<double>(c, BUF_PV_PTS) + pvjp_moments_offset(c->rules.Q, M);
+    HIPCHK(c, hipMemcpyAsync(h.data(), d, 2 * (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int64_t k = 0; k < M; k++) { mean[c->pv_src[(size_t)k]] = h[(size_t)k]; var[c->pv_src[(size_t)k]] = h[(size_t)M + (size_t)k]; }
+    return MEDGP_OK;
 }
 
 // The negative forecast score and its gradient (kernels_forecast_grad.h).  ONE pipeline run in the CALLER's order (as
