@@ -545,6 +545,61 @@ int medgp_posterior_vjp_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, 
  * the next medgp_posterior_vjp_batch of the context; without one before it: MEDGP_ERR_ARG.  Host pointers. */
 int medgp_posterior_vjp_moments(medgp_ctx *ctx, int64_t M, double *mean, double *var);
 
+/* A constant BASELINE per covariate, fixed or integrated out (ABI 20).  Every other call has a zero mean: between observations and at
+ * every forecast horizon a patient's covariates revert to 0, the cohort mean after z-scoring.  Here y = H beta + f + noise with
+ * H[i, d] = [m_i = d] (n x D; SE / SM: D = 1) and
+ *   mode = MEDGP_MEAN_FIXED (1)     beta = b0: the reference's c_meanfunc_constMO with b0 its mean hypers (the scalar c_meanfunc_const is
+ *                                   the D = 1 case); lam is ignored and may be NULL
+ *        ref: mean/c_meanfunc_constMO.cpp (compute_mean_vector / compute_mean_gradients), inference/c_inference_exact.cpp:77-80, 221-232
+ *   mode = MEDGP_MEAN_MARGINAL (0)  beta_d ~ N(b0_d, 1 / lam_d) integrated out in closed form (Rasmussen & Williams section 2.7): no
+ *                                   further hyper to optimise.  lam_d = 0 is the flat prior (eq. 2.45); (0, 1) suits z-scored data.
+ * theta keeps the context's H hypers (medgp_num_hyp): the mean is a separate argument.  b0 and lam are [nbatch][D], row b for patient b.
+ * With K the matrix the pipeline factored (after its jitter rounds, as everywhere), P = K^-1, G = L^-1 H, Lambda = diag(lam),
+ * r0 = y - H b0 (the definition is tests/mean_truth.py, in long double):
+ *   A = Lambda + G^T G,  c = G^T L^-1 r0,  beta^ = b0 + A^-1 c,  alpha~ = P (y - H beta^),  W~ = P - P H A^-1 H^T P - alpha~ alpha~^T
+ *   nlml[b]  = 1/2 (r0^T P r0 - c^T A^-1 c) + 1/2 log|K| + 1/2 log|A| - 1/2 sum_{lam_d > 0} log lam_d + 1/2 (n - #{lam_d = 0}) log 2 pi
+ *              (all lam_d > 0: exactly -log N(y; H b0, K + H Lambda^-1 H^T)), minus the log prior of theta as medgp_nlml_grad
+ *   grad[b]  = 1/2 tr(W~ dK/dtheta_h), the prior lines as medgp_nlml_grad; the noise lines from diag(W~), not scaled by jitter rounds
+ *   dmean[b] = d nlml / d b0_d = -lam_d (beta^_d - b0_d) = -(H^T alpha~)_d
+ *   beta[b] = beta^,  beta_cov[b] = A^-1 ([D][D], symmetric): d nlml / d lam_d = 1/2 (A^-1)_dd + 1/2 (beta^_d - b0_d)^2 - 1/(2 lam_d)
+ *              is formed from them on the host (medgp_amd.baseline.prior_grad)
+ * FIXED: alpha~ = P r0, W~ = P - alpha~ alpha~^T, nlml = 1/2 r0^T alpha~ + 1/2 log|K| + 1/2 n log 2 pi, dmean_d = -sum_{m_i = d} alpha~_i,
+ * beta = b0, beta_cov = 0.  With b0 = 0 it is medgp_nlml_grad to rounding (another summation order: not to bits).
+ * The quadratic form is evaluated as |L^-1 r0 - G (beta^ - b0)|^2 + sum_d lam_d (beta^_d - b0_d)^2, a sum of squares: nothing cancels
+ * where lam is small.
+ * A covariate WITHOUT observations has a zero column in H: with lam_d > 0, beta^_d = b0_d and the predictive variance gains 1 / lam_d;
+ * with lam_d = 0 (MARGINAL) the model is improper for that entry: status -1, decided on the device; batch-mates are unaffected.
+ * status[b]: jitter rounds, or -1 (n <= 2 as medgp_nlml_grad, a failed factorisation, an improper entry, a failed pivot of A); the
+ * entry's outputs are then NaN.  flag_grad = 0: nlml, dmean, beta and beta_cov alone.  Every output pointer may be NULL.
+ * MEDGP_ERR_ARG before any device work: mode outside the two values, lam NULL in MARGINAL mode, a negative or NaN lam, a non-finite b0,
+ * Q > 16.  MEDGP_ERR_CAPACITY: D > 64 (the rank-D correction is ONE 64-column panel and A lives in LDS), and a call whose two
+ * per-entry matrices and three n x 64 panels exceed the memory budget (no memory waves, as medgp_fisher_vec).
+ * Blocking.  Route selection, size classes and medgp_pin_route as medgp_nlml_grad; the generic kernels (MEDGP_V0) are not honoured.
+ * No atomics: with the route pinned an entry's bits depend on the patient, theta, b0, lam and mode alone -- not on batch-mates,
+ * position, batch size or how the call is cut into launches.
+ * Accuracy: tests/test_mean_gpu.py holds every output to the fp64 budget M_MEAN max(E_programs, 2^-53) of tests/mean_truth.py.
+ * All pointers are HOST memory. */
+#define MEDGP_MEAN_MARGINAL 0
+#define MEDGP_MEAN_FIXED    1
+int medgp_mean_nlml_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int mode,
+                         const double *b0 /* [nbatch][D] */, const double *lam /* [nbatch][D]; NULL in FIXED mode */, int flag_grad,
+                         double *nlml, double *grad /* [nbatch][H] */, double *dmean /* [nbatch][D] */, double *beta /* [nbatch][D] */,
+                         double *beta_cov /* [nbatch][D][D] */, int32_t *status);
+/* The posterior at test points (m*_j, t*_j) under the same model, from ONE factorisation per patient.  With V_j = L^-1 k*_j and
+ * r_j = e_{m*_j} - G^T V_j:
+ *   mean[j] = V_j^T z + r_j^T beta^                                        (the zero-mean posterior mean plus the baseline's share)
+ *   var[j]  = (k** - V_j^T V_j + sigma^2_{m*_j}) + r_j^T A^-1 r_j          (FIXED: the last term is absent)
+ * fp64 outputs in the caller's point order; offsets / meta2 / t2 as medgp_posterior_batch (meta2 may be NULL for SE / SM and is
+ * range-checked for LMC-SM; a patient without points is allowed); no n > 2 guard, as there.  mode, b0, lam, beta, the improper-entry
+ * rule, the argument errors and the capacity rules as medgp_mean_nlml_grad; the work rows are chunked within
+ * MEDGP_POSTERIOR_BUDGET_GB.  The points of a patient with status[b] < 0 get NaN.  mean and var: both or neither may be NULL.
+ * A point's bits depend on the patient, theta, b0, lam, mode and that point alone: not on the other points or their ORDER, the tile or
+ * column it lands in, the launch chunk, or -- with the route pinned -- the batch-mates.
+ * Supported range of the time stamps: |t| <= 2^14 h, as medgp_posterior_batch.  All pointers are HOST memory. */
+int medgp_mean_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0,
+                               const double *lam, const int64_t *offsets, const int32_t *meta2, const float *t2,
+                               double *mean, double *var /* fp64, [M] */, double *beta /* [nbatch][D] */, int32_t *status);
+
 /* Rolling-origin forecasts: every test point predicted from a LEADING block of its patient's observations, all from ONE
  * factorisation per patient -- what the model says at time t from what was known before t.
  *   ref: core/gp_regression.cpp:128-214 (GP_Regression::predict), main_one_test.cpp:269-300 (the "past" training sets of the
@@ -875,7 +930,8 @@ int medgp_profile_num_kernels_all(void);
    k_lgo_t, k_lgo_wgrad, medgp_fisher_vec's k_fisher_prep, k_fisher_kdot, k_fisher_t, k_fisher_wgrad, and medgp_hess_vec's k_hess_moments,
    k_hess_slabsum, k_hess_beta, k_hess_wgrad, k_hess_epilogue, and medgp_posterior_jvp_batch's k_pjvp_solve, k_pjvp_u, k_pjvp_dir (ids 43 to 45), and
    medgp_posterior_vjp_batch's k_pvjp_cot, k_pvjp_wgrad, k_pvjp_cross, k_pvjp_finish (ids 46 to 49; its k_slabsum and k_epilogue launches are
-   accounted under "k_epilogue", its solve under "k_pjvp_solve") -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
+   accounted under "k_epilogue", its solve under "k_pjvp_solve"), and the baseline calls' k_mean_g, k_mean_small, k_mean_panel,
+   k_mean_wgrad, k_mean_post (ids 50 to 54; their k_slabsum, k_epilogue and k_pjvp_solve launches likewise) -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
    in the same way.  A caller that wants every entry walks [0, medgp_profile_num_kernels_ext()) and does not assume its length. */
 int medgp_profile_num_kernels_ext(void);
 const char *medgp_profile_kernel_name(int k);

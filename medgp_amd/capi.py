@@ -14,6 +14,7 @@ import numpy as np
 KERNEL_SE, KERNEL_LMC_SM, KERNEL_SM = 0, 7, 8
 PRIOR_NONE, PRIOR_CLAMP, PRIOR_NORMAL, PRIOR_LAPLACE = -1, 0, 1, 2
 FLAG_GRAD, FLAG_KEEP_FACTOR = 1, 2   # flag_grad bits (include/medgp_hip.h)
+MEAN_MARGINAL, MEAN_FIXED = 0, 1     # mode of the baseline calls (include/medgp_hip.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -23,7 +24,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_posterior_jvp_batch", "medgp_posterior_vjp_batch", "medgp_posterior_vjp_moments", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_posterior_jvp_batch", "medgp_posterior_vjp_batch", "medgp_posterior_vjp_moments", "medgp_mean_nlml_grad", "medgp_mean_posterior_batch", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at", "medgp_gmm_fit",
 ]
 
@@ -103,6 +104,10 @@ def load():
     lib.medgp_posterior_vjp_batch.restype = C.c_int
     lib.medgp_posterior_vjp_moments.restype = C.c_int
     lib.medgp_posterior_vjp_moments.argtypes = [vp, C.c_int64, dp, dp]
+    lib.medgp_mean_nlml_grad.restype = C.c_int
+    lib.medgp_mean_nlml_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, C.c_int, dp, dp, dp, dp, dp, i32p]
+    lib.medgp_mean_posterior_batch.restype = C.c_int
+    lib.medgp_mean_posterior_batch.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, C.POINTER(C.c_int64), i32p, fp, dp, dp, dp, i32p]
     lib.medgp_posterior_vjp_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, dp, C.c_int, dp, dp, fp, fp, dp, dp, i32p]
     lib.medgp_forecast_grad.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, C.c_int, dp, dp, i32p]
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
@@ -972,6 +977,65 @@ class Context:
             mv = (mean[a:e].copy(), var[a:e].copy()) if want_posterior else (None, None)
             out.append(mv + ((grad[b].copy(),) if loss is None else (grad[b, 0].copy(), float(lossv[b]))))
         return out, st
+
+    def _mean_args(self, nb, b0, lam, fixed):
+        """(mode, b0 [nb, D], lam [nb, D] or None) of the baseline calls; a vector [D] serves every patient"""
+        D = self.D if self.kernel_index == KERNEL_LMC_SM else 1
+
+        def rows(a, what):
+            a = np.asarray(a, dtype=np.float64)
+            if a.size == D:
+                a = np.broadcast_to(a.reshape(1, D), (nb, D))
+            if a.size != nb * D:
+                raise ValueError(f"{what} has {a.size} values, expected {D} or {nb} x {D}")
+            return np.ascontiguousarray(a.reshape(nb, D))
+        if fixed:
+            if lam is not None:
+                raise ValueError("fixed=True takes no lam (the mean is b0 itself)")
+            return MEAN_FIXED, rows(b0, "b0"), None
+        if lam is None:
+            raise ValueError("lam is required unless fixed=True (medgp_amd.baseline.standard_prior / flat build it)")
+        return MEAN_MARGINAL, rows(b0, "b0"), rows(lam, "lam")
+
+    def mean_nlml_grad(self, slots, theta, b0, lam=None, fixed=False, flag_grad=True):
+        """medgp_mean_nlml_grad: the nlml with a constant baseline per covariate -- fixed=True: the mean is b0 (the reference's
+        c_meanfunc_constMO); else beta_d ~ N(b0_d, 1 / lam_d) is integrated out (lam_d = 0: flat).  b0, lam: [D] for every patient or
+        [nbatch, D].  Returns dict(nlml [nbatch], grad [nbatch, H] or None, dmean [nbatch, D] = d nlml / d b0, beta [nbatch, D],
+        beta_cov [nbatch, D, D], status [nbatch]); a failed or improper patient's rows are NaN."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        nb = slots.shape[0]
+        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
+        mode, b0, lam = self._mean_args(nb, b0, lam, fixed)
+        D = b0.shape[1]
+        nlml, grad = np.empty(nb), (np.empty((nb, self.H)) if flag_grad else None)
+        dmean, beta, cov = np.empty((nb, D)), np.empty((nb, D)), np.empty((nb, D, D))
+        st = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_mean_nlml_grad(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), mode, _ptr(b0, C.c_double),
+                                                 _ptr(lam, C.c_double), int(bool(flag_grad)), _ptr(nlml, C.c_double), _ptr(grad, C.c_double),
+                                                 _ptr(dmean, C.c_double), _ptr(beta, C.c_double), _ptr(cov, C.c_double), _ptr(st, C.c_int32)))
+        return dict(nlml=nlml, grad=grad, dmean=dmean, beta=beta, beta_cov=cov, status=st)
+
+    def mean_posterior(self, slots, theta, meta2_list, t2_list, b0, lam=None, fixed=False):
+        """medgp_mean_posterior_batch: the posterior at test points under the baseline model of mean_nlml_grad, float64.
+        slots, theta, meta2_list, t2_list as posterior().  Returns ([(mean[m], var[m]) per patient], beta [nbatch, D], status)."""
+        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
+        nb = slots.shape[0]
+        mode, b0, lam = self._mean_args(nb, b0, lam, fixed)
+        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum(cnt)
+        M = int(offsets[-1])
+        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
+        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+        mean, var = np.empty(max(M, 1)), np.empty(max(M, 1))
+        beta = np.empty(b0.shape)
+        st = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_mean_posterior_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), mode, _ptr(b0, C.c_double),
+                                                       _ptr(lam, C.c_double), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32),
+                                                       _ptr(t2, C.c_float), _ptr(mean, C.c_double), _ptr(var, C.c_double), _ptr(beta, C.c_double),
+                                                       _ptr(st, C.c_int32)))
+        out = [(mean[int(offsets[b]):int(offsets[b + 1])].copy(), var[int(offsets[b]):int(offsets[b + 1])].copy()) for b in range(nb)]
+        return out, beta, st
 
     def forecast_grad(self, slots, theta, prefixes=None, flag_grad=1):
         """medgp_forecast_grad: the negative forecast score J = - sum_i lpd_i (plus the prior term, as nlml_grad) and its gradient in

@@ -28,6 +28,7 @@
 #include "kernels_hess.h"
 #include "kernels_posterior_jvp.h"
 #include "kernels_posterior_vjp.h"
+#include "kernels_mean.h"
 
 #include <algorithm>
 #include <chrono>
@@ -36,14 +37,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_PJ_SOLVE, KID_PJ_U, KID_PJ_DIR, KID_PV_COT, KID_PV_WGRAD, KID_PV_CROSS, KID_PV_FINISH, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue", "k_pjvp_solve", "k_pjvp_u", "k_pjvp_dir", "k_pvjp_cot", "k_pvjp_wgrad", "k_pvjp_cross", "k_pvjp_finish"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_PJ_SOLVE, KID_PJ_U, KID_PJ_DIR, KID_PV_COT, KID_PV_WGRAD, KID_PV_CROSS, KID_PV_FINISH, KID_MN_G, KID_MN_SMALL, KID_MN_PANEL, KID_MN_WGRAD, KID_MN_POST, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue", "k_pjvp_solve", "k_pjvp_u", "k_pjvp_dir", "k_pvjp_cot", "k_pvjp_wgrad", "k_pvjp_cross", "k_pvjp_finish", "k_mean_g", "k_mean_small", "k_mean_panel", "k_mean_wgrad", "k_mean_post"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -106,9 +108,12 @@ struct Arena {
 //   points, BUF_PV_ORD caller point -> device point; BUF_PV_IN the caller's per-point inputs, BUF_PV_PTS the cotangents, loss terms and
 //   cos / sin tables of the points, BUF_PV_VEC c = W cm (laid out like alpha), BUF_PV_SMALL per entry [sum cv D | loss | -], BUF_PV_OUT
 //   the gradients, set-major [ncot][nbatch][H]; the per-point buffers, the tile table and the work rows in the posterior call's roles
+//   medgp_mean_nlml_grad / medgp_mean_posterior_batch (mean_tables.h): BUF_MN_G, BUF_MN_PH, BUF_MN_PM the panels G = L^-1 H, K^-1 H and
+//   Pm (laid out like alpha, 64 doubles per row), BUF_MN_VEC [w | alpha~], BUF_MN_SMALL the per-entry blocks (beta^, dmean, delta,
+//   chol(A)^-1, A^-1), BUF_MN_IN [b0 | lam] in the caller's order, BUF_MN_OUT the fp64 [mean | var] of the posterior call's points
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_PJ_U, BUF_PJ_OUT, BUF_PV_ENT, BUF_PV_SEG, BUF_PV_ORD, BUF_PV_IN, BUF_PV_PTS, BUF_PV_VEC, BUF_PV_SMALL, BUF_PV_OUT, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_PJ_U, BUF_PJ_OUT, BUF_PV_ENT, BUF_PV_SEG, BUF_PV_ORD, BUF_PV_IN, BUF_PV_PTS, BUF_PV_VEC, BUF_PV_SMALL, BUF_PV_OUT, BUF_MN_G, BUF_MN_PH, BUF_MN_PM, BUF_MN_VEC, BUF_MN_SMALL, BUF_MN_IN, BUF_MN_OUT, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -879,7 +884,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 19; }
+int medgp_abi_version(void) { return 20; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -3043,6 +3048,207 @@ int medgp_posterior_vjp_moments(medgp_ctx *c, int64_t M, double *mean, double *v
     HIPCHK(c, hipMemcpyAsync(h.data(), d, 2 * (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int64_t k = 0; k < M; k++) { mean[c->pv_src[(size_t)k]] = h[(size_t)k]; var[c->pv_src[(size_t)k]] = h[(size_t)M + (size_t)k]; }
+    return MEDGP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// What the two baseline calls share (kernels_mean.h): the argument checks, the plan, the capacity rule, the call's buffers, [b0 | lam] to
+// the device, ONE pipeline run in the grouped order (factor, U = L^-T, z, alpha; min_n as the caller's family has it) and, per size
+// class in stream order, k_mean_g (G = L^-1 H) and k_mean_small (A, its factor, beta^, A^-1, dmean, the objective -> scal[2]; status -1
+// for an improper entry or a failed pivot of A).
+struct MeanCall {
+    MeanBuffers mb;
+    double *G, *PH, *Pm, *vec, *small, *in;
+};
+int mean_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0,
+                 const double *lam, int min_n, MeanCall &mc) {
+    if (!slots || !theta || !b0) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    if (mode != MEDGP_MEAN_MARGINAL && mode != MEDGP_MEAN_FIXED) return fail(c, MEDGP_ERR_ARG, "unknown mode %d", mode);
+    if (mode == MEDGP_MEAN_MARGINAL && !lam) return fail(c, MEDGP_ERR_ARG, "lam is NULL with MEDGP_MEAN_MARGINAL");
+    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "%s supports Q <= 16 (Q = %d)", who, c->rules.Q);
+    const int D = c->rules.D;
+    if (D > MEAN_MAX_D) return fail(c, MEDGP_ERR_CAPACITY, "%s supports D <= %d covariates (D = %d): the rank-D correction is one 64-column panel", who, MEAN_MAX_D, D);
+    int rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    for (size_t i = 0; i < (size_t)nbatch * D; i++) {
+        if (!std::isfinite(b0[i])) return fail(c, MEDGP_ERR_ARG, "b0[%zu] = %g is not finite", i, b0[i]);
+        if (mode == MEDGP_MEAN_MARGINAL && !(lam[i] >= 0.0 && std::isfinite(lam[i]))) return fail(c, MEDGP_ERR_ARG, "lam[%zu] = %g: a precision is finite and >= 0", i, lam[i]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
+    const BatchPlan &P = c->plan;
+    if (P.nwaves > 1 || !mean_fits(P.need_mat, P.need_vec, c->rules.mem_budget))
+        return fail(c, MEDGP_ERR_CAPACITY, "the call's per-entry matrices (%d of %zu MB) and panels exceed the memory budget of %zu MB (MEDGP_MEM_BUDGET_GB): split the call",
+                    MEAN_MATS, (P.need_mat * sizeof(double)) >> 20, c->rules.mem_budget >> 20);
+    mc.mb = mean_buffers(P.need_vec, nbatch, D);
+    if ((rc = buf_ensure(c, BUF_MN_G, mc.mb.panel_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_MN_PH, mc.mb.panel_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_MN_PM, mc.mb.panel_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_MN_VEC, mc.mb.vec_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_MN_SMALL, mc.mb.small_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_MN_IN, mc.mb.in_doubles * sizeof(double)))) return rc;
+    mc.G = buf<double>(c, BUF_MN_G); mc.PH = buf<double>(c, BUF_MN_PH); mc.Pm = buf<double>(c, BUF_MN_PM);
+    mc.vec = buf<double>(c, BUF_MN_VEC); mc.small = buf<double>(c, BUF_MN_SMALL); mc.in = buf<double>(c, BUF_MN_IN);
+    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
+    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    HIPCHK(c, hipMemcpyAsync(mc.in, b0, sizeof(double) * nbatch * D, hipMemcpyHostToDevice, c->stream));
+    if (mode == MEDGP_MEAN_MARGINAL)
+        HIPCHK(c, hipMemcpyAsync(mc.in + mean_lam_offset(nbatch, D), lam, sizeof(double) * nbatch * D, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
+    // the generic kernels (MEDGP_V0) keep W where P goes: these calls always take the templated ones
+    const bool v0 = c->rules.use_v0;
+    c->rules.use_v0 = false;
+    rc = run_pipeline(c, c->d_theta, 0, true, min_n, nullptr, nullptr, nullptr, false, true);
+    c->rules.use_v0 = v0;
+    if (rc) return rc;
+    for (const SizeClass &k : P.cls) {
+        const MedgpDev V = class_view(c, P, k);
+        double *Gk = mc.G + MEAN_PW * k.off_vec;
+        { Launcher l(c, KID_MN_G); hipLaunchKernelGGL(k_mean_g, dim3(mean_g_grid(k.nbmax), k.count), dim3(256), 0, c->stream, V, Gk); }
+        Launcher l(c, KID_MN_SMALL);
+        hipLaunchKernelGGL(k_mean_small, dim3(k.count), dim3(256), 0, c->stream, V, Gk, mc.in, nbatch, mode, mc.vec + k.off_vec,
+                           mc.small + (size_t)k.b0 * mean_small_stride(D));
+    }
+    return MEDGP_OK;
+}
+
+// beta, dmean and beta_cov of the call from the downloaded per-entry blocks (internal order) to the caller's rows; NaN for failed entries
+void mean_scatter(const BatchPlan &P, const std::vector<double> &hs, const int32_t *st, int nbatch, int D, double *dmean, double *beta, double *beta_cov) {
+    const size_t ms = mean_small_stride(D);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int i = 0; i < nbatch; i++) {
+        const int b = P.order[i];
+        const double *s = hs.data() + (size_t)i * ms;
+        const bool ok = st[b] >= 0;
+        for (int d = 0; d < D; d++) {
+            if (beta) beta[(size_t)b * D + d] = ok ? s[mean_off_beta(D) + d] : nan;
+            if (dmean) dmean[(size_t)b * D + d] = ok ? s[mean_off_dmean(D) + d] : nan;
+        }
+        if (beta_cov)
+            for (int x = 0; x < D * D; x++) beta_cov[(size_t)b * D * D + x] = ok ? s[mean_off_cov(D) + x] : nan;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// The nlml with a constant baseline per covariate, fixed or integrated out, and its gradients (kernels_mean.h).  mean_prepare, then per
+// size class in stream order, for a gradient: k_mean_panel (PH = U G on fp64 MFMA, Pm, alpha~), k_mean_wgrad (W~ tiles -> slab, wdiag) on
+// a view whose alpha is alpha~, the nlml gradient's own k_slabsum; then k_epilogue told to report the objective k_mean_small left in
+// scal[2], which adds the priors on theta.  flag_grad = 0 runs mean_prepare and k_epilogue only.  L, U, z and alpha are never overwritten.
+int medgp_mean_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0, const double *lam,
+                         int flag_grad, double *nlml, double *grad, double *dmean, double *beta, double *beta_cov, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
+    MeanCall mc{};
+    int rc;
+    if ((rc = mean_prepare(c, "medgp_mean_nlml_grad", nbatch, slots, theta, mode, b0, lam, 3, mc))) return rc;
+    const BatchPlan &P = c->plan;
+    const int D = c->rules.D;
+    const size_t H = c->H;
+    for (const SizeClass &k : P.cls) {
+        MedgpDev V = class_view(c, P, k);
+        const int nb = k.count, nt64 = k.nbmax;
+        if (flag_grad) {
+            double *Gk = mc.G + MEAN_PW * k.off_vec, *PHk = mc.PH + MEAN_PW * k.off_vec, *Pmk = mc.Pm + MEAN_PW * k.off_vec;
+            double *at = mc.vec + mean_alpha_offset(P.need_vec) + k.off_vec;
+            {
+                Launcher l(c, KID_MN_PANEL);
+                hipLaunchKernelGGL(k_mean_panel, dim3(mean_panel_grid(nt64), nb), dim3(256), 0, c->stream, V, Gk, mc.small + (size_t)k.b0 * mean_small_stride(D), mode, PHk, Pmk, at);
+            }
+            V.alpha = at;   // the gradient pass and what follows see alpha~
+            const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
+            const int k1 = mode == MEDGP_MEAN_MARGINAL ? mean_wgrad_k1(D, WG_KC) : 0;
+            {
+                Launcher l(c, KID_MN_WGRAD);   // (Q <= 16 was checked)
+                with_q16(V.Q, [&](auto q, auto q0) {
+                    hipLaunchKernelGGL((k_mean_wgrad<decltype(q)::value, decltype(q0)::value>), dim3(wg.grid), dim3(WG_THREADS), 0, c->stream, V, Pmk, k1, nb, wg.wg_tiles, wg.nbp);
+                });
+            }
+            const int nbins3 = 3 * V.Q * tri(V.D);
+            Launcher l(c, KID_EPILOGUE);
+            hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V);
+        }
+        Launcher l(c, KID_EPILOGUE);
+        const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
+        hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, c->d_theta, flag_grad, 1, c->d_nlml, c->d_grad, c->d_status_out, 1);
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> hs(mc.mb.small_doubles);
+    std::vector<int32_t> st(nbatch);
+    if (nlml) HIPCHK(c, hipMemcpyAsync(nlml, c->d_nlml, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    if (flag_grad && grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * H, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hs.data(), mc.small, mc.mb.small_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_retired(c);
+    mean_scatter(P, hs, st.data(), nbatch, D, dmean, beta, beta_cov);
+    if (status) std::memcpy(status, st.data(), sizeof(int32_t) * nbatch);
+    return MEDGP_OK;
+}
+
+// The posterior at test points under the same model (kernels_mean.h).  mean_prepare (no n > 2 guard, as medgp_posterior_batch), then per
+// launch chunk of tiles of 64 points, in stream order: the unchanged k_pjvp_solve (V = L^-1 K* behind the first panel of every tile's
+// work rows) and k_mean_post (G^T V on fp64 MFMA, mean, var in fp64).  The points keep the caller's order.
+int medgp_mean_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0,
+                               const double *lam, const int64_t *offsets, const int32_t *meta2, const float *t2, double *mean, double *var,
+                               double *beta, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!offsets) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    if (nbatch < 1) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d", nbatch);
+    int rc;
+    if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
+    for (int b = 0; b < nbatch; b++)
+        if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
+    const int64_t M = offsets[nbatch];
+    if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
+    if (M > 0 && !t2) return fail(c, MEDGP_ERR_ARG, "t2 is NULL");
+    if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
+    if ((mean == nullptr) != (var == nullptr)) return fail(c, MEDGP_ERR_ARG, "mean and var: both or neither");
+    std::vector<double> ht2;
+    std::vector<int> hm2;
+    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
+    MeanCall mc{};
+    if ((rc = mean_prepare(c, "medgp_mean_posterior_batch", nbatch, slots, theta, mode, b0, lam, 1, mc))) return rc;
+    const BatchPlan &P = c->plan;
+    const int D = c->rules.D;
+    PointTables<PostTile> T;
+    build_pjvp_tiles(table_classes(P), P.order.data(), offsets, c->posterior_budget, T);
+    const size_t Mz = (size_t)std::max<int64_t>(M, 1);
+    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
+    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
+    if ((rc = buf_ensure(c, BUF_MN_OUT, 2 * Mz * sizeof(double)))) return rc;
+    double *d_mean = buf<double>(c, BUF_MN_OUT), *d_var = d_mean + Mz;
+    for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
+        const SizeClass &k = P.cls[ch.cls];
+        const MedgpDev V = class_view(c, P, k);
+        const PostTile *tiles = buf<PostTile>(c, BUF_TILES) + ch.t0;
+        {
+            Launcher l(c, KID_PJ_SOLVE);   // (nvec = 0: no derivative output is touched)
+            hipLaunchKernelGGL(k_pjvp_solve, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK),
+                               ch.stride, 0, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), (double *)nullptr, (double *)nullptr);
+        }
+        Launcher l(c, KID_MN_POST);
+        hipLaunchKernelGGL(k_mean_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_WORK), ch.stride,
+                           mc.G + MEAN_PW * k.off_vec, mc.small + (size_t)k.b0 * mean_small_stride(D), mode, d_mean, d_var);
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> hs(mc.mb.small_doubles);
+    std::vector<int32_t> st(nbatch);
+    if (M > 0 && mean) {
+        HIPCHK(c, hipMemcpyAsync(mean, d_mean, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(var, d_var, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(hs.data(), mc.small, mc.mb.small_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = read_status(c, nbatch, st.data()))) return rc;
+    free_retired(c);
+    mean_scatter(P, hs, st.data(), nbatch, D, nullptr, beta, nullptr);
+    if (status) std::memcpy(status, st.data(), sizeof(int32_t) * nbatch);
     return MEDGP_OK;
 }
 
