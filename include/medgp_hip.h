@@ -600,6 +600,60 @@ int medgp_mean_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots,
                                const double *lam, const int64_t *offsets, const int32_t *meta2, const float *t2,
                                double *mean, double *var /* fp64, [M] */, double *beta /* [nbatch][D] */, int32_t *status);
 
+/* FIXED EFFECTS with a general basis (ABI 21): the baseline calls' model y = H beta + f + noise with ANY H (n x p) in place of the
+ * indicator H[i, d] = [m_i = d] -- a linear drift per covariate, a step or ramp that is 1 while a drug runs (its coefficient, with its
+ * posterior standard deviation, says whether and by how much the intervention moved the covariate), a time-of-day harmonic shared by
+ * several covariates, a dose-proportional column (medgp_amd.basis builds them for observations and test points alike).
+ *
+ * medgp_set_basis -- a resident basis per slot: hmat holds rows [offsets[k], offsets[k+1]) x p (row-major, fp64) for slots[k], in the
+ * CALLER's observation order of the patient currently uploaded there (rows must equal its n).  hmat == NULL removes the basis of the
+ * listed slots (p and offsets are then ignored).  The basis is uploaded once, like medgp_set_patients and medgp_set_priors: H does not
+ * change between the evaluations of a training loop.  The library brings the rows into its grouped order, packs all listed slots into
+ * one pinned buffer and sends them in ONE host-to-device transfer; nothing waits for the device.  All device memory of the bases is
+ * obtained here, never inside an evaluation call: a call that repeats an earlier one (same slots, same order, same sizes) overwrites
+ * its rows in place, any other is placed behind what is in use, and when that does not fit the live bases are compacted into a
+ * larger block.  A later medgp_set_patient[s] on a slot DROPS that slot's basis (the rows no longer belong to the data); an evaluation
+ * on a slot without a basis returns MEDGP_ERR_ARG before any device work, as does a call whose slots do not all carry the same p.
+ * 1 <= p <= 64: p < 1 is MEDGP_ERR_ARG, p > 64 MEDGP_ERR_CAPACITY (one 64-column panel, A in LDS, as D <= 64 of the baseline calls).
+ * MEDGP_ERR_ARG: a non-finite entry, a row count different from the slot's n, a slot without a patient, a slot listed twice. */
+int medgp_set_basis(medgp_ctx *ctx, int nslots, const int32_t *slots, int p, const int64_t *offsets, const double *hmat);
+/* medgp_mean_nlml_grad with H from the resident basis and p in place of D; mode takes MEDGP_MEAN_MARGINAL / MEDGP_MEAN_FIXED.  b0 and
+ * lam are [nbatch][p].  With K the matrix the pipeline factored, P = K^-1, G = L^-1 H, Lambda = diag(lam), r0 = y - H b0, w = L^-1 r0
+ * (the definition is tests/basis_truth.py, in long double):
+ *   A = Lambda + G^T G,  c = G^T w,  delta = A^-1 c,  beta^ = b0 + delta,  alpha~ = P (y - H beta^),  W~ = P - P H A^-1 H^T P - alpha~ alpha~^T
+ *   nlml[b]  = 1/2 quad + 1/2 log|K| + 1/2 log|A| - 1/2 sum_{lam_c > 0} log lam_c + 1/2 (n - #{lam_c = 0}) log 2 pi, minus the log prior
+ *              of theta as medgp_nlml_grad; quad = r0^T P r0 - c^T A^-1 c evaluated as |w - G delta|^2 + sum_c lam_c delta_c^2
+ *   grad[b]  = 1/2 tr(W~ dK/dtheta_h), the prior lines as medgp_nlml_grad; the noise lines from diag(W~), not scaled by jitter rounds
+ *   dbeta[b] = d nlml / d b0 = -lam o delta (MARGINAL), -G^T w = -H^T alpha~ (FIXED)
+ *   beta[b] = beta^,  beta_cov[b] = A^-1 ([p][p], symmetric; FIXED: beta = b0, beta_cov = 0)
+ * There is no segment table to consult for an improper entry: under lam_c = 0 a basis whose flat-prior columns are linearly dependent
+ * on the patient's rows makes A singular, and the failed pivot of its factorisation gives status -1 on the device; batch-mates are
+ * unaffected.  A pivot fails when it is NaN or not above 4 p 2^-52 times the column's own diagonal entry of A: rounding leaves noise
+ * of either sign where an exactly dependent column's pivot would be 0, so "pivot <= 0" alone would pass half of such entries.  A zero column with lam_c > 0 is legal: beta^_c = b0_c, and the variance at a point gains h*_c^2 / lam_c.  A NEARLY
+ * dependent basis is the caller's to avoid (centre and scale the time of a trend; no column that others almost reproduce):
+ * medgp_amd.basis.conditioning measures it.
+ * status, the NaN rows of failed entries, flag_grad, "every output pointer may be NULL", the argument errors (mode, lam, b0, Q > 16),
+ * the capacity rule of the per-entry matrices and panels (no memory waves), MEDGP_V0 not honoured, and the determinism promise -- no
+ * atomics; with the route pinned an entry's bits depend on the patient, its basis, theta, b0, lam and mode alone, not on batch-mates,
+ * position, batch size or launch chunk -- as medgp_mean_nlml_grad.
+ * Accuracy: tests/test_basis_gpu.py holds every output to the fp64 budget M_BASIS max(E_programs, 2^-53) of tests/basis_truth.py.
+ * All pointers are HOST memory. */
+int medgp_basis_nlml_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int mode,
+                          const double *b0 /* [nbatch][p] */, const double *lam /* [nbatch][p]; NULL in FIXED mode */, int flag_grad,
+                          double *nlml, double *grad /* [nbatch][H] */, double *dbeta /* [nbatch][p] = d nlml / d b0 */,
+                          double *beta /* [nbatch][p] */, double *beta_cov /* [nbatch][p][p] */, int32_t *status);
+/* medgp_mean_posterior_batch under the same model: h2 holds the basis row h*_j of every test point ([M][p], the caller's point
+ * order; required when M > 0, a non-finite entry is MEDGP_ERR_ARG).  With V_j = L^-1 k*_j and r_j = h*_j - G^T V_j:
+ *   mean[j] = V_j^T z + r_j^T beta^
+ *   var[j]  = (k** - V_j^T V_j + sigma^2_{m*_j}) + r_j^T A^-1 r_j          (FIXED: the last term is absent)
+ * Everything else -- offsets / meta2 / t2, the fp64 outputs, a patient without points, NaN for the points of a failed entry, mean and
+ * var both or neither, the chunking, the supported range of the time stamps, a point's bits independent of the other points and
+ * their order -- as medgp_mean_posterior_batch.  All pointers are HOST memory. */
+int medgp_basis_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0,
+                                const double *lam, const int64_t *offsets, const int32_t *meta2, const float *t2,
+                                const double *h2 /* [M][p]: the basis rows of the test points */,
+                                double *mean, double *var /* fp64, [M] */, double *beta /* [nbatch][p] */, int32_t *status);
+
 /* Rolling-origin forecasts: every test point predicted from a LEADING block of its patient's observations, all from ONE
  * factorisation per patient -- what the model says at time t from what was known before t.
  *   ref: core/gp_regression.cpp:128-214 (GP_Regression::predict), main_one_test.cpp:269-300 (the "past" training sets of the

@@ -24,7 +24,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_posterior_jvp_batch", "medgp_posterior_vjp_batch", "medgp_posterior_vjp_moments", "medgp_mean_nlml_grad", "medgp_mean_posterior_batch", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_posterior_jvp_batch", "medgp_posterior_vjp_batch", "medgp_posterior_vjp_moments", "medgp_mean_nlml_grad", "medgp_mean_posterior_batch", "medgp_set_basis", "medgp_basis_nlml_grad", "medgp_basis_posterior_batch", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at", "medgp_gmm_fit",
 ]
 
@@ -108,6 +108,12 @@ def load():
     lib.medgp_mean_nlml_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, C.c_int, dp, dp, dp, dp, dp, i32p]
     lib.medgp_mean_posterior_batch.restype = C.c_int
     lib.medgp_mean_posterior_batch.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, C.POINTER(C.c_int64), i32p, fp, dp, dp, dp, i32p]
+    lib.medgp_set_basis.restype = C.c_int
+    lib.medgp_set_basis.argtypes = [vp, C.c_int, i32p, C.c_int, C.POINTER(C.c_int64), dp]
+    lib.medgp_basis_nlml_grad.restype = C.c_int
+    lib.medgp_basis_nlml_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, C.c_int, dp, dp, dp, dp, dp, i32p]
+    lib.medgp_basis_posterior_batch.restype = C.c_int
+    lib.medgp_basis_posterior_batch.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, C.POINTER(C.c_int64), i32p, fp, dp, dp, dp, dp, i32p]
     lib.medgp_posterior_vjp_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, dp, C.c_int, dp, dp, fp, fp, dp, dp, i32p]
     lib.medgp_forecast_grad.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, C.c_int, dp, dp, i32p]
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
@@ -978,9 +984,9 @@ class Context:
             out.append(mv + ((grad[b].copy(),) if loss is None else (grad[b, 0].copy(), float(lossv[b]))))
         return out, st
 
-    def _mean_args(self, nb, b0, lam, fixed):
-        """(mode, b0 [nb, D], lam [nb, D] or None) of the baseline calls; a vector [D] serves every patient"""
-        D = self.D if self.kernel_index == KERNEL_LMC_SM else 1
+    def _mean_args(self, nb, b0, lam, fixed, ncol=None):
+        """(mode, b0 [nb, D], lam [nb, D] or None) of the baseline calls; a vector [D] serves every patient (ncol: the basis calls' p)"""
+        D = ncol if ncol is not None else (self.D if self.kernel_index == KERNEL_LMC_SM else 1)
 
         def rows(a, what):
             a = np.asarray(a, dtype=np.float64)
@@ -1034,6 +1040,83 @@ class Context:
                                                        _ptr(lam, C.c_double), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32),
                                                        _ptr(t2, C.c_float), _ptr(mean, C.c_double), _ptr(var, C.c_double), _ptr(beta, C.c_double),
                                                        _ptr(st, C.c_int32)))
+        out = [(mean[int(offsets[b]):int(offsets[b + 1])].copy(), var[int(offsets[b]):int(offsets[b + 1])].copy()) for b in range(nb)]
+        return out, beta, st
+
+    def set_basis(self, slots, H_list):
+        """medgp_set_basis: a resident basis per slot.  H_list: one [n, p] array per slot, rows in the order the patient was uploaded
+        (medgp_amd.basis.Design.design builds it), the same p for all; one packed transfer, no device wait.  H_list=None removes the
+        bases of the slots.  A later set_patient[s] on a slot drops its basis."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        if H_list is None:
+            self._chk(self._lib.medgp_set_basis(self._h, slots.shape[0], _ptr(slots, C.c_int32), 0, None, None))
+            return
+        if len(H_list) != slots.shape[0]:
+            raise ValueError(f"{len(H_list)} bases for {slots.shape[0]} slots")
+        Hs = [np.asarray(h, dtype=np.float64) for h in H_list]
+        Hs = [h.reshape(-1, 1) if h.ndim == 1 else h for h in Hs]
+        p = Hs[0].shape[1]
+        if any(h.ndim != 2 or h.shape[1] != p for h in Hs):
+            raise ValueError("every basis of one set_basis call has the same number of columns")
+        offsets = np.zeros(len(Hs) + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([h.shape[0] for h in Hs])
+        hm = np.ascontiguousarray(np.concatenate(Hs, axis=0) if offsets[-1] else np.zeros((1, max(p, 1))))
+        self._chk(self._lib.medgp_set_basis(self._h, slots.shape[0], _ptr(slots, C.c_int32), int(p), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            _ptr(hm, C.c_double)))
+
+    @staticmethod
+    def _basis_cols(b0, lam, nb):
+        """p of a basis call from its b0 ([p] or [nbatch, p]; lam decides where b0.size == nbatch * p is ambiguous)"""
+        a = np.asarray(b0, dtype=np.float64)
+        if a.ndim == 2:
+            return a.shape[1]
+        la = None if lam is None else np.asarray(lam, dtype=np.float64)
+        return la.shape[1] if la is not None and la.ndim == 2 else a.size
+
+    def basis_nlml_grad(self, slots, theta, b0, lam=None, fixed=False, flag_grad=True):
+        """medgp_basis_nlml_grad: mean_nlml_grad with H from the slots' resident bases (set_basis) -- fixed=True: beta = b0; else
+        beta_c ~ N(b0_c, 1 / lam_c) is integrated out (lam_c = 0: flat).  b0, lam: [p] for every patient or [nbatch, p].  Returns
+        dict(nlml [nbatch], grad [nbatch, H] or None, dbeta [nbatch, p] = d nlml / d b0, beta [nbatch, p], beta_cov [nbatch, p, p],
+        status [nbatch]); a failed patient's rows (a singular A among them) are NaN."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        nb = slots.shape[0]
+        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
+        mode, b0, lam = self._mean_args(nb, b0, lam, fixed, self._basis_cols(b0, lam, nb))
+        p = b0.shape[1]
+        nlml, grad = np.empty(nb), (np.empty((nb, self.H)) if flag_grad else None)
+        dbeta, beta, cov = np.empty((nb, p)), np.empty((nb, p)), np.empty((nb, p, p))
+        st = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_basis_nlml_grad(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), mode, _ptr(b0, C.c_double),
+                                                  _ptr(lam, C.c_double), int(bool(flag_grad)), _ptr(nlml, C.c_double), _ptr(grad, C.c_double),
+                                                  _ptr(dbeta, C.c_double), _ptr(beta, C.c_double), _ptr(cov, C.c_double), _ptr(st, C.c_int32)))
+        return dict(nlml=nlml, grad=grad, dbeta=dbeta, beta=beta, beta_cov=cov, status=st)
+
+    def basis_posterior(self, slots, theta, meta2_list, t2_list, h2_list, b0, lam=None, fixed=False):
+        """medgp_basis_posterior_batch: the posterior at test points under the model of basis_nlml_grad, float64.  slots, theta,
+        meta2_list, t2_list as posterior(); h2_list: one [m, p] array of basis rows per patient (the recipe of the observations'
+        basis at the test points: medgp_amd.basis.Design.design(meta2, t2)).  Returns ([(mean[m], var[m]) per patient],
+        beta [nbatch, p], status)."""
+        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
+        nb = slots.shape[0]
+        mode, b0, lam = self._mean_args(nb, b0, lam, fixed, self._basis_cols(b0, lam, nb))
+        p = b0.shape[1]
+        if len(h2_list) != nb:
+            raise ValueError(f"{len(h2_list)} basis arrays for {nb} patients")
+        hs = [np.asarray(h, dtype=np.float64).reshape(x.shape[0], p) for h, x in zip(h2_list, ts)]
+        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum(cnt)
+        M = int(offsets[-1])
+        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
+        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+        h2 = np.ascontiguousarray(np.concatenate(hs, axis=0) if M else np.zeros((1, p)))
+        mean, var = np.empty(max(M, 1)), np.empty(max(M, 1))
+        beta = np.empty(b0.shape)
+        st = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_basis_posterior_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), mode, _ptr(b0, C.c_double),
+                                                        _ptr(lam, C.c_double), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32),
+                                                        _ptr(t2, C.c_float), _ptr(h2, C.c_double), _ptr(mean, C.c_double), _ptr(var, C.c_double),
+                                                        _ptr(beta, C.c_double), _ptr(st, C.c_int32)))
         out = [(mean[int(offsets[b]):int(offsets[b + 1])].copy(), var[int(offsets[b]):int(offsets[b + 1])].copy()) for b in range(nb)]
         return out, beta, st
 

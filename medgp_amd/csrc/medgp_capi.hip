@@ -29,6 +29,7 @@
 #include "kernels_posterior_jvp.h"
 #include "kernels_posterior_vjp.h"
 #include "kernels_mean.h"
+#include "kernels_basis.h"
 
 #include <algorithm>
 #include <chrono>
@@ -44,8 +45,8 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_PJ_SOLVE, KID_PJ_U, KID_PJ_DIR, KID_PV_COT, KID_PV_WGRAD, KID_PV_CROSS, KID_PV_FINISH, KID_MN_G, KID_MN_SMALL, KID_MN_PANEL, KID_MN_WGRAD, KID_MN_POST, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue", "k_pjvp_solve", "k_pjvp_u", "k_pjvp_dir", "k_pvjp_cot", "k_pvjp_wgrad", "k_pvjp_cross", "k_pvjp_finish", "k_mean_g", "k_mean_small", "k_mean_panel", "k_mean_wgrad", "k_mean_post"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_PJ_SOLVE, KID_PJ_U, KID_PJ_DIR, KID_PV_COT, KID_PV_WGRAD, KID_PV_CROSS, KID_PV_FINISH, KID_MN_G, KID_MN_SMALL, KID_MN_PANEL, KID_MN_WGRAD, KID_MN_POST, KID_BS_G, KID_BS_SMALL, KID_BS_POST, KID_COUNT };
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue", "k_pjvp_solve", "k_pjvp_u", "k_pjvp_dir", "k_pvjp_cot", "k_pvjp_wgrad", "k_pvjp_cross", "k_pvjp_finish", "k_mean_g", "k_mean_small", "k_mean_panel", "k_mean_wgrad", "k_mean_post", "k_basis_g", "k_basis_small", "k_basis_post"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -111,9 +112,11 @@ struct Arena {
 //   medgp_mean_nlml_grad / medgp_mean_posterior_batch (mean_tables.h): BUF_MN_G, BUF_MN_PH, BUF_MN_PM the panels G = L^-1 H, K^-1 H and
 //   Pm (laid out like alpha, 64 doubles per row), BUF_MN_VEC [w | alpha~], BUF_MN_SMALL the per-entry blocks (beta^, dmean, delta,
 //   chol(A)^-1, A^-1), BUF_MN_IN [b0 | lam] in the caller's order, BUF_MN_OUT the fp64 [mean | var] of the posterior call's points
+//   medgp_basis_nlml_grad / medgp_basis_posterior_batch (basis_tables.h): the seven buffers above in the same roles with p columns;
+//   BUF_BS_OFF the offset of every entry's rows in the resident store (caller's order), BUF_BS_H2 the basis rows of the call's points
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_PJ_U, BUF_PJ_OUT, BUF_PV_ENT, BUF_PV_SEG, BUF_PV_ORD, BUF_PV_IN, BUF_PV_PTS, BUF_PV_VEC, BUF_PV_SMALL, BUF_PV_OUT, BUF_MN_G, BUF_MN_PH, BUF_MN_PM, BUF_MN_VEC, BUF_MN_SMALL, BUF_MN_IN, BUF_MN_OUT, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_PJ_U, BUF_PJ_OUT, BUF_PV_ENT, BUF_PV_SEG, BUF_PV_ORD, BUF_PV_IN, BUF_PV_PTS, BUF_PV_VEC, BUF_PV_SMALL, BUF_PV_OUT, BUF_MN_G, BUF_MN_PH, BUF_MN_PM, BUF_MN_VEC, BUF_MN_SMALL, BUF_MN_IN, BUF_MN_OUT, BUF_BS_OFF, BUF_BS_H2, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -193,6 +196,14 @@ struct medgp_ctx {
     size_t bounce_cap = 0;
     int *d_one_slot = nullptr;       // single-entry slot table for the caller-order re-factorisation of medgp_get_factor
     DevBuf buf[BUF_COUNT];          // the inference entry points' buffers (enum BufId)
+    // the resident bases of medgp_set_basis (basis_tables.h): ONE device block, the host's map of it, and the pinned buffer the packed
+    // rows of a call travel through (guarded by ev_basis)
+    BasisStore basis;
+    double *d_basis = nullptr;
+    char *h_basis_stage = nullptr;
+    size_t basis_stage_cap = 0;
+    hipEvent_t ev_basis = nullptr;
+    bool basis_pending = false;
     std::vector<int64_t> pv_src;    // medgp_posterior_vjp_batch: device point -> caller point of the last call (medgp_posterior_vjp_moments)
     bool pv_valid = false;          // ... and whether BUF_PV_PTS still holds that call's fp64 mean / var
     size_t posterior_budget = (size_t)2 << 30;   // MEDGP_POSTERIOR_BUDGET_GB
@@ -884,7 +895,7 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
 
 extern "C" {
 
-int medgp_abi_version(void) { return 20; }
+int medgp_abi_version(void) { return 21; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -961,6 +972,8 @@ void medgp_destroy(medgp_ctx *c) {
     for (int i = 0; i < 2; i++) { if (c->ev_up[i]) (void)hipEventDestroy(c->ev_up[i]); if (c->ev_k[i]) (void)hipEventDestroy(c->ev_k[i]); }
     if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
+    if (c->ev_basis) (void)hipEventDestroy(c->ev_basis);
+    if (c->h_basis_stage) (void)hipHostFree(c->h_basis_stage);
     if (c->h_bounce) (void)hipHostFree(c->h_bounce);
     if (c->h_small) (void)hipHostFree(c->h_small);
     if (c->d_small) (void)hipFree(c->d_small);
@@ -1088,6 +1101,10 @@ int medgp_reserve(medgp_ctx *c, int max_slots, int max_n, int max_batch) {
     c->h_n.assign(max_slots, -1);
     c->h_perm.assign(max_slots, {});
     c->h_perm_identity.assign(max_slots, 1);
+    c->basis = BasisStore{};
+    c->basis.slot.assign(max_slots, BasisSlot{});
+    c->d_basis = nullptr;   // freed by free_all above
+    c->basis_pending = false;
     c->h_bslot.assign(max_batch, -1);
     c->last_nbatch = 0;
     c->plan = BatchPlan{};
@@ -1246,6 +1263,7 @@ int upload_patients(medgp_ctx *c, const std::vector<UpEntry> &ents) {
         c->h_n[s] = ents[k].n;
         c->h_perm[s] = std::move(perms[k]);
         c->h_perm_identity[s] = ident[k];
+        c->basis.drop(s);   // its rows no longer belong to the data
     }
     c->last_nbatch = 0;   // cached batch selection / factors no longer describe the resident patients
     c->last_has_inverse = false;
@@ -3059,20 +3077,33 @@ namespace {
 // the device, ONE pipeline run in the grouped order (factor, U = L^-T, z, alpha; min_n as the caller's family has it) and, per size
 // class in stream order, k_mean_g (G = L^-1 H) and k_mean_small (A, its factor, beta^, A^-1, dmean, the objective -> scal[2]; status -1
 // for an improper entry or a failed pivot of A).
+// The two basis calls (kernels_basis.h) share all of it with H from the resident store: basis = true takes the column count p from the
+// slots' bases (all the same, else MEDGP_ERR_ARG, as for a slot without a basis: before any device work), sends every entry's offset
+// into the store beside [b0 | lam], and launches k_basis_g / k_basis_small in the two kernels' places.  mc.ncol: D or p.
 struct MeanCall {
     MeanBuffers mb;
     double *G, *PH, *Pm, *vec, *small, *in;
+    int ncol;
 };
 int mean_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0,
-                 const double *lam, int min_n, MeanCall &mc) {
+                 const double *lam, int min_n, bool basis, MeanCall &mc) {
     if (!slots || !theta || !b0) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if (mode != MEDGP_MEAN_MARGINAL && mode != MEDGP_MEAN_FIXED) return fail(c, MEDGP_ERR_ARG, "unknown mode %d", mode);
     if (mode == MEDGP_MEAN_MARGINAL && !lam) return fail(c, MEDGP_ERR_ARG, "lam is NULL with MEDGP_MEAN_MARGINAL");
     if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "%s supports Q <= 16 (Q = %d)", who, c->rules.Q);
-    const int D = c->rules.D;
-    if (D > MEAN_MAX_D) return fail(c, MEDGP_ERR_CAPACITY, "%s supports D <= %d covariates (D = %d): the rank-D correction is one 64-column panel", who, MEAN_MAX_D, D);
+    if (!basis && c->rules.D > MEAN_MAX_D) return fail(c, MEDGP_ERR_CAPACITY, "%s supports D <= %d covariates (D = %d): the rank-D correction is one 64-column panel", who, MEAN_MAX_D, c->rules.D);
     int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
+    int D = c->rules.D;   // the column count of H
+    if (basis) {
+        for (int b = 0; b < nbatch; b++) {
+            if (!c->basis.has(slots[b])) return fail(c, MEDGP_ERR_ARG, "slots[%d] = %d has no basis (medgp_set_basis; a new patient drops it)", b, slots[b]);
+            if (c->basis.slot[slots[b]].p != c->basis.slot[slots[0]].p)
+                return fail(c, MEDGP_ERR_ARG, "slots[%d] = %d carries a basis of %d columns, slots[0] one of %d: one p per call", b, slots[b], c->basis.slot[slots[b]].p, c->basis.slot[slots[0]].p);
+        }
+        D = c->basis.slot[slots[0]].p;
+    }
+    mc.ncol = D;
     for (size_t i = 0; i < (size_t)nbatch * D; i++) {
         if (!std::isfinite(b0[i])) return fail(c, MEDGP_ERR_ARG, "b0[%zu] = %g is not finite", i, b0[i]);
         if (mode == MEDGP_MEAN_MARGINAL && !(lam[i] >= 0.0 && std::isfinite(lam[i]))) return fail(c, MEDGP_ERR_ARG, "lam[%zu] = %g: a precision is finite and >= 0", i, lam[i]);
@@ -3098,6 +3129,13 @@ int mean_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots
     if (mode == MEDGP_MEAN_MARGINAL)
         HIPCHK(c, hipMemcpyAsync(mc.in + mean_lam_offset(nbatch, D), lam, sizeof(double) * nbatch * D, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
+    if (basis) {   // (through the pinned ring: the table is the call's own)
+        if ((rc = buf_ensure(c, BUF_BS_OFF, sizeof(long long) * nbatch))) return rc;
+        void *pin = nullptr;
+        if ((rc = pin_stage(c, sizeof(long long) * nbatch, &pin))) return rc;
+        for (int b = 0; b < nbatch; b++) ((long long *)pin)[b] = c->basis.slot[slots[b]].off;
+        HIPCHK(c, hipMemcpyAsync(buf<long long>(c, BUF_BS_OFF), pin, sizeof(long long) * nbatch, hipMemcpyHostToDevice, c->stream));
+    }
     // the generic kernels (MEDGP_V0) keep W where P goes: these calls always take the templated ones
     const bool v0 = c->rules.use_v0;
     c->rules.use_v0 = false;
@@ -3107,6 +3145,23 @@ int mean_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots
     for (const SizeClass &k : P.cls) {
         const MedgpDev V = class_view(c, P, k);
         double *Gk = mc.G + MEAN_PW * k.off_vec;
+        if (basis) {
+            {
+                Launcher l(c, KID_BS_G);
+                const dim3 grid(basis_g_grid(k.nbmax), k.count);
+                const long long *hoff = buf<long long>(c, BUF_BS_OFF);
+                switch ((D + 15) / 16) {   // the column tiles of the panel that carry columns
+                case 1: hipLaunchKernelGGL(k_basis_g<1>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
+                case 2: hipLaunchKernelGGL(k_basis_g<2>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
+                case 3: hipLaunchKernelGGL(k_basis_g<3>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
+                default: hipLaunchKernelGGL(k_basis_g<4>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
+                }
+            }
+            Launcher l(c, KID_BS_SMALL);
+            hipLaunchKernelGGL(k_basis_small, dim3(k.count), dim3(256), 0, c->stream, V, Gk, mc.in, nbatch, mode, D, mc.vec + k.off_vec,
+                               mc.small + (size_t)k.b0 * mean_small_stride(D));
+            continue;
+        }
         { Launcher l(c, KID_MN_G); hipLaunchKernelGGL(k_mean_g, dim3(mean_g_grid(k.nbmax), k.count), dim3(256), 0, c->stream, V, Gk); }
         Launcher l(c, KID_MN_SMALL);
         hipLaunchKernelGGL(k_mean_small, dim3(k.count), dim3(256), 0, c->stream, V, Gk, mc.in, nbatch, mode, mc.vec + k.off_vec,
@@ -3132,23 +3187,21 @@ void mean_scatter(const BatchPlan &P, const std::vector<double> &hs, const int32
     }
 }
 
-}  // namespace
-
-extern "C" {
-
 // The nlml with a constant baseline per covariate, fixed or integrated out, and its gradients (kernels_mean.h).  mean_prepare, then per
 // size class in stream order, for a gradient: k_mean_panel (PH = U G on fp64 MFMA, Pm, alpha~), k_mean_wgrad (W~ tiles -> slab, wdiag) on
 // a view whose alpha is alpha~, the nlml gradient's own k_slabsum; then k_epilogue told to report the objective k_mean_small left in
 // scal[2], which adds the priors on theta.  flag_grad = 0 runs mean_prepare and k_epilogue only.  L, U, z and alpha are never overwritten.
-int medgp_mean_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0, const double *lam,
-                         int flag_grad, double *nlml, double *grad, double *dmean, double *beta, double *beta_cov, int32_t *status) {
+// basis: medgp_basis_nlml_grad -- the same launches on p columns (k_mean_panel reads its column count from the view's D: it is handed
+// a view whose D is p; the gradient pass and the epilogue keep the covariate count).
+int mean_grad_impl(medgp_ctx *c, const char *who, bool basis, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0,
+                   const double *lam, int flag_grad, double *nlml, double *grad, double *dmean, double *beta, double *beta_cov, int32_t *status) {
     if (!c) return MEDGP_ERR_ARG;
     if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
     MeanCall mc{};
     int rc;
-    if ((rc = mean_prepare(c, "medgp_mean_nlml_grad", nbatch, slots, theta, mode, b0, lam, 3, mc))) return rc;
+    if ((rc = mean_prepare(c, who, nbatch, slots, theta, mode, b0, lam, 3, basis, mc))) return rc;
     const BatchPlan &P = c->plan;
-    const int D = c->rules.D;
+    const int D = mc.ncol;   // the columns of H
     const size_t H = c->H;
     for (const SizeClass &k : P.cls) {
         MedgpDev V = class_view(c, P, k);
@@ -3158,7 +3211,9 @@ int medgp_mean_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const d
             double *at = mc.vec + mean_alpha_offset(P.need_vec) + k.off_vec;
             {
                 Launcher l(c, KID_MN_PANEL);
-                hipLaunchKernelGGL(k_mean_panel, dim3(mean_panel_grid(nt64), nb), dim3(256), 0, c->stream, V, Gk, mc.small + (size_t)k.b0 * mean_small_stride(D), mode, PHk, Pmk, at);
+                MedgpDev Vp = V;
+                Vp.D = D;
+                hipLaunchKernelGGL(k_mean_panel, dim3(mean_panel_grid(nt64), nb), dim3(256), 0, c->stream, Vp, Gk, mc.small + (size_t)k.b0 * mean_small_stride(D), mode, PHk, Pmk, at);
             }
             V.alpha = at;   // the gradient pass and what follows see alpha~
             const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
@@ -3194,9 +3249,10 @@ int medgp_mean_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const d
 // The posterior at test points under the same model (kernels_mean.h).  mean_prepare (no n > 2 guard, as medgp_posterior_batch), then per
 // launch chunk of tiles of 64 points, in stream order: the unchanged k_pjvp_solve (V = L^-1 K* behind the first panel of every tile's
 // work rows) and k_mean_post (G^T V on fp64 MFMA, mean, var in fp64).  The points keep the caller's order.
-int medgp_mean_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0,
-                               const double *lam, const int64_t *offsets, const int32_t *meta2, const float *t2, double *mean, double *var,
-                               double *beta, int32_t *status) {
+// basis: medgp_basis_posterior_batch -- k_basis_post in k_mean_post's place, with the points' basis rows h2 ([M][p], finite).
+int mean_post_impl(medgp_ctx *c, const char *who, bool basis, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0,
+                   const double *lam, const int64_t *offsets, const int32_t *meta2, const float *t2, const double *h2, double *mean, double *var,
+                   double *beta, int32_t *status) {
     if (!c) return MEDGP_ERR_ARG;
     if (!offsets) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if (nbatch < 1) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d", nbatch);
@@ -3213,9 +3269,21 @@ int medgp_mean_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, c
     std::vector<int> hm2;
     if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
     MeanCall mc{};
-    if ((rc = mean_prepare(c, "medgp_mean_posterior_batch", nbatch, slots, theta, mode, b0, lam, 1, mc))) return rc;
+    if (basis && M > 0) {   // (p from the first slot's basis; mean_prepare refuses what is wrong with the slots)
+        if (!h2) return fail(c, MEDGP_ERR_ARG, "h2 is NULL");
+        if (!slots) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+        if ((rc = check_call(c, nbatch, slots))) return rc;
+        const size_t p = c->basis.has(slots[0]) ? c->basis.slot[slots[0]].p : 0;
+        for (size_t i = 0; i < (size_t)M * p; i++)
+            if (!std::isfinite(h2[i])) return fail(c, MEDGP_ERR_ARG, "h2[%zu] = %g is not finite", i, h2[i]);
+    }
+    if ((rc = mean_prepare(c, who, nbatch, slots, theta, mode, b0, lam, 1, basis, mc))) return rc;
     const BatchPlan &P = c->plan;
-    const int D = c->rules.D;
+    const int D = mc.ncol;   // the columns of H
+    if (basis && M > 0) {
+        if ((rc = buf_ensure(c, BUF_BS_H2, sizeof(double) * M * D))) return rc;
+        HIPCHK(c, hipMemcpyAsync(buf<double>(c, BUF_BS_H2), h2, sizeof(double) * M * D, hipMemcpyHostToDevice, c->stream));
+    }
     PointTables<PostTile> T;
     build_pjvp_tiles(table_classes(P), P.order.data(), offsets, c->posterior_budget, T);
     const size_t Mz = (size_t)std::max<int64_t>(M, 1);
@@ -3233,6 +3301,12 @@ int medgp_mean_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, c
             hipLaunchKernelGGL(k_pjvp_solve, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK),
                                ch.stride, 0, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), (double *)nullptr, (double *)nullptr);
         }
+        if (basis) {
+            Launcher l(c, KID_BS_POST);
+            hipLaunchKernelGGL(k_basis_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_BS_H2), buf<double>(c, BUF_WORK),
+                               ch.stride, mc.G + MEAN_PW * k.off_vec, mc.small + (size_t)k.b0 * mean_small_stride(D), mode, D, d_mean, d_var);
+            continue;
+        }
         Launcher l(c, KID_MN_POST);
         hipLaunchKernelGGL(k_mean_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_WORK), ch.stride,
                            mc.G + MEAN_PW * k.off_vec, mc.small + (size_t)k.b0 * mean_small_stride(D), mode, d_mean, d_var);
@@ -3249,6 +3323,107 @@ int medgp_mean_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, c
     free_retired(c);
     mean_scatter(P, hs, st.data(), nbatch, D, nullptr, beta, nullptr);
     if (status) std::memcpy(status, st.data(), sizeof(int32_t) * nbatch);
+    return MEDGP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int medgp_mean_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0, const double *lam,
+                         int flag_grad, double *nlml, double *grad, double *dmean, double *beta, double *beta_cov, int32_t *status) {
+    return mean_grad_impl(c, "medgp_mean_nlml_grad", false, nbatch, slots, theta, mode, b0, lam, flag_grad, nlml, grad, dmean, beta, beta_cov, status);
+}
+
+int medgp_mean_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0,
+                               const double *lam, const int64_t *offsets, const int32_t *meta2, const float *t2, double *mean, double *var,
+                               double *beta, int32_t *status) {
+    return mean_post_impl(c, "medgp_mean_posterior_batch", false, nbatch, slots, theta, mode, b0, lam, offsets, meta2, t2, nullptr, mean, var, beta, status);
+}
+
+int medgp_basis_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0, const double *lam,
+                          int flag_grad, double *nlml, double *grad, double *dbeta, double *beta, double *beta_cov, int32_t *status) {
+    return mean_grad_impl(c, "medgp_basis_nlml_grad", true, nbatch, slots, theta, mode, b0, lam, flag_grad, nlml, grad, dbeta, beta, beta_cov, status);
+}
+
+int medgp_basis_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0,
+                                const double *lam, const int64_t *offsets, const int32_t *meta2, const float *t2, const double *h2,
+                                double *mean, double *var, double *beta, int32_t *status) {
+    return mean_post_impl(c, "medgp_basis_posterior_batch", true, nbatch, slots, theta, mode, b0, lam, offsets, meta2, t2, h2, mean, var, beta, status);
+}
+
+// The resident bases (basis_tables.h).  Everything is validated before any state changes.  The rows of all listed slots are packed in
+// the grouped order (the slot's permutation) into one pinned buffer and travel in ONE copy into one contiguous range of the store: in
+// place when the call repeats an earlier one, otherwise behind what is used; when the block is too small the live ranges are
+// compacted into a new one by device-to-device copies in stream order and the old block is retired (freed at the context's next
+// idle point), so nothing here waits for the device unless the pinned buffer of the previous call is still being read.
+int medgp_set_basis(medgp_ctx *c, int nslots, const int32_t *slots, int p, const int64_t *offsets, const double *hmat) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
+    if (nslots < 1 || !slots) return fail(c, MEDGP_ERR_ARG, "medgp_set_basis: bad argument");
+    std::vector<uint8_t> seen((size_t)c->max_slots, 0);
+    for (int k = 0; k < nslots; k++) {
+        if (slots[k] < 0 || slots[k] >= c->max_slots) return fail(c, MEDGP_ERR_CAPACITY, "slot %d outside [0, %d)", slots[k], c->max_slots);
+        if (seen[slots[k]]) return fail(c, MEDGP_ERR_ARG, "slot %d appears twice in one medgp_set_basis", slots[k]);
+        seen[slots[k]] = 1;
+    }
+    if (!hmat) {   // remove
+        for (int k = 0; k < nslots; k++) c->basis.drop(slots[k]);
+        return MEDGP_OK;
+    }
+    if (p < 1) return fail(c, MEDGP_ERR_ARG, "p = %d: a basis has at least one column", p);
+    if (p > BASIS_MAX_P) return fail(c, MEDGP_ERR_CAPACITY, "p = %d: a basis has at most %d columns (one 64-column panel)", p, BASIS_MAX_P);
+    if (!offsets) return fail(c, MEDGP_ERR_ARG, "offsets is NULL");
+    std::vector<int> rows(nslots);
+    for (int k = 0; k < nslots; k++) {
+        const int n = c->h_n[slots[k]];
+        if (n < 0) return fail(c, MEDGP_ERR_ARG, "slot %d holds no patient", slots[k]);
+        if (offsets[k + 1] - offsets[k] != n) return fail(c, MEDGP_ERR_ARG, "slot %d: %lld basis rows for a patient of n = %d", slots[k], (long long)(offsets[k + 1] - offsets[k]), n);
+        if (offsets[k] < 0) return fail(c, MEDGP_ERR_ARG, "offsets[%d] = %lld", k, (long long)offsets[k]);
+        rows[k] = n;
+        const double *h = hmat + (size_t)offsets[k] * p;
+        for (size_t i = 0; i < (size_t)n * p; i++)
+            if (!std::isfinite(h[i])) return fail(c, MEDGP_ERR_ARG, "slot %d: hmat[%zu] = %g is not finite", slots[k], i, h[i]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t total = 0;
+    for (int k = 0; k < nslots; k++) total += BasisStore::need(rows[k], p);
+    const size_t bytes = std::max<size_t>(total, 1) * sizeof(double);
+    if (c->basis_pending) { HIPCHK(c, hipEventSynchronize(c->ev_basis)); c->basis_pending = false; }
+    if (bytes > c->basis_stage_cap) {
+        AllocTimer tm(c);
+        if (c->h_basis_stage) (void)hipHostFree(c->h_basis_stage);
+        c->h_basis_stage = nullptr; c->basis_stage_cap = 0;
+        HIPCHK(c, hipHostMalloc((void **)&c->h_basis_stage, bytes + bytes / 4, hipHostMallocDefault));
+        c->basis_stage_cap = bytes + bytes / 4;
+    }
+    if (!c->ev_basis) HIPCHK(c, hipEventCreateWithFlags(&c->ev_basis, hipEventDisableTiming));
+    const BasisStore before = c->basis;
+    const BasisPlace pl = c->basis.place(nslots, slots, rows.data(), p);
+    if (pl.new_cap) {
+        double *nb = nullptr;
+        int rc = dalloc(c, &nb, pl.new_cap);
+        if (rc) { c->basis = before; return rc; }
+        for (const BasisMove &m : pl.moves)
+            HIPCHK(c, hipMemcpyAsync(nb + m.dst, c->d_basis + m.src, m.count * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (c->d_basis) {   // queued kernels may still read it
+            c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), (void *)c->d_basis), c->allocs.end());
+            c->retired.push_back(c->d_basis);
+            c->retired_bytes += before.cap * sizeof(double);
+        }
+        c->d_basis = nb;
+    }
+    double *st = (double *)c->h_basis_stage;
+    size_t at = 0;
+    for (int k = 0; k < nslots; k++) {
+        basis_pack_rows(hmat + (size_t)offsets[k] * p, c->h_perm[slots[k]].data(), rows[k], p, st + at);
+        at += BasisStore::need(rows[k], p);
+    }
+    if (total) {
+        HIPCHK(c, hipMemcpyAsync(c->d_basis + pl.base, st, total * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_basis, c->stream));
+        c->basis_pending = true;
+    }
     return MEDGP_OK;
 }
 
