@@ -97,6 +97,14 @@ inline WgradGrid wgrad_grid(const int *entry_n, int nbatch, int nt64) {
     return g;
 }
 
+// The y extent of the gradient epilogue's grid (k_epilogue, k_hess_epilogue) for a class of nbatch entries of H hypers on num_cu CUs.
+// Few entries: the hypers of an entry are spread over workgroups (H = 2954 at D = 64: 0.18 -> 0.07 ms for one entry); with a
+// workgroup per CU anyway, one part per entry is faster (each part stages S and A again: 0.09 vs 0.20 ms at 512 entries).
+// max_parts: the parts the per-entry partial sums have room for (MEDGP_EPI_PARTS).
+inline int epilogue_parts(int nbatch, int num_cu, int H, int max_parts) {
+    return (2 * nbatch >= num_cu) ? 1 : std::min(max_parts, (H + 255) / 256);
+}
+
 // the gradient slab of one entry of a view of leading dimension ld: 3 Q planes of R x C bins (kernels_wgrad.h); stride in doubles
 struct SlabGeom { int R, C; size_t stride; };
 inline SlabGeom slab_geom(int ld, int Q, int D) {

@@ -345,6 +345,19 @@ void test_wgrad_grid() {
                 CHECK(w.nbp >= nbatch && w.grid >= w.nbp * w.wg_tiles);   // every (entry, tile) pair has a workgroup
             }
 }
+
+// ---- epilogue_parts against its definition: every (entries, CUs, hypers, room) of the ranges below ------------------------------------
+void test_epilogue_parts() {
+    for (int nbatch = 1; nbatch <= 300; nbatch++)
+        for (int num_cu : {1, 2, 64, 255, 256, 304})
+            for (int H = 1; H <= 3000; H += (H < 520 ? 1 : 97))
+                for (int max_parts : {1, 2, 8, 16}) {
+                    const int ceil256 = H / 256 + (H % 256 ? 1 : 0);
+                    const int want = 2 * nbatch >= num_cu ? 1 : (ceil256 < max_parts ? ceil256 : max_parts);
+                    const int got = epilogue_parts(nbatch, num_cu, H, max_parts);
+                    CHECK(got == want && got >= 1 && got <= max_parts);
+                }
+}
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -358,6 +371,7 @@ int main(int argc, char **argv) {
     test_la_scratch();
     test_screen();
     test_wgrad_grid();
+    test_epilogue_parts();
     std::printf("call_plan ok (cohort of %d sizes)\n", (int)cohort.size());
     return 0;
 }

@@ -212,9 +212,15 @@ __device__ inline void prior_apply(const MedgpPrior &p, double hv, double pi, bo
 
 __device__ inline double sym_get(const double *S, int D, int d, int e) { return d >= e ? S[d * D + e] : S[e * D + d]; }
 
+// epi_mode of k_epilogue: what it reports beside the gradient lines
+//   EPI_NLML       the nlml of the factorisation, minus the log prior
+//   EPI_OBJECTIVE  the objective an earlier kernel of the call left in scal[2] (LOO, LGO, forecast score, baseline nlml), minus the log prior
+//   EPI_BARE       nothing: no prior stage, no scalar (Fisher / Hessian / VJP: the gradient lines alone)
+enum EpilogueMode { EPI_NLML = 0, EPI_OBJECTIVE = 1, EPI_BARE = 2 };
+
 __global__ void __launch_bounds__(256) k_epilogue(MedgpDev L, const double *__restrict__ theta, int flag_grad, int from_slab,
                                                   double *__restrict__ nlml_out, double *__restrict__ grad_out,
-                                                  int *__restrict__ status_out, int loo_objective = 0) {
+                                                  int *__restrict__ status_out, int epi_mode = 0) {
     __shared__ double red2[MEDGP_EPI_PARTS][256];   // per-chunk partial sums of the prior log-density
     // LDS copies of S_q (all q) and of A for the Q D R gradients dA_q = S_q A_q (each a D-term dot product whose
     // operands otherwise come from global memory one dependent pair at a time); used when they fit
@@ -238,7 +244,7 @@ __global__ void __launch_bounds__(256) k_epilogue(MedgpDev L, const double *__re
     double *g = grad_out ? grad_out + (size_t)pos * H : nullptr;
     if (tid == 0 && part == 0 && status_out) status_out[pos] = st;
     if (st < 0) {
-        if (tid == 0 && part == 0 && loo_objective != 2) nlml_out[pos] = __builtin_nan("");
+        if (tid == 0 && part == 0 && epi_mode != 2) nlml_out[pos] = __builtin_nan("");
         if (flag_grad && g) for (int h = h0 + tid; h < h1; h += nt) g[h] = __builtin_nan("");
         return;
     }
@@ -298,8 +304,8 @@ __global__ void __launch_bounds__(256) k_epilogue(MedgpDev L, const double *__re
     }
     // a caller-order copy of a patient (slot + max_slots, nlml-only evaluations) shares the prior of its patient
     const int pslot = slot >= L.max_slots ? slot - L.max_slots : slot;
-    // loo_objective == 2 (medgp_fisher_vec): the gradient lines alone -- no prior stage, no scalar
-    const MedgpPrior *pr = (loo_objective != 2 && L.prior_on[pslot]) ? L.prior + (size_t)pslot * H : nullptr;
+    // epi_mode == 2 (medgp_fisher_vec): the gradient lines alone -- no prior stage, no scalar
+    const MedgpPrior *pr = (epi_mode != 2 && L.prior_on[pslot]) ? L.prior + (size_t)pslot * H : nullptr;
     double lp_part = 0.0;   // thread 0: sum of this part's chunk sums, in chunk order
   for (int ch = ch0; ch < ch1; ch++) {
     double lp_local = 0.0;
@@ -425,7 +431,7 @@ __global__ void __launch_bounds__(256) k_epilogue(MedgpDev L, const double *__re
         }
         double logdet = L.scal[b * 4 + 0], quad = L.scal[b * 4 + 1];
         double nlml = quad / 2.0 + logdet + n * log(2. * L.pi) / 2.0;   // ref: c_inference_exact.cpp:149-152
-        if (loo_objective) nlml = L.scal[b * 4 + 2];   // medgp_loo_grad: k_loo_vec left the negative LOO log pseudo-likelihood there
-        if (loo_objective != 2) nlml_out[pos] = nlml - lp;
+        if (epi_mode) nlml = L.scal[b * 4 + 2];   // medgp_loo_grad: k_loo_vec left the negative LOO log pseudo-likelihood there
+        if (epi_mode != 2) nlml_out[pos] = nlml - lp;
     }
 }

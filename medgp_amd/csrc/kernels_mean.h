@@ -23,7 +23,7 @@
 //   k_mean_wgrad  k_wgrad's prologue and phase 1 on U, the accumulators continued through pv_phase1 over the one Pm panel with the
 //                 staged operand negated (MARGINAL only), then k_wgrad's phases 2 and 3 with the nlml element on a view whose alpha is
 //                 alpha~; diag(W~) leaves through wdiag.  W~ never reaches HBM.
-//   k_slabsum, k_epilogue (kernels_core.h, unchanged; loo_objective = 1: the priors are added to the objective in scal[2])
+//   k_slabsum, k_epilogue (kernels_core.h, unchanged; epi_mode = EPI_OBJECTIVE: the priors are added to the objective in scal[2])
 //   k_mean_post   behind the unchanged k_pjvp_solve (V = L^-1 K* per tile of 64 points): the D x 64 tile G^T V on fp64 MFMA,
 //                 r_j = e_{m*_j} - G^T V_j, mean_j = V_j^T z + r_j^T beta^, var_j = k** - V_j^T V_j + sigma^2 + |Ti r_j|^2 in fp64
 // No atomics; every sum in a fixed order over operands of the entry alone: an entry's bits depend neither on its batch-mates, nor on

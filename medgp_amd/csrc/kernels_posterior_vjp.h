@@ -26,7 +26,7 @@
 //   k_slabsum     (kernels_core.h, unchanged)
 //   k_pvjp_cross  one wave per lower bin (d, e): X_q[d,e] and X_q[e,d], lanes stride over the (row, point) pairs of the bin in a fixed
 //                 order, one fixed butterfly; folds them and the test diagonal into S, SM, SV behind k_slabsum
-//   k_epilogue    (kernels_core.h, unchanged; loo_objective = 2: gradient lines alone, no prior, no scalar)
+//   k_epilogue    (kernels_core.h, unchanged; epi_mode = EPI_BARE: gradient lines alone, no prior, no scalar)
 //   k_pvjp_finish adds the test diagonal's noise term  sigma_d^2 2 sum cv  to line d (a covariate with test points and no observation
 //                 has no row in wdiag) and turns the lines of an entry whose built-in loss is NaN into NaN
 // The host sorts every patient's points by covariate (stable) before the upload (pvjp_tables.h), so the points of a covariate are a

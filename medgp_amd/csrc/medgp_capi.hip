@@ -365,6 +365,34 @@ struct Launcher {
     ~Launcher() { finish(); }
 };
 
+// ---- the tail of every gradient: block sums of the slab, then the gradient lines (kernels_core.h) -- on the stream the caller runs on
+// the block sums S, SM, SV of the nb entries of the view V from the slab its tile kernel filled
+void launch_slabsum(medgp_ctx *c, hipStream_t stream, const MedgpDev &V, int nb) {
+    const int nbins3 = 3 * V.Q * tri(V.D);
+    Launcher l(c, KID_EPILOGUE, stream);
+    hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, stream, V);
+}
+// the gradient lines (flag_grad; from_slab: from the block sums) and the scalar `mode` names, into the caller's rows of nlml / grad / status
+void launch_epilogue(medgp_ctx *c, hipStream_t stream, const MedgpDev &V, int nb, const double *theta, int flag_grad, int from_slab,
+                     double *nlml, double *grad, int *status, EpilogueMode mode) {
+    const dim3 grid(nb, epilogue_parts(nb, c->rules.num_cu, V.H, MEDGP_EPI_PARTS));
+    Launcher l(c, KID_EPILOGUE, stream);
+    hipLaunchKernelGGL(k_epilogue, grid, dim3(256), 0, stream, V, theta, flag_grad, from_slab, nlml, grad, status, (int)mode);
+}
+// The tail of a size class of a call whose objective an earlier kernel left in scal[2] (LOO, LGO, forecast score, baseline nlml): for
+// a gradient the block sums, then the epilogue into the context's result staging.
+void finish_objective_class(medgp_ctx *c, const MedgpDev &V, int nb, int flag_grad) {
+    if (flag_grad) launch_slabsum(c, c->stream, V, nb);
+    launch_epilogue(c, c->stream, V, nb, c->d_theta, flag_grad, 1, c->d_nlml, c->d_grad, c->d_status_out, EPI_OBJECTIVE);
+}
+// One launch (two for 9 .. 16 components, each on its own components: kernels_wgrad.h) of a kernel that walks the tiles of
+// wgrad_grid, under label kid: f(q, q0, grid, block) names the kernel.  Every caller has refused Q > 16.
+template <class F>
+void launch_tiles(medgp_ctx *c, int kid, int Q, const WgradGrid &wg, F &&f) {
+    Launcher l(c, kid);
+    with_q16(Q, [&](auto q, auto q0) { f(q, q0, dim3(wg.grid), dim3(WG_THREADS)); });
+}
+
 int drain_events(medgp_ctx *c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (auto &e : c->events) {
@@ -721,18 +749,8 @@ int run_pipeline_one(medgp_ctx *c, hipStream_t stream, const MedgpDev &L, int nb
             { Launcher l(c, KID_GRADBINS, stream); hipLaunchKernelGGL(k_gradbins_v0, dim3((nbins + 255) / 256, nbatch), dim3(256), 0, stream, L); }
         }
     }
-    if (flag_grad && from_slab) {
-        const int nbins3 = 3 * L.Q * tri(L.D);
-        Launcher l(c, KID_EPILOGUE, stream);
-        hipLaunchKernelGGL(k_slabsum, dim3(nbatch, (nbins3 + 255) / 256), dim3(256), 0, stream, L);
-    }
-    if (nlml_dev) {
-        Launcher l(c, KID_EPILOGUE, stream);
-        // few entries: the hypers of an entry are spread over workgroups (H = 2954 at D = 64: 0.18 -> 0.07 ms for one entry); with a
-        // workgroup per CU anyway, one part per entry is faster (each part stages S and A again: 0.09 vs 0.20 ms at 512 entries)
-        const int nparts = (2 * nbatch >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (L.H + 255) / 256);
-        hipLaunchKernelGGL(k_epilogue, dim3(nbatch, nparts), dim3(256), 0, stream, L, theta_dev, flag_grad, from_slab, nlml_dev, grad_dev, (int *)status_dev);
-    }
+    if (flag_grad && from_slab) launch_slabsum(c, stream, L, nbatch);
+    if (nlml_dev) launch_epilogue(c, stream, L, nbatch, theta_dev, flag_grad, from_slab, nlml_dev, grad_dev, (int *)status_dev, EPI_NLML);
     HIPCHK(c, hipGetLastError());
     return MEDGP_OK;
 }
@@ -841,10 +859,10 @@ int stage_points(medgp_ctx *c, int64_t M, const int32_t *meta2, const float *t2,
 
 // theta to the device and the ONE pipeline run of an inference call: factor and z = L^-1 y of every entry, with U = L^-T and
 // alpha = K^-1 y (need_inverse: medgp_get_factor is valid afterwards) or the diagonal-block inverses U_kk (store_ukk).  The call reads
-// per-entry buffers of all entries afterwards: it must fit one memory wave.
-int factor_run(medgp_ctx *c, int nbatch, const double *theta, bool need_inverse, bool store_ukk) {
+// per-entry buffers of all entries afterwards: it must fit one memory wave.  min_n: entries of fewer observations get status -1 (k_prep).
+int factor_run(medgp_ctx *c, int nbatch, const double *theta, bool need_inverse, bool store_ukk, int min_n = 1) {
     HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
-    return run_pipeline(c, c->d_theta, 0, need_inverse, 1, nullptr, nullptr, nullptr, store_ukk, true);
+    return run_pipeline(c, c->d_theta, 0, need_inverse, min_n, nullptr, nullptr, nullptr, store_ukk, true);
 }
 
 // The end of a blocking call: the status words of its entries are read back behind whatever the caller has queued, the stream is
@@ -889,6 +907,94 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->buf[id].p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
     return MEDGP_OK;
+}
+
+// ---- what the derivative entry points share on top of that (the gradient objectives, Fisher / Hessian products, posterior JVP / VJP,
+// ---- the baseline and basis calls; launch_slabsum, launch_epilogue, finish_objective_class and launch_tiles stand next to Launcher) --
+// The tile kernels of these calls are instantiated for Q <= 16 only.  why: what the generic route would break in the call (null: nothing said).
+static_assert(PJVP_MAX_Q == 16, "the column tables of the JVP / VJP tile kernels are sized for what check_q16 lets through");
+int check_q16(medgp_ctx *c, const char *who, const char *why) {
+    if (c->rules.Q <= 16) return MEDGP_OK;
+    return fail(c, MEDGP_ERR_ARG, "%s supports Q <= 16 (Q = %d)%s%s", who, c->rules.Q, why ? ": " : "", why ? why : "");
+}
+const char *const kWhyKinv = "the generic gradient route keeps W in the buffer that holds K^-1 here";
+
+// The nmats matrices of every entry of the call are alive at once: the plan has one memory wave and the call's own buffers fit beside
+// it (fits: the call's rule, *_tables.h).  suffix: what else the rule counts, for the message.
+int check_one_wave(medgp_ctx *c, bool fits, int nmats, const char *suffix) {
+    if (c->plan.nwaves == 1 && fits) return MEDGP_OK;
+    return fail(c, MEDGP_ERR_CAPACITY,
+                "the call's per-entry matrices (%d of %zu MB)%s exceed the memory budget of %zu MB (MEDGP_MEM_BUDGET_GB): split the call",
+                nmats, (c->plan.need_mat * sizeof(double)) >> 20, suffix, c->rules.mem_budget >> 20);
+}
+
+// These calls leave their results in lane 0's staging (d_nlml, d_grad, d_status_out): a download of that lane still in flight on the copy
+// stream must have read it first.
+int wait_lane0_staging(medgp_ctx *c) {
+    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    return MEDGP_OK;
+}
+
+// factor_run of a derivative call: theta to the device and the one pipeline run with U = L^-T and alpha, always on the templated
+// kernels.  The generic ones (MEDGP_V0) are not honoured: their gradient route keeps W in the block of Kmat where these calls put
+// K^-1 (the forecast gradient: Qm), and the second pass of every call is instantiated for the templated route alone.
+int factor_run_templated(medgp_ctx *c, int nbatch, const double *theta, int min_n = 1) {
+    const bool v0 = c->rules.use_v0;
+    c->rules.use_v0 = false;
+    const int rc = factor_run(c, nbatch, theta, true, false, min_n);
+    c->rules.use_v0 = v0;
+    return rc;
+}
+
+// P = K^-1 = U U^T of the entries of class k into the dead Kmat block (kernels_loo_grad.h)
+void launch_kinv(medgp_ctx *c, const BatchPlan &P, const SizeClass &k, const MedgpDev &V) {
+    const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, k.count, k.nbmax);
+    Launcher l(c, KID_LOO_KINV);
+    hipLaunchKernelGGL(k_loo_kinv, dim3(wg.grid), dim3(WG_THREADS), 0, c->stream, V, k.count, wg.wg_tiles, wg.nbp);
+}
+// Kdot of direction j of nvec of class k (kernels_fisher.h): the direction's coefficients into cf, then the matrix into Kd
+void launch_kdot(medgp_ctx *c, const MedgpDev &V, const SizeClass &k, const double *d_dir, int nvec, int j, double *cf, double *Kd) {
+    {
+        Launcher l(c, KID_FI_PREP);
+        hipLaunchKernelGGL(k_fisher_prep, dim3(k.count, 1 + (V.Q * V.D * V.D + 255) / 256), dim3(256), 0, c->stream, V, c->d_theta, d_dir, nvec, j, cf);
+    }
+    Launcher l(c, KID_FI_KDOT);   // (Q <= 16 was checked)
+    with_q16(V.Q, [&](auto q, auto q0) {
+        hipLaunchKernelGGL((k_fisher_kdot<decltype(q)::value, decltype(q0)::value>), dim3(fisher_kdot_grid(k.nbmax), k.count), dim3(256), 0, c->stream, V, cf, Kd);
+    });
+}
+// T = P Kdot of class k (kernels_fisher.h)
+void launch_fisher_t(medgp_ctx *c, const MedgpDev &V, const SizeClass &k, const double *Kd, double *Tm) {
+    Launcher l(c, KID_FI_T);
+    hipLaunchKernelGGL(k_fisher_t, dim3(fisher_t_grid(k.nbmax), k.count), dim3(WG_THREADS), 0, c->stream, V, Kd, Tm, k.nbmax);
+}
+
+// The end of a blocking call whose epilogue wrote lane 0's staging: objective, gradient (flag_grad) and status of the caller's rows to
+// the host (null: not wanted), with one more block of the call's own (extra_bytes of extra_src -> extra_dst; 0: none) behind them;
+// the stream is waited for and the blocks outgrown arenas left behind are freed.
+int download_objective(medgp_ctx *c, int nbatch, int flag_grad, double *obj, double *grad, int32_t *status,
+                       void *extra_dst = nullptr, const void *extra_src = nullptr, size_t extra_bytes = 0) {
+    if (obj) HIPCHK(c, hipMemcpyAsync(obj, c->d_nlml, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    if (flag_grad && grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * c->H, hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    if (extra_bytes) HIPCHK(c, hipMemcpyAsync(extra_dst, extra_src, extra_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_retired(c);
+    return MEDGP_OK;
+}
+
+// The per-direction outputs of a call, [nvec][nbatch][H] on the device (count doubles: the call's *_tables.h rule): download_directions
+// queues their way to `out`; once the stream has been waited for, transpose_directions lays them out as the caller takes them,
+// [nbatch][nvec][H].
+int download_directions(medgp_ctx *c, const double *d_out, size_t count, std::vector<double> &out) {
+    out.resize(count);
+    HIPCHK(c, hipMemcpyAsync(out.data(), d_out, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return MEDGP_OK;
+}
+void transpose_directions(const std::vector<double> &out, int nbatch, int nvec, size_t H, double *dst) {
+    for (int b = 0; b < nbatch; b++)
+        for (int j = 0; j < nvec; j++)
+            std::memcpy(dst + ((size_t)b * nvec + j) * H, out.data() + ((size_t)j * nbatch + b) * H, H * sizeof(double));
 }
 
 }  // namespace
@@ -1422,17 +1528,11 @@ int medgp_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double
         free_retired(c);   // (the stream is idle: blocks that outgrown arenas left behind can go)
         return MEDGP_OK;
     }
-    // (this path shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
-    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    int rc;
+    if ((rc = wait_lane0_staging(c))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, th_bytes, hipMemcpyHostToDevice, c->stream));
-    int rc = medgp_nlml_grad_device(c, nbatch, slots, c->d_theta, flag_grad, c->d_nlml, c->d_grad, c->d_status_out);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(nlml, c->d_nlml, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    if (want_grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * H, hipMemcpyDeviceToHost, c->stream));
-    if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_retired(c);
-    return MEDGP_OK;
+    if ((rc = medgp_nlml_grad_device(c, nbatch, slots, c->d_theta, flag_grad, c->d_nlml, c->d_grad, c->d_status_out))) return rc;
+    return download_objective(c, nbatch, want_grad, nlml, grad, status);
 }
 
 int medgp_screen(medgp_ctx *c, int nslots, const int32_t *slots, int ninit, const double *theta, double *nlml, int32_t *status) {
@@ -1450,8 +1550,7 @@ int medgp_screen(medgp_ctx *c, int nslots, const int32_t *slots, int ninit, cons
         if (rc) return rc;
         c->screen_theta_cap = (size_t)ninit * H;
     }
-    // (the result staging is lane 0's: a download of that lane still in flight on the copy stream must have read it first)
-    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    { int rc = wait_lane0_staging(c); if (rc) return rc; }
     HIPCHK(c, hipMemcpyAsync(c->d_screen_theta, theta, sizeof(double) * ninit * H, hipMemcpyHostToDevice, c->stream));
     // pinned landing area of all results: [nlml: total doubles | status: total ints]
     const size_t land = sizeof(double) * total + sizeof(int32_t) * total;
@@ -2379,31 +2478,24 @@ int medgp_loo_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double
 
 // The negative LOO log pseudo-likelihood and its gradient (kernels_loo_grad.h).  ONE pipeline run in the grouped order (as
 // medgp_loo_batch: factor, U = L^-T, alpha), then per size class, in stream order: k_loo_kinv (P = U U^T into the dead Kmat block),
-// k_loo_vec (u, s, log p; then v = P u and J), k_loo_wgrad (W_loo tiles -> slab, wdiag), and the nlml gradient's own k_slabsum and
-// k_epilogue, the latter told to report J (scal[2]) instead of the nlml.  flag_grad = 0 stops after the first pass of k_loo_vec.
+// k_loo_vec (u, s, log p; then v = P u and J -> scal[2]), k_loo_wgrad (W_loo tiles -> slab, wdiag), and finish_objective_class
+// (k_slabsum, k_epilogue).  flag_grad = 0 stops after the first pass of k_loo_vec.
 int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int flag_grad, double *obj, double *grad,
                    int32_t *status) {
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !obj) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
     if (flag_grad && !grad) return fail(c, MEDGP_ERR_ARG, "grad is NULL with flag_grad set");
-    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_loo_grad supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds K^-1 here", c->rules.Q);
     int rc;
+    if ((rc = check_q16(c, "medgp_loo_grad", kWhyKinv))) return rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const BatchPlan &P = c->plan;
     if ((rc = buf_ensure(c, BUF_GVEC, 4 * P.need_vec * sizeof(double)))) return rc;
     double *gvec = buf<double>(c, BUF_GVEC);
-    const size_t H = c->H;
-    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
-    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
-    // the generic kernels (MEDGP_V0) keep W where P goes: this call always takes the templated ones
-    const bool v0 = c->rules.use_v0;
-    c->rules.use_v0 = false;
-    rc = factor_run(c, nbatch, theta, true, false);
-    c->rules.use_v0 = v0;
-    if (rc) return rc;
+    if ((rc = wait_lane0_staging(c))) return rc;
+    if ((rc = factor_run_templated(c, nbatch, theta))) return rc;
     const double log2pi = std::log(2.0 * c->pi);
     for (const SizeClass &k : P.cls) {
         const MedgpDev V = class_view(c, P, k);
@@ -2415,30 +2507,16 @@ int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
             hipLaunchKernelGGL(k_loo_vec, dim3(1, nb), dim3(256), 0, c->stream, V, vec, 2, log2pi);
         } else {
             const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
-            const dim3 tg(wg.grid), tb(WG_THREADS);
-            { Launcher l(c, KID_LOO_KINV); hipLaunchKernelGGL(k_loo_kinv, tg, tb, 0, c->stream, V, nb, wg.wg_tiles, wg.nbp); }
+            launch_kinv(c, P, k, V);
             { Launcher l(c, KID_LOO_VEC); hipLaunchKernelGGL(k_loo_vec, dim3(4 * nt64, nb), dim3(256), 0, c->stream, V, vec, 1, log2pi); }
-            {
-                Launcher l(c, KID_LOO_WGRAD);   // (Q <= 16 was checked)
-                with_q16(V.Q, [&](auto q, auto q0) {
-                    hipLaunchKernelGGL((k_loo_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, vec, nb, wg.wg_tiles, wg.nbp);
-                });
-            }
-            const int nbins3 = 3 * V.Q * tri(V.D);
-            Launcher l(c, KID_EPILOGUE);
-            hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V);
+            launch_tiles(c, KID_LOO_WGRAD, V.Q, wg, [&](auto q, auto q0, dim3 tg, dim3 tb) {
+                hipLaunchKernelGGL((k_loo_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, vec, nb, wg.wg_tiles, wg.nbp);
+            });
         }
-        Launcher l(c, KID_EPILOGUE);
-        const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
-        hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, c->d_theta, flag_grad, 1, c->d_nlml, c->d_grad, c->d_status_out, 1);
+        finish_objective_class(c, V, nb, flag_grad);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(obj, c->d_nlml, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    if (flag_grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * H, hipMemcpyDeviceToHost, c->stream));
-    if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_retired(c);
-    return MEDGP_OK;
+    return download_objective(c, nbatch, flag_grad, obj, grad, status);
 }
 
 // The negative leave-group-out log pseudo-likelihood and its gradient (kernels_lgo_grad.h).  ONE pipeline run in the grouped order (as
@@ -2446,16 +2524,16 @@ int medgp_loo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
 // singleton groups: u, s, lpd), for a gradient k_loo_kinv (P into the dead Kmat block) and k_lgo_prep (Tt = P diag(s)); per launch
 // chunk of the class's larger groups k_loo_gram / k_postfactor / k_loo_solve (R, w, lpd_g: medgp_loo_batch's kernels and bits) and, for
 // a gradient, k_lgo_inv (R^-1), k_lgo_s (S_g, r_g) and k_lgo_t (the group's columns of Tt) -- a chunk is finished before the next one
-// reuses the blocks; then k_loo_vec mode 1 (v = P r), k_lgo_obj (J -> scal[2]), k_lgo_wgrad and the nlml gradient's k_slabsum and
-// k_epilogue.  flag_grad = 0 runs k_loo_vec mode 0, k_lgo_mask, the three LOO kernels of every chunk, k_lgo_obj and k_epilogue.
+// reuses the blocks; then k_loo_vec mode 1 (v = P r), k_lgo_obj (J -> scal[2]), k_lgo_wgrad and finish_objective_class (k_slabsum,
+// k_epilogue).  flag_grad = 0 runs k_loo_vec mode 0, k_lgo_mask, the three LOO kernels of every chunk, k_lgo_obj and k_epilogue.
 int medgp_lgo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int32_t *group, const int32_t *ngroups,
                    int flag_grad, double *obj, double *grad, int32_t *status, int32_t *group_status) {
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !obj || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
     if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
     if (flag_grad && !grad) return fail(c, MEDGP_ERR_ARG, "grad is NULL with flag_grad set");
-    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_lgo_grad supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds K^-1 here", c->rules.Q);
     int rc;
+    if ((rc = check_q16(c, "medgp_lgo_grad", kWhyKinv))) return rc;
     if (!group) {   // classic LOO: medgp_loo_grad's bits
         if (ngroups) return fail(c, MEDGP_ERR_ARG, "ngroups without group ids");
         std::vector<int32_t> st((size_t)nbatch, 0);
@@ -2520,14 +2598,8 @@ int medgp_lgo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     const JointTile *d_pairs = buf<JointTile>(c, BUF_PAIRS), *d_jobs = buf<JointTile>(c, BUF_BLKS);
     const JointTile *d_cols = buf<JointTile>(c, BUF_LGO_COLS), *d_trows = buf<JointTile>(c, BUF_LGO_TROWS);
     const int *d_sgl = buf<int>(c, BUF_LGO_SGL), *d_ent = buf<int>(c, BUF_LGO_ENT), *d_gord = buf<int>(c, BUF_LGO_GORD);
-    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
-    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
-    // the generic kernels (MEDGP_V0) keep W where P goes: this call always takes the templated ones
-    const bool v0 = c->rules.use_v0;
-    c->rules.use_v0 = false;
-    rc = factor_run(c, nbatch, theta, true, false);
-    c->rules.use_v0 = v0;
-    if (rc) return rc;
+    if ((rc = wait_lane0_staging(c))) return rc;
+    if ((rc = factor_run_templated(c, nbatch, theta))) return rc;
     const double log2pi = std::log(2.0 * c->pi);
     for (size_t ci = 0; ci < P.cls.size(); ci++) {
         const SizeClass &k = P.cls[ci];
@@ -2536,11 +2608,10 @@ int medgp_lgo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
         double *Tm = flag_grad ? tmat + k.off_mat : nullptr;
         const int nb = k.count, nt64 = k.nbmax;
         const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
-        const dim3 tg(wg.grid), tb(WG_THREADS);
         { Launcher l(c, KID_LOO_VEC); hipLaunchKernelGGL(k_loo_vec, dim3(4 * nt64, nb), dim3(256), 0, c->stream, V, vec, 0, log2pi); }
         { Launcher l(c, KID_LGO_VEC); hipLaunchKernelGGL(k_lgo_mask, dim3((k.ld + 255) / 256, nb), dim3(256), 0, c->stream, V, vec, d_sgl + G.sgl_off[ci], d_lpd); }
         if (flag_grad) {
-            { Launcher l(c, KID_LOO_KINV); hipLaunchKernelGGL(k_loo_kinv, tg, tb, 0, c->stream, V, nb, wg.wg_tiles, wg.nbp); }
+            launch_kinv(c, P, k, V);
             { Launcher l(c, KID_LGO_VEC); hipLaunchKernelGGL(k_lgo_prep, dim3(nt64, 16 * nt64, nb), dim3(256), 0, c->stream, V, vec, Tm); }
         }
         for (size_t x = 0; x < T.chunks.size(); x++) {   // chunks reuse the blocks in stream order
@@ -2561,30 +2632,16 @@ int medgp_lgo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
         }
         if (flag_grad) { Launcher l(c, KID_LOO_VEC); hipLaunchKernelGGL(k_loo_vec, dim3(4 * nt64, nb), dim3(256), 0, c->stream, V, vec, 1, log2pi); }
         { Launcher l(c, KID_LGO_VEC); hipLaunchKernelGGL(k_lgo_obj, dim3(nb), dim3(64), 0, c->stream, V, d_ent + 2 * k.b0, d_gord, d_lpd); }
-        if (flag_grad) {
-            {
-                Launcher l(c, KID_LGO_WGRAD);   // (Q <= 16 was checked)
-                with_q16(V.Q, [&](auto q, auto q0) {
-                    hipLaunchKernelGGL((k_lgo_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, vec, Tm, nb, wg.wg_tiles, wg.nbp);
-                });
-            }
-            const int nbins3 = 3 * V.Q * tri(V.D);
-            Launcher l(c, KID_EPILOGUE);
-            hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V);
-        }
-        Launcher l(c, KID_EPILOGUE);
-        const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
-        hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, c->d_theta, flag_grad, 1, c->d_nlml, c->d_grad, c->d_status_out, 1);
+        if (flag_grad)
+            launch_tiles(c, KID_LGO_WGRAD, V.Q, wg, [&](auto q, auto q0, dim3 tg, dim3 tb) {
+                hipLaunchKernelGGL((k_lgo_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, vec, Tm, nb, wg.wg_tiles, wg.nbp);
+            });
+        finish_objective_class(c, V, nb, flag_grad);
     }
     HIPCHK(c, hipGetLastError());
     std::vector<int32_t> st((size_t)nbatch, 0);
     std::vector<int> gst(NGz, 0);
-    HIPCHK(c, hipMemcpyAsync(obj, c->d_nlml, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    if (flag_grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * H, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    if (NG > 0) HIPCHK(c, hipMemcpyAsync(gst.data(), d_gstat, sizeof(int) * NG, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_retired(c);
+    if ((rc = download_objective(c, nbatch, flag_grad, obj, grad, st.data(), gst.data(), d_gstat, sizeof(int) * (size_t)NG))) return rc;
     for (int b = 0; b < nbatch; b++) {
         if (status) status[b] = st[b];
         bool bad = false;
@@ -2603,25 +2660,23 @@ int medgp_lgo_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
 
 // Products of the Fisher information with nvec directions per entry (kernels_fisher.h).  ONE pipeline run in the grouped order (as
 // medgp_loo_grad: factor, U = L^-T), then per size class k_loo_kinv (P = U U^T into the dead Kmat block).  Then, direction by
-// direction, per size class in stream order: k_fisher_prep (the direction's coefficients), k_fisher_kdot (Kdot), k_fisher_t
-// (T = P Kdot), k_fisher_wgrad (W_F tiles -> slab, wdiag) and the nlml gradient's own k_slabsum and k_epilogue, the latter told to
-// leave the prior and the scalar out.  Kdot and T are buffers of the call, reused by every direction; every direction runs the same
-// launches with the same geometry, so its bits depend neither on nvec nor on its position.  The four matrices of every entry are
-// alive at once: a call that needs more than the memory budget is refused (fisher_tables.h), there are no memory waves.
+// direction, per size class in stream order: launch_kdot (k_fisher_prep, k_fisher_kdot), k_fisher_t (T = P Kdot), k_fisher_wgrad
+// (W_F tiles -> slab, wdiag), k_slabsum and k_epilogue (EPI_BARE).  Kdot and T are buffers of the call, reused by every direction;
+// every direction runs the same launches with the same geometry, so its bits depend neither on nvec nor on its position.  The four
+// matrices of every entry are alive at once: a call that needs more than the memory budget is refused (fisher_tables.h), there are
+// no memory waves.
 int medgp_fisher_vec(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int nvec, const double *vec, double *fvec,
                      int32_t *status) {
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !vec || !fvec) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if (nvec < 1) return fail(c, MEDGP_ERR_ARG, "nvec = %d", nvec);
-    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_fisher_vec supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds K^-1 here", c->rules.Q);
     int rc;
+    if ((rc = check_q16(c, "medgp_fisher_vec", kWhyKinv))) return rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const BatchPlan &P = c->plan;
-    if (P.nwaves > 1 || !fisher_fits(P.need_mat, c->rules.mem_budget))
-        return fail(c, MEDGP_ERR_CAPACITY, "the call's per-entry matrices (%d of %zu MB) exceed the memory budget of %zu MB (MEDGP_MEM_BUDGET_GB): split the call",
-                    FISHER_MATS, (P.need_mat * sizeof(double)) >> 20, c->rules.mem_budget >> 20);
+    if ((rc = check_one_wave(c, fisher_fits(P.need_mat, c->rules.mem_budget), FISHER_MATS, ""))) return rc;
     const size_t H = c->H;
     const FisherBuffers fb = fisher_buffers(P.need_mat, nbatch, nvec, (int)H, c->rules.Q, c->rules.D);
     if ((rc = buf_ensure(c, BUF_FI_KDOT, fb.mat_doubles * sizeof(double)))) return rc;
@@ -2631,60 +2686,29 @@ int medgp_fisher_vec(medgp_ctx *c, int nbatch, const int32_t *slots, const doubl
     if ((rc = buf_ensure(c, BUF_FI_OUT, fb.dir_doubles * sizeof(double)))) return rc;
     double *kdot = buf<double>(c, BUF_FI_KDOT), *tmat = buf<double>(c, BUF_FI_T), *coef = buf<double>(c, BUF_FI_COEF);
     double *d_dir = buf<double>(c, BUF_FI_DIR), *d_out = buf<double>(c, BUF_FI_OUT);
-    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
-    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    if ((rc = wait_lane0_staging(c))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_dir, vec, fb.dir_doubles * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    // the generic kernels (MEDGP_V0) keep W where P goes: this call always takes the templated ones
-    const bool v0 = c->rules.use_v0;
-    c->rules.use_v0 = false;
-    rc = factor_run(c, nbatch, theta, true, false);
-    c->rules.use_v0 = v0;
-    if (rc) return rc;
-    for (const SizeClass &k : P.cls) {
-        const MedgpDev V = class_view(c, P, k);
-        const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, k.count, k.nbmax);
-        Launcher l(c, KID_LOO_KINV);
-        hipLaunchKernelGGL(k_loo_kinv, dim3(wg.grid), dim3(WG_THREADS), 0, c->stream, V, k.count, wg.wg_tiles, wg.nbp);
-    }
+    if ((rc = factor_run_templated(c, nbatch, theta))) return rc;
+    for (const SizeClass &k : P.cls) launch_kinv(c, P, k, class_view(c, P, k));
     for (int j = 0; j < nvec; j++)
         for (const SizeClass &k : P.cls) {
             const MedgpDev V = class_view(c, P, k);
-            const int nb = k.count, nt64 = k.nbmax;
+            const int nb = k.count;
             double *Kd = kdot + k.off_mat, *Tm = tmat + k.off_mat, *cf = coef + (size_t)k.b0 * V.hyp_stride;
-            const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
-            const dim3 tg(wg.grid), tb(WG_THREADS);
-            {
-                Launcher l(c, KID_FI_PREP);
-                hipLaunchKernelGGL(k_fisher_prep, dim3(nb, 1 + (V.Q * V.D * V.D + 255) / 256), dim3(256), 0, c->stream, V, c->d_theta, d_dir, nvec, j, cf);
-            }
-            {
-                Launcher l(c, KID_FI_KDOT);   // (Q <= 16 was checked)
-                with_q16(V.Q, [&](auto q, auto q0) {
-                    hipLaunchKernelGGL((k_fisher_kdot<decltype(q)::value, decltype(q0)::value>), dim3(fisher_kdot_grid(nt64), nb), dim3(256), 0, c->stream, V, cf, Kd);
-                });
-            }
-            { Launcher l(c, KID_FI_T); hipLaunchKernelGGL(k_fisher_t, dim3(fisher_t_grid(nt64), nb), tb, 0, c->stream, V, Kd, Tm, nt64); }
-            {
-                Launcher l(c, KID_FI_WGRAD);
-                with_q16(V.Q, [&](auto q, auto q0) {
-                    hipLaunchKernelGGL((k_fisher_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, Tm, nb, wg.wg_tiles, wg.nbp);
-                });
-            }
-            const int nbins3 = 3 * V.Q * tri(V.D);
-            { Launcher l(c, KID_EPILOGUE); hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V); }
-            Launcher l(c, KID_EPILOGUE);
-            const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
-            hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, c->d_theta, 1, 1, c->d_nlml, d_out + (size_t)j * nbatch * H, c->d_status_out, 2);
+            const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, k.nbmax);
+            launch_kdot(c, V, k, d_dir, nvec, j, cf, Kd);
+            launch_fisher_t(c, V, k, Kd, Tm);
+            launch_tiles(c, KID_FI_WGRAD, V.Q, wg, [&](auto q, auto q0, dim3 tg, dim3 tb) {
+                hipLaunchKernelGGL((k_fisher_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, Tm, nb, wg.wg_tiles, wg.nbp);
+            });
+            launch_slabsum(c, c->stream, V, nb);
+            launch_epilogue(c, c->stream, V, nb, c->d_theta, 1, 1, c->d_nlml, d_out + (size_t)j * nbatch * H, c->d_status_out, EPI_BARE);
         }
     HIPCHK(c, hipGetLastError());
-    std::vector<double> out(fb.dir_doubles);
-    HIPCHK(c, hipMemcpyAsync(out.data(), d_out, fb.dir_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_retired(c);
-    for (int b = 0; b < nbatch; b++)
-        for (int j = 0; j < nvec; j++)
-            std::memcpy(fvec + ((size_t)b * nvec + j) * H, out.data() + ((size_t)j * nbatch + b) * H, H * sizeof(double));
+    std::vector<double> out;
+    if ((rc = download_directions(c, d_out, fb.dir_doubles, out))) return rc;
+    if ((rc = download_objective(c, nbatch, 0, nullptr, nullptr, status))) return rc;
+    transpose_directions(out, nbatch, nvec, H, fvec);
     return MEDGP_OK;
 }
 
@@ -2700,15 +2724,13 @@ int medgp_hess_vec(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     if (!c) return MEDGP_ERR_ARG;
     if (!slots || !theta || !vec || !hvec) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if (nvec < 1) return fail(c, MEDGP_ERR_ARG, "nvec = %d", nvec);
-    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_hess_vec supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds K^-1 here", c->rules.Q);
     int rc;
+    if ((rc = check_q16(c, "medgp_hess_vec", kWhyKinv))) return rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const BatchPlan &P = c->plan;
-    if (P.nwaves > 1 || !hess_fits(P.need_mat, c->rules.mem_budget))
-        return fail(c, MEDGP_ERR_CAPACITY, "the call's per-entry matrices (%d of %zu MB) exceed the memory budget of %zu MB (MEDGP_MEM_BUDGET_GB): split the call",
-                    HESS_MATS, (P.need_mat * sizeof(double)) >> 20, c->rules.mem_budget >> 20);
+    if ((rc = check_one_wave(c, hess_fits(P.need_mat, c->rules.mem_budget), HESS_MATS, ""))) return rc;
     const size_t H = c->H, QDD = (size_t)c->rules.Q * c->rules.D * c->rules.D;
     const HessBuffers hb = hess_buffers(P.need_mat, P.need_vec, P.need_slab, nbatch, nvec, (int)H, c->rules.Q, c->rules.D);
     if ((rc = buf_ensure(c, BUF_FI_KDOT, hb.mat_doubles * sizeof(double)))) return rc;
@@ -2722,15 +2744,9 @@ int medgp_hess_vec(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     double *kdot = buf<double>(c, BUF_FI_KDOT), *tmat = buf<double>(c, BUF_FI_T), *coef = buf<double>(c, BUF_FI_COEF);
     double *d_dir = buf<double>(c, BUF_FI_DIR), *d_out = buf<double>(c, BUF_FI_OUT);
     double *hislab = buf<double>(c, BUF_HE_SLAB), *sums = buf<double>(c, BUF_HE_SUMS), *hvecs = buf<double>(c, BUF_HE_VEC);
-    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
-    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    if ((rc = wait_lane0_staging(c))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_dir, vec, hb.dir_doubles * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    // the generic kernels (MEDGP_V0) keep W where P goes: this call always takes the templated ones
-    const bool v0 = c->rules.use_v0;
-    c->rules.use_v0 = false;
-    rc = factor_run(c, nbatch, theta, true, false);
-    c->rules.use_v0 = v0;
-    if (rc) return rc;
+    if ((rc = factor_run_templated(c, nbatch, theta))) return rc;
     // the view of the W pass of a class: block sums and diag(W) in the call's own buffers, the direction's view keeps the context's
     auto w_view = [&](const MedgpDev &V, const SizeClass &k) {
         MedgpDev W = V;
@@ -2742,23 +2758,14 @@ int medgp_hess_vec(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
         const MedgpDev V = class_view(c, P, k), W = w_view(V, k);
         const int nb = k.count;
         const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, k.nbmax);
-        const dim3 tg(wg.grid), tb(WG_THREADS);
         double *hi = hislab + hess_hislab_of(k.off_slab), *M3 = sums + (3 * (size_t)nbatch + k.b0) * QDD, *M4 = M3 + (size_t)nbatch * QDD;
-        { Launcher l(c, KID_LOO_KINV); hipLaunchKernelGGL(k_loo_kinv, tg, tb, 0, c->stream, V, nb, wg.wg_tiles, wg.nbp); }
-        {
-            Launcher l(c, KID_HE_MOMENTS);   // (Q <= 16 was checked)
-            with_q16(V.Q, [&](auto q, auto q0) {
-                hipLaunchKernelGGL((k_hess_moments<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, W, hi, nb, wg.wg_tiles, wg.nbp);
-            });
-        }
-        const int nbins3 = 3 * V.Q * tri(V.D);
-        { Launcher l(c, KID_EPILOGUE); hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, W); }
+        launch_kinv(c, P, k, V);
+        launch_tiles(c, KID_HE_MOMENTS, V.Q, wg, [&](auto q, auto q0, dim3 tg, dim3 tb) {
+            hipLaunchKernelGGL((k_hess_moments<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, W, hi, nb, wg.wg_tiles, wg.nbp);
+        });
+        launch_slabsum(c, c->stream, W, nb);
         { Launcher l(c, KID_HE_SLABSUM); hipLaunchKernelGGL(k_hess_slabsum, dim3(nb, hess_slabsum_grid(V.Q, V.D)), dim3(256), 0, c->stream, W, hi, M3, M4); }
-        if (grad) {
-            Launcher l(c, KID_EPILOGUE);
-            const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
-            hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, W, c->d_theta, 1, 1, c->d_nlml, c->d_grad, c->d_status_out, 2);
-        }
+        if (grad) launch_epilogue(c, c->stream, W, nb, c->d_theta, 1, 1, c->d_nlml, c->d_grad, c->d_status_out, EPI_BARE);
     }
     for (int j = 0; j < nvec; j++)
         for (const SizeClass &k : P.cls) {
@@ -2767,42 +2774,23 @@ int medgp_hess_vec(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
             double *Kd = kdot + k.off_mat, *Tm = tmat + k.off_mat, *cf = coef + (size_t)k.b0 * V.hyp_stride, *beta = hvecs + k.off_vec;
             const HessW hw{W.S, W.SM, W.SV, W.SV + (size_t)nbatch * QDD, W.SV + 2 * (size_t)nbatch * QDD, W.wdiag};
             const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
-            const dim3 tg(wg.grid), tb(WG_THREADS);
-            {
-                Launcher l(c, KID_FI_PREP);
-                hipLaunchKernelGGL(k_fisher_prep, dim3(nb, 1 + (V.Q * V.D * V.D + 255) / 256), dim3(256), 0, c->stream, V, c->d_theta, d_dir, nvec, j, cf);
-            }
-            {
-                Launcher l(c, KID_FI_KDOT);
-                with_q16(V.Q, [&](auto q, auto q0) {
-                    hipLaunchKernelGGL((k_fisher_kdot<decltype(q)::value, decltype(q0)::value>), dim3(fisher_kdot_grid(nt64), nb), dim3(256), 0, c->stream, V, cf, Kd);
-                });
-            }
-            { Launcher l(c, KID_FI_T); hipLaunchKernelGGL(k_fisher_t, dim3(fisher_t_grid(nt64), nb), tb, 0, c->stream, V, Kd, Tm, nt64); }
+            launch_kdot(c, V, k, d_dir, nvec, j, cf, Kd);
+            launch_fisher_t(c, V, k, Kd, Tm);
             { Launcher l(c, KID_HE_BETA); hipLaunchKernelGGL(k_hess_beta, dim3(hess_beta_grid(nt64), nb), dim3(256), 0, c->stream, V, Tm, beta); }
-            {
-                Launcher l(c, KID_HE_WGRAD);
-                with_q16(V.Q, [&](auto q, auto q0) {
-                    hipLaunchKernelGGL((k_hess_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, Tm, beta, nb, wg.wg_tiles, wg.nbp);
-                });
-            }
-            const int nbins3 = 3 * V.Q * tri(V.D);
-            { Launcher l(c, KID_EPILOGUE); hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V); }
+            launch_tiles(c, KID_HE_WGRAD, V.Q, wg, [&](auto q, auto q0, dim3 tg, dim3 tb) {
+                hipLaunchKernelGGL((k_hess_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, Tm, beta, nb, wg.wg_tiles, wg.nbp);
+            });
+            launch_slabsum(c, c->stream, V, nb);
+            const dim3 eg(nb, epilogue_parts(nb, c->rules.num_cu, V.H, MEDGP_EPI_PARTS));
             Launcher l(c, KID_HE_EPILOGUE);
-            const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
-            hipLaunchKernelGGL(k_hess_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, hw, c->d_theta, d_dir, nvec, j, cf,
+            hipLaunchKernelGGL(k_hess_epilogue, eg, dim3(256), 0, c->stream, V, hw, c->d_theta, d_dir, nvec, j, cf,
                                d_out + (size_t)j * nbatch * H, c->d_status_out);
         }
     HIPCHK(c, hipGetLastError());
-    std::vector<double> out(hb.dir_doubles);
-    HIPCHK(c, hipMemcpyAsync(out.data(), d_out, hb.dir_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * H, hipMemcpyDeviceToHost, c->stream));
-    if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_retired(c);
-    for (int b = 0; b < nbatch; b++)
-        for (int j = 0; j < nvec; j++)
-            std::memcpy(hvec + ((size_t)b * nvec + j) * H, out.data() + ((size_t)j * nbatch + b) * H, H * sizeof(double));
+    std::vector<double> out;
+    if ((rc = download_directions(c, d_out, hb.dir_doubles, out))) return rc;
+    if ((rc = download_objective(c, nbatch, 1, nullptr, grad, status))) return rc;
+    transpose_directions(out, nbatch, nvec, H, hvec);
     return MEDGP_OK;
 }
 
@@ -2820,8 +2808,8 @@ int medgp_posterior_jvp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
     if (!slots || !theta || !offsets || !vec || !dmean || !dvar) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if (nvec < 1) return fail(c, MEDGP_ERR_ARG, "nvec = %d", nvec);
     if ((mean == nullptr) != (var == nullptr)) return fail(c, MEDGP_ERR_ARG, "mean and var: both or neither");
-    if (c->rules.Q > PJVP_MAX_Q) return fail(c, MEDGP_ERR_ARG, "medgp_posterior_jvp_batch supports Q <= 16 (Q = %d)", c->rules.Q);
     int rc;
+    if ((rc = check_q16(c, "medgp_posterior_jvp_batch", nullptr))) return rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     // (mean / var are optional here: the per-point outputs the call requires are dmean / dvar, checked above)
     if ((rc = check_points(c, nbatch, offsets, meta2, t2, (const float *)dmean, (const float *)dvar, "dmean / dvar"))) return rc;
@@ -2832,9 +2820,7 @@ int medgp_posterior_jvp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const BatchPlan &P = c->plan;
-    if (P.nwaves > 1 || !pjvp_fits(P.need_mat, c->rules.mem_budget))
-        return fail(c, MEDGP_ERR_CAPACITY, "the call's per-entry matrices (%d of %zu MB) exceed the memory budget of %zu MB (MEDGP_MEM_BUDGET_GB): split the call",
-                    PJVP_MATS, (P.need_mat * sizeof(double)) >> 20, c->rules.mem_budget >> 20);
+    if ((rc = check_one_wave(c, pjvp_fits(P.need_mat, c->rules.mem_budget), PJVP_MATS, ""))) return rc;
     const size_t H = c->H;
     const PjvpBuffers pb = pjvp_buffers(P.need_mat, P.need_vec, nbatch, nvec, (int)H, c->rules.Q, c->rules.D, M);
     PointTables<PostTile> T;
@@ -2850,12 +2836,7 @@ int medgp_posterior_jvp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
     double *kdot = buf<double>(c, BUF_FI_KDOT), *coef = buf<double>(c, BUF_FI_COEF), *d_dir = buf<double>(c, BUF_FI_DIR);
     double *uvec = buf<double>(c, BUF_PJ_U), *d_dmean = buf<double>(c, BUF_PJ_OUT), *d_dvar = d_dmean + pjvp_dvar_offset(M, nvec);
     HIPCHK(c, hipMemcpyAsync(d_dir, vec, pb.dir_doubles * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    // the generic kernels (MEDGP_V0) are not honoured: this call always takes the templated ones, as the Fisher call
-    const bool v0 = c->rules.use_v0;
-    c->rules.use_v0 = false;
-    rc = factor_run(c, nbatch, theta, true, false);
-    c->rules.use_v0 = v0;
-    if (rc) return rc;
+    if ((rc = factor_run_templated(c, nbatch, theta))) return rc;   // (its results travel through buffers of its own: no wait for lane 0's staging)
     for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
         const SizeClass &k = P.cls[ch.cls];
         const MedgpDev V = class_view(c, P, k);
@@ -2868,16 +2849,7 @@ int medgp_posterior_jvp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
                                ch.stride, nvec, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), d_dmean, d_dvar);
         }
         for (int j = 0; j < nvec; j++) {
-            {
-                Launcher l(c, KID_FI_PREP);
-                hipLaunchKernelGGL(k_fisher_prep, dim3(nb, 1 + (V.Q * V.D * V.D + 255) / 256), dim3(256), 0, c->stream, V, c->d_theta, d_dir, nvec, j, cf);
-            }
-            {
-                Launcher l(c, KID_FI_KDOT);   // (Q <= 16 was checked)
-                with_q16(V.Q, [&](auto q, auto q0) {
-                    hipLaunchKernelGGL((k_fisher_kdot<decltype(q)::value, decltype(q0)::value>), dim3(fisher_kdot_grid(nt64), nb), dim3(256), 0, c->stream, V, cf, Kd);
-                });
-            }
+            launch_kdot(c, V, k, d_dir, nvec, j, cf, Kd);
             { Launcher l(c, KID_PJ_U); hipLaunchKernelGGL(k_pjvp_u, dim3(pjvp_u_grid(nt64), nb), dim3(256), 0, c->stream, V, Kd, u); }
             Launcher l(c, KID_PJ_DIR);
             hipLaunchKernelGGL(k_pjvp_dir, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK),
@@ -2919,8 +2891,8 @@ int medgp_posterior_vjp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
     if (builtin && (!loss || !y2)) return fail(c, MEDGP_ERR_ARG, "loss / y2 is NULL with a built-in loss");
     if (!builtin && (!cot_mean || !cot_var)) return fail(c, MEDGP_ERR_ARG, "cot_mean / cot_var is NULL with MEDGP_PLOSS_CUSTOM");
     if (!builtin && (loss || y2 || wt)) return fail(c, MEDGP_ERR_ARG, "loss / y2 / wt given with MEDGP_PLOSS_CUSTOM");
-    if (c->rules.Q > PJVP_MAX_Q) return fail(c, MEDGP_ERR_ARG, "medgp_posterior_vjp_batch supports Q <= 16 (Q = %d)", c->rules.Q);
     int rc;
+    if ((rc = check_q16(c, "medgp_posterior_vjp_batch", nullptr))) return rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     // (mean / var are optional here: the per-point inputs the call requires stand in their place)
     const float *need_a = (const float *)(builtin ? y2 : cot_mean), *need_b = (const float *)(builtin ? y2 : cot_var);
@@ -2934,9 +2906,7 @@ int medgp_posterior_vjp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const BatchPlan &P = c->plan;
-    if (P.nwaves > 1 || !pvjp_fits(P.need_mat, c->rules.mem_budget))
-        return fail(c, MEDGP_ERR_CAPACITY, "the call's per-entry matrices (%d of %zu MB) exceed the memory budget of %zu MB (MEDGP_MEM_BUDGET_GB): split the call",
-                    PVJP_MATS, (P.need_mat * sizeof(double)) >> 20, c->rules.mem_budget >> 20);
+    if ((rc = check_one_wave(c, pvjp_fits(P.need_mat, c->rules.mem_budget), PVJP_MATS, ""))) return rc;
     PvjpTables T;
     TableError terr{};
     if (!build_pvjp_tables(table_classes(P), P.order.data(), offsets, (lmc && M > 0) ? meta2 : nullptr, nbatch, D, c->posterior_budget, T, terr))
@@ -2978,14 +2948,8 @@ int medgp_posterior_vjp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
     const double *d_in = buf<double>(c, BUF_PV_IN), *d_t2 = buf<double>(c, BUF_T2);
     double *d_pts = buf<double>(c, BUF_PV_PTS), *d_cvec = buf<double>(c, BUF_PV_VEC), *d_small = buf<double>(c, BUF_PV_SMALL);
     double *d_out = buf<double>(c, BUF_PV_OUT), *d_work = buf<double>(c, BUF_WORK);
-    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
-    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
-    // the generic kernels (MEDGP_V0) are not honoured: this call always takes the templated ones, as the JVP call
-    const bool v0 = c->rules.use_v0;
-    c->rules.use_v0 = false;
-    rc = factor_run(c, nbatch, theta, true, false);
-    c->rules.use_v0 = v0;
-    if (rc) return rc;
+    if ((rc = wait_lane0_staging(c))) return rc;
+    if ((rc = factor_run_templated(c, nbatch, theta))) return rc;
     for (const PvjpChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
         const SizeClass &k = P.cls[ch.cls];
         const MedgpDev V = class_view(c, P, k), Vc = shifted_view(V, ch.e0);
@@ -3007,32 +2971,24 @@ int medgp_posterior_vjp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
                 hipLaunchKernelGGL(k_pvjp_cot, dim3(nb), dim3(256), 0, c->stream, Vc, ents, d_meta2, d_t2, d_ord, d_work, ch.stride, d_in, d_pts, cvec, small,
                                    Mz, loss_kind, ncot, s, wt ? 1 : 0);
             }
-            {
-                Launcher l(c, KID_PV_WGRAD);   // (Q <= 16 was checked)
-                with_q16(Q, [&](auto q, auto q0) {
-                    hipLaunchKernelGGL((k_pvjp_wgrad<decltype(q)::value, decltype(q0)::value>), dim3(wg.grid), dim3(WG_THREADS), 0, c->stream, Vc, ents, d_work,
-                                       ch.stride, d_pts + Mz, cvec, nb, wg.wg_tiles, wg.nbp);
-                });
-            }
-            const int nbins3 = 3 * Q * tri(D);
-            { Launcher l(c, KID_EPILOGUE); hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, Vc); }
+            launch_tiles(c, KID_PV_WGRAD, Q, wg, [&](auto q, auto q0, dim3 tg, dim3 tb) {
+                hipLaunchKernelGGL((k_pvjp_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, Vc, ents, d_work, ch.stride,
+                                   d_pts + Mz, cvec, nb, wg.wg_tiles, wg.nbp);
+            });
+            launch_slabsum(c, c->stream, Vc, nb);
             {
                 Launcher l(c, KID_PV_CROSS);
                 hipLaunchKernelGGL(k_pvjp_cross, dim3(pvjp_cross_grid(D), nb), dim3(256), 0, c->stream, Vc, ents, d_pseg, d_t2, d_work, ch.stride, d_pts, small, Mz);
             }
-            {
-                Launcher l(c, KID_EPILOGUE);
-                const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
-                hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, Vc, c->d_theta + row0 * H, 1, 1, c->d_nlml, g, c->d_status_out + row0, 2);
-            }
+            launch_epilogue(c, c->stream, Vc, nb, c->d_theta + row0 * H, 1, 1, c->d_nlml, g, c->d_status_out + row0, EPI_BARE);
             Launcher l(c, KID_PV_FINISH);
             hipLaunchKernelGGL(k_pvjp_finish, dim3(nb), dim3(256), 0, c->stream, Vc, small, g, builtin ? 1 : 0);
         }
     }
     HIPCHK(c, hipGetLastError());
-    std::vector<double> out(pb.out_doubles), hsmall(pb.small_doubles);
+    std::vector<double> out, hsmall(pb.small_doubles);
     std::vector<float> hmean, hvar;
-    HIPCHK(c, hipMemcpyAsync(out.data(), d_out, pb.out_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = download_directions(c, d_out, pb.out_doubles, out))) return rc;
     if (builtin) HIPCHK(c, hipMemcpyAsync(hsmall.data(), d_small, pb.small_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (M > 0 && mean) {
         hmean.resize((size_t)M); hvar.resize((size_t)M);
@@ -3041,9 +2997,7 @@ int medgp_posterior_vjp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
     }
     if ((rc = read_status(c, nbatch, status))) return rc;
     free_retired(c);
-    for (int b = 0; b < nbatch; b++)
-        for (int s = 0; s < ncot; s++)
-            std::memcpy(grad + ((size_t)b * ncot + s) * H, out.data() + ((size_t)s * nbatch + b) * H, H * sizeof(double));
+    transpose_directions(out, nbatch, ncot, H, grad);
     if (builtin)
         for (int i = 0; i < nbatch; i++) loss[P.order[i]] = hsmall[(size_t)i * (D + 2) + D];
     if (M > 0 && mean)
@@ -3090,9 +3044,9 @@ int mean_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots
     if (!slots || !theta || !b0) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if (mode != MEDGP_MEAN_MARGINAL && mode != MEDGP_MEAN_FIXED) return fail(c, MEDGP_ERR_ARG, "unknown mode %d", mode);
     if (mode == MEDGP_MEAN_MARGINAL && !lam) return fail(c, MEDGP_ERR_ARG, "lam is NULL with MEDGP_MEAN_MARGINAL");
-    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "%s supports Q <= 16 (Q = %d)", who, c->rules.Q);
-    if (!basis && c->rules.D > MEAN_MAX_D) return fail(c, MEDGP_ERR_CAPACITY, "%s supports D <= %d covariates (D = %d): the rank-D correction is one 64-column panel", who, MEAN_MAX_D, c->rules.D);
     int rc;
+    if ((rc = check_q16(c, who, nullptr))) return rc;
+    if (!basis && c->rules.D > MEAN_MAX_D) return fail(c, MEDGP_ERR_CAPACITY, "%s supports D <= %d covariates (D = %d): the rank-D correction is one 64-column panel", who, MEAN_MAX_D, c->rules.D);
     if ((rc = check_call(c, nbatch, slots))) return rc;
     int D = c->rules.D;   // the column count of H
     if (basis) {
@@ -3111,9 +3065,7 @@ int mean_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const BatchPlan &P = c->plan;
-    if (P.nwaves > 1 || !mean_fits(P.need_mat, P.need_vec, c->rules.mem_budget))
-        return fail(c, MEDGP_ERR_CAPACITY, "the call's per-entry matrices (%d of %zu MB) and panels exceed the memory budget of %zu MB (MEDGP_MEM_BUDGET_GB): split the call",
-                    MEAN_MATS, (P.need_mat * sizeof(double)) >> 20, c->rules.mem_budget >> 20);
+    if ((rc = check_one_wave(c, mean_fits(P.need_mat, P.need_vec, c->rules.mem_budget), MEAN_MATS, " and panels"))) return rc;
     mc.mb = mean_buffers(P.need_vec, nbatch, D);
     if ((rc = buf_ensure(c, BUF_MN_G, mc.mb.panel_doubles * sizeof(double)))) return rc;
     if ((rc = buf_ensure(c, BUF_MN_PH, mc.mb.panel_doubles * sizeof(double)))) return rc;
@@ -3123,12 +3075,10 @@ int mean_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots
     if ((rc = buf_ensure(c, BUF_MN_IN, mc.mb.in_doubles * sizeof(double)))) return rc;
     mc.G = buf<double>(c, BUF_MN_G); mc.PH = buf<double>(c, BUF_MN_PH); mc.Pm = buf<double>(c, BUF_MN_PM);
     mc.vec = buf<double>(c, BUF_MN_VEC); mc.small = buf<double>(c, BUF_MN_SMALL); mc.in = buf<double>(c, BUF_MN_IN);
-    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
-    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
+    if ((rc = wait_lane0_staging(c))) return rc;
     HIPCHK(c, hipMemcpyAsync(mc.in, b0, sizeof(double) * nbatch * D, hipMemcpyHostToDevice, c->stream));
     if (mode == MEDGP_MEAN_MARGINAL)
         HIPCHK(c, hipMemcpyAsync(mc.in + mean_lam_offset(nbatch, D), lam, sizeof(double) * nbatch * D, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * c->H * nbatch, hipMemcpyHostToDevice, c->stream));
     if (basis) {   // (through the pinned ring: the table is the call's own)
         if ((rc = buf_ensure(c, BUF_BS_OFF, sizeof(long long) * nbatch))) return rc;
         void *pin = nullptr;
@@ -3136,12 +3086,7 @@ int mean_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots
         for (int b = 0; b < nbatch; b++) ((long long *)pin)[b] = c->basis.slot[slots[b]].off;
         HIPCHK(c, hipMemcpyAsync(buf<long long>(c, BUF_BS_OFF), pin, sizeof(long long) * nbatch, hipMemcpyHostToDevice, c->stream));
     }
-    // the generic kernels (MEDGP_V0) keep W where P goes: these calls always take the templated ones
-    const bool v0 = c->rules.use_v0;
-    c->rules.use_v0 = false;
-    rc = run_pipeline(c, c->d_theta, 0, true, min_n, nullptr, nullptr, nullptr, false, true);
-    c->rules.use_v0 = v0;
-    if (rc) return rc;
+    if ((rc = factor_run_templated(c, nbatch, theta, min_n))) return rc;
     for (const SizeClass &k : P.cls) {
         const MedgpDev V = class_view(c, P, k);
         double *Gk = mc.G + MEAN_PW * k.off_vec;
@@ -3189,8 +3134,8 @@ void mean_scatter(const BatchPlan &P, const std::vector<double> &hs, const int32
 
 // The nlml with a constant baseline per covariate, fixed or integrated out, and its gradients (kernels_mean.h).  mean_prepare, then per
 // size class in stream order, for a gradient: k_mean_panel (PH = U G on fp64 MFMA, Pm, alpha~), k_mean_wgrad (W~ tiles -> slab, wdiag) on
-// a view whose alpha is alpha~, the nlml gradient's own k_slabsum; then k_epilogue told to report the objective k_mean_small left in
-// scal[2], which adds the priors on theta.  flag_grad = 0 runs mean_prepare and k_epilogue only.  L, U, z and alpha are never overwritten.
+// a view whose alpha is alpha~; then finish_objective_class (k_slabsum, k_epilogue: the objective k_mean_small left in scal[2], to which
+// it adds the priors on theta).  flag_grad = 0 runs mean_prepare and k_epilogue only.  L, U, z and alpha are never overwritten.
 // basis: medgp_basis_nlml_grad -- the same launches on p columns (k_mean_panel reads its column count from the view's D: it is handed
 // a view whose D is p; the gradient pass and the epilogue keep the covariate count).
 int mean_grad_impl(medgp_ctx *c, const char *who, bool basis, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0,
@@ -3202,7 +3147,6 @@ int mean_grad_impl(medgp_ctx *c, const char *who, bool basis, int nbatch, const 
     if ((rc = mean_prepare(c, who, nbatch, slots, theta, mode, b0, lam, 3, basis, mc))) return rc;
     const BatchPlan &P = c->plan;
     const int D = mc.ncol;   // the columns of H
-    const size_t H = c->H;
     for (const SizeClass &k : P.cls) {
         MedgpDev V = class_view(c, P, k);
         const int nb = k.count, nt64 = k.nbmax;
@@ -3218,29 +3162,16 @@ int mean_grad_impl(medgp_ctx *c, const char *who, bool basis, int nbatch, const 
             V.alpha = at;   // the gradient pass and what follows see alpha~
             const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
             const int k1 = mode == MEDGP_MEAN_MARGINAL ? mean_wgrad_k1(D, WG_KC) : 0;
-            {
-                Launcher l(c, KID_MN_WGRAD);   // (Q <= 16 was checked)
-                with_q16(V.Q, [&](auto q, auto q0) {
-                    hipLaunchKernelGGL((k_mean_wgrad<decltype(q)::value, decltype(q0)::value>), dim3(wg.grid), dim3(WG_THREADS), 0, c->stream, V, Pmk, k1, nb, wg.wg_tiles, wg.nbp);
-                });
-            }
-            const int nbins3 = 3 * V.Q * tri(V.D);
-            Launcher l(c, KID_EPILOGUE);
-            hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V);
+            launch_tiles(c, KID_MN_WGRAD, V.Q, wg, [&](auto q, auto q0, dim3 tg, dim3 tb) {
+                hipLaunchKernelGGL((k_mean_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, Pmk, k1, nb, wg.wg_tiles, wg.nbp);
+            });
         }
-        Launcher l(c, KID_EPILOGUE);
-        const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
-        hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, c->d_theta, flag_grad, 1, c->d_nlml, c->d_grad, c->d_status_out, 1);
+        finish_objective_class(c, V, nb, flag_grad);
     }
     HIPCHK(c, hipGetLastError());
     std::vector<double> hs(mc.mb.small_doubles);
     std::vector<int32_t> st(nbatch);
-    if (nlml) HIPCHK(c, hipMemcpyAsync(nlml, c->d_nlml, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    if (flag_grad && grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * H, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(st.data(), c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hs.data(), mc.small, mc.mb.small_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_retired(c);
+    if ((rc = download_objective(c, nbatch, flag_grad, nlml, grad, st.data(), hs.data(), mc.small, mc.mb.small_doubles * sizeof(double)))) return rc;
     mean_scatter(P, hs, st.data(), nbatch, D, dmean, beta, beta_cov);
     if (status) std::memcpy(status, st.data(), sizeof(int32_t) * nbatch);
     return MEDGP_OK;
@@ -3433,7 +3364,7 @@ int medgp_set_basis(medgp_ctx *c, int nslots, const int32_t *slots, int p, const
 // k_fc_scan (running sums of U diag(z), in place), k_fc_qm (Qm into the dead Kmat block).  T and Qm have their rows at the positions of
 // the GROUPED order, so the gradient body runs against the grouped patient copy: once every class has stored its operands, bslot is
 // pointed at the grouped slots, and per class k_fc_tables redoes cos / sin for that copy, k_fc_wgrad forms the W_fc tiles -> slab,
-// wdiag, and the nlml gradient's own k_slabsum and k_epilogue finish, the latter told to report J instead of the nlml.
+// wdiag, and finish_objective_class (k_slabsum, k_epilogue) ends the class.
 // flag_grad = 0 runs k_fc_vec and k_epilogue only.  The cached batch selection is dropped at the end: the next call uploads its own
 // bslot, and medgp_get_factor is refused (L and U are overwritten).
 int medgp_forecast_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets, const int32_t *prefix,
@@ -3442,8 +3373,8 @@ int medgp_forecast_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const do
     if (!slots || !theta || !obj) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
     if (flag_grad && !grad) return fail(c, MEDGP_ERR_ARG, "grad is NULL with flag_grad set");
-    if (c->rules.Q > 16) return fail(c, MEDGP_ERR_ARG, "medgp_forecast_grad supports Q <= 16 (Q = %d): the generic gradient route keeps W in the buffer that holds Qm here", c->rules.Q);
     int rc;
+    if ((rc = check_q16(c, "medgp_forecast_grad", "the generic gradient route keeps W in the buffer that holds Qm here"))) return rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     std::vector<int> hn(nbatch);
     for (int b = 0; b < nbatch; b++) hn[b] = c->h_n[slots[b]];
@@ -3472,14 +3403,8 @@ int medgp_forecast_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const do
     if ((rc = upload_table(c, BUF_FC_TAB, htab))) return rc;
     double *gvec = buf<double>(c, BUF_GVEC), *tmat = buf<double>(c, BUF_FC_T);
     const int *dtab = buf<int>(c, BUF_FC_TAB);
-    const size_t H = c->H;
-    // (this call shares lane 0's result staging: a download of that lane still in flight on the copy stream must have read it first)
-    if (c->lane_pending[0] && c->ev_lane[0]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane[0], 0));
-    // the generic kernels (MEDGP_V0) keep W where Qm goes: this call always takes the templated ones
-    const bool v0 = c->rules.use_v0;
-    c->rules.use_v0 = false;
-    rc = factor_run(c, nbatch, theta, true, false);
-    c->rules.use_v0 = v0;
+    if ((rc = wait_lane0_staging(c))) return rc;
+    rc = factor_run_templated(c, nbatch, theta);
     // whatever happens from here on, the next call selects its batch afresh and no factor is on offer
     c->last_nbatch = 0;
     c->last_has_inverse = false;
@@ -3513,28 +3438,14 @@ int medgp_forecast_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const do
             const double *Tm = tmat + k.off_mat;
             if (switched) { Launcher l(c, KID_FC_TABLES); hipLaunchKernelGGL(k_fc_tables, dim3(nb, (V.Q * V.ldn + PREP_CHUNK - 1) / PREP_CHUNK), dim3(256), 0, c->stream, V); }
             const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, nt64);
-            const dim3 tg(wg.grid), tb(WG_THREADS);
-            {
-                Launcher l(c, KID_FC_WGRAD);   // (Q <= 16 was checked)
-                with_q16(V.Q, [&](auto q, auto q0) {
-                    hipLaunchKernelGGL((k_fc_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, Tm, tab, nb, wg.wg_tiles, wg.nbp);
-                });
-            }
-            const int nbins3 = 3 * V.Q * tri(V.D);
-            Launcher l(c, KID_EPILOGUE);
-            hipLaunchKernelGGL(k_slabsum, dim3(nb, (nbins3 + 255) / 256), dim3(256), 0, c->stream, V);
+            launch_tiles(c, KID_FC_WGRAD, V.Q, wg, [&](auto q, auto q0, dim3 tg, dim3 tb) {
+                hipLaunchKernelGGL((k_fc_wgrad<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, c->stream, V, Tm, tab, nb, wg.wg_tiles, wg.nbp);
+            });
         }
-        Launcher l(c, KID_EPILOGUE);
-        const int nparts = (2 * nb >= c->rules.num_cu) ? 1 : std::min(MEDGP_EPI_PARTS, (V.H + 255) / 256);
-        hipLaunchKernelGGL(k_epilogue, dim3(nb, nparts), dim3(256), 0, c->stream, V, c->d_theta, flag_grad, 1, c->d_nlml, c->d_grad, c->d_status_out, 1);
+        finish_objective_class(c, V, nb, flag_grad);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(obj, c->d_nlml, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    if (flag_grad) HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * nbatch * H, hipMemcpyDeviceToHost, c->stream));
-    if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_status_out, sizeof(int32_t) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_retired(c);
-    return MEDGP_OK;
+    return download_objective(c, nbatch, flag_grad, obj, grad, status);
 }
 
 #ifdef MEDGP_STAMPS
