@@ -1008,38 +1008,52 @@ class Context:
         c_meanfunc_constMO); else beta_d ~ N(b0_d, 1 / lam_d) is integrated out (lam_d = 0: flat).  b0, lam: [D] for every patient or
         [nbatch, D].  Returns dict(nlml [nbatch], grad [nbatch, H] or None, dmean [nbatch, D] = d nlml / d b0, beta [nbatch, D],
         beta_cov [nbatch, D, D], status [nbatch]); a failed or improper patient's rows are NaN."""
+        return self._fe_nlml_grad(self._lib.medgp_mean_nlml_grad, "dmean", False, slots, theta, b0, lam, fixed, flag_grad)
+
+    def _fe_nlml_grad(self, fn, dkey, basis, slots, theta, b0, lam, fixed, flag_grad):
+        """mean_nlml_grad and basis_nlml_grad: fn the C entry point, dkey the result's key of d nlml / d b0; basis: the column count
+        is the p of b0 and lam, not D"""
         slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
         nb = slots.shape[0]
         theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
-        mode, b0, lam = self._mean_args(nb, b0, lam, fixed)
+        mode, b0, lam = self._mean_args(nb, b0, lam, fixed, self._basis_cols(b0, lam, nb) if basis else None)
         D = b0.shape[1]
         nlml, grad = np.empty(nb), (np.empty((nb, self.H)) if flag_grad else None)
-        dmean, beta, cov = np.empty((nb, D)), np.empty((nb, D)), np.empty((nb, D, D))
+        db0, beta, cov = np.empty((nb, D)), np.empty((nb, D)), np.empty((nb, D, D))
         st = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_mean_nlml_grad(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), mode, _ptr(b0, C.c_double),
-                                                 _ptr(lam, C.c_double), int(bool(flag_grad)), _ptr(nlml, C.c_double), _ptr(grad, C.c_double),
-                                                 _ptr(dmean, C.c_double), _ptr(beta, C.c_double), _ptr(cov, C.c_double), _ptr(st, C.c_int32)))
-        return dict(nlml=nlml, grad=grad, dmean=dmean, beta=beta, beta_cov=cov, status=st)
+        self._chk(fn(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), mode, _ptr(b0, C.c_double), _ptr(lam, C.c_double),
+                     int(bool(flag_grad)), _ptr(nlml, C.c_double), _ptr(grad, C.c_double), _ptr(db0, C.c_double), _ptr(beta, C.c_double),
+                     _ptr(cov, C.c_double), _ptr(st, C.c_int32)))
+        return {"nlml": nlml, "grad": grad, dkey: db0, "beta": beta, "beta_cov": cov, "status": st}
 
     def mean_posterior(self, slots, theta, meta2_list, t2_list, b0, lam=None, fixed=False):
         """medgp_mean_posterior_batch: the posterior at test points under the baseline model of mean_nlml_grad, float64.
         slots, theta, meta2_list, t2_list as posterior().  Returns ([(mean[m], var[m]) per patient], beta [nbatch, D], status)."""
+        return self._fe_posterior(self._lib.medgp_mean_posterior_batch, False, slots, theta, meta2_list, t2_list, None, b0, lam, fixed)
+
+    def _fe_posterior(self, fn, basis, slots, theta, meta2_list, t2_list, h2_list, b0, lam, fixed):
+        """mean_posterior and basis_posterior: fn the C entry point; basis: the column count is the p of b0 and lam, not D, and the
+        points' rows h2 ([M, p], from h2_list) go in behind t2"""
         slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
         nb = slots.shape[0]
-        mode, b0, lam = self._mean_args(nb, b0, lam, fixed)
+        mode, b0, lam = self._mean_args(nb, b0, lam, fixed, self._basis_cols(b0, lam, nb) if basis else None)
+        p = b0.shape[1]
+        if basis and len(h2_list) != nb:
+            raise ValueError(f"{len(h2_list)} basis arrays for {nb} patients")
+        hs = [np.asarray(h, dtype=np.float64).reshape(x.shape[0], p) for h, x in zip(h2_list, ts)] if basis else None
         cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
         offsets = np.zeros(nb + 1, dtype=np.int64)
         offsets[1:] = np.cumsum(cnt)
         M = int(offsets[-1])
         t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
         m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+        h2 = [np.ascontiguousarray(np.concatenate(hs, axis=0) if M else np.zeros((1, p)))] if basis else []
         mean, var = np.empty(max(M, 1)), np.empty(max(M, 1))
         beta = np.empty(b0.shape)
         st = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_mean_posterior_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), mode, _ptr(b0, C.c_double),
-                                                       _ptr(lam, C.c_double), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32),
-                                                       _ptr(t2, C.c_float), _ptr(mean, C.c_double), _ptr(var, C.c_double), _ptr(beta, C.c_double),
-                                                       _ptr(st, C.c_int32)))
+        self._chk(fn(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), mode, _ptr(b0, C.c_double), _ptr(lam, C.c_double),
+                     offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float), *[_ptr(h, C.c_double) for h in h2],
+                     _ptr(mean, C.c_double), _ptr(var, C.c_double), _ptr(beta, C.c_double), _ptr(st, C.c_int32)))
         out = [(mean[int(offsets[b]):int(offsets[b + 1])].copy(), var[int(offsets[b]):int(offsets[b + 1])].copy()) for b in range(nb)]
         return out, beta, st
 
@@ -1078,47 +1092,14 @@ class Context:
         beta_c ~ N(b0_c, 1 / lam_c) is integrated out (lam_c = 0: flat).  b0, lam: [p] for every patient or [nbatch, p].  Returns
         dict(nlml [nbatch], grad [nbatch, H] or None, dbeta [nbatch, p] = d nlml / d b0, beta [nbatch, p], beta_cov [nbatch, p, p],
         status [nbatch]); a failed patient's rows (a singular A among them) are NaN."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
-        nb = slots.shape[0]
-        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
-        mode, b0, lam = self._mean_args(nb, b0, lam, fixed, self._basis_cols(b0, lam, nb))
-        p = b0.shape[1]
-        nlml, grad = np.empty(nb), (np.empty((nb, self.H)) if flag_grad else None)
-        dbeta, beta, cov = np.empty((nb, p)), np.empty((nb, p)), np.empty((nb, p, p))
-        st = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_basis_nlml_grad(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), mode, _ptr(b0, C.c_double),
-                                                  _ptr(lam, C.c_double), int(bool(flag_grad)), _ptr(nlml, C.c_double), _ptr(grad, C.c_double),
-                                                  _ptr(dbeta, C.c_double), _ptr(beta, C.c_double), _ptr(cov, C.c_double), _ptr(st, C.c_int32)))
-        return dict(nlml=nlml, grad=grad, dbeta=dbeta, beta=beta, beta_cov=cov, status=st)
+        return self._fe_nlml_grad(self._lib.medgp_basis_nlml_grad, "dbeta", True, slots, theta, b0, lam, fixed, flag_grad)
 
     def basis_posterior(self, slots, theta, meta2_list, t2_list, h2_list, b0, lam=None, fixed=False):
         """medgp_basis_posterior_batch: the posterior at test points under the model of basis_nlml_grad, float64.  slots, theta,
         meta2_list, t2_list as posterior(); h2_list: one [m, p] array of basis rows per patient (the recipe of the observations'
         basis at the test points: medgp_amd.basis.Design.design(meta2, t2)).  Returns ([(mean[m], var[m]) per patient],
         beta [nbatch, p], status)."""
-        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
-        nb = slots.shape[0]
-        mode, b0, lam = self._mean_args(nb, b0, lam, fixed, self._basis_cols(b0, lam, nb))
-        p = b0.shape[1]
-        if len(h2_list) != nb:
-            raise ValueError(f"{len(h2_list)} basis arrays for {nb} patients")
-        hs = [np.asarray(h, dtype=np.float64).reshape(x.shape[0], p) for h, x in zip(h2_list, ts)]
-        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
-        offsets = np.zeros(nb + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum(cnt)
-        M = int(offsets[-1])
-        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
-        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
-        h2 = np.ascontiguousarray(np.concatenate(hs, axis=0) if M else np.zeros((1, p)))
-        mean, var = np.empty(max(M, 1)), np.empty(max(M, 1))
-        beta = np.empty(b0.shape)
-        st = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_basis_posterior_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), mode, _ptr(b0, C.c_double),
-                                                        _ptr(lam, C.c_double), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32),
-                                                        _ptr(t2, C.c_float), _ptr(h2, C.c_double), _ptr(mean, C.c_double), _ptr(var, C.c_double),
-                                                        _ptr(beta, C.c_double), _ptr(st, C.c_int32)))
-        out = [(mean[int(offsets[b]):int(offsets[b + 1])].copy(), var[int(offsets[b]):int(offsets[b + 1])].copy()) for b in range(nb)]
-        return out, beta, st
+        return self._fe_posterior(self._lib.medgp_basis_posterior_batch, True, slots, theta, meta2_list, t2_list, h2_list, b0, lam, fixed)
 
     def forecast_grad(self, slots, theta, prefixes=None, flag_grad=1):
         """medgp_forecast_grad: the negative forecast score J = - sum_i lpd_i (plus the prior term, as nlml_grad) and its gradient in

@@ -17,7 +17,8 @@
 //                 in order by one thread per (row, covariate); zeros on the padding rows and beyond column D
 //   k_mean_small  one workgroup per entry: w, c, A and its Cholesky factor in LDS (packed lower triangles), Ti = chol(A)^-1, delta,
 //                 beta^, A^-1, dmean, quad and the objective (-> scal[2], where k_epilogue's supplied-objective mode reads it).  A
-//                 covariate without observations under the flat prior, or a failed pivot of A: status -1
+//                 covariate without observations under the flat prior, or a failed pivot of A: status -1.  The program is
+//                 fe_small_body, shared with k_basis_small (kernels_basis.h: any H with p <= 64 columns) behind a column policy
 //   k_mean_panel  one workgroup per 64 rows: PH = U G on fp64 MFMA (k from the diagonal block on), then per row Pm = PH Ti^T and
 //                 alpha~ = alpha - PH beta^, terms in order
 //   k_mean_wgrad  k_wgrad's prologue and phase 1 on U, the accumulators continued through pv_phase1 over the one Pm panel with the
@@ -25,7 +26,8 @@
 //                 alpha~; diag(W~) leaves through wdiag.  W~ never reaches HBM.
 //   k_slabsum, k_epilogue (kernels_core.h, unchanged; epi_mode = EPI_OBJECTIVE: the priors are added to the objective in scal[2])
 //   k_mean_post   behind the unchanged k_pjvp_solve (V = L^-1 K* per tile of 64 points): the D x 64 tile G^T V on fp64 MFMA,
-//                 r_j = e_{m*_j} - G^T V_j, mean_j = V_j^T z + r_j^T beta^, var_j = k** - V_j^T V_j + sigma^2 + |Ti r_j|^2 in fp64
+//                 r_j = e_{m*_j} - G^T V_j, mean_j = V_j^T z + r_j^T beta^, var_j = k** - V_j^T V_j + sigma^2 + |Ti r_j|^2 in fp64.  The
+//                 program is fe_post_body, shared with k_basis_post behind the policy that gives a point's basis row
 // No atomics; every sum in a fixed order over operands of the entry alone: an entry's bits depend neither on its batch-mates, nor on
 // its position, the batch size or the launch chunk (with the route pinned, as everywhere); a point's neither on the other points nor
 // on the tile column it lands in.
@@ -56,21 +58,28 @@ __global__ void __launch_bounds__(256) k_mean_g(MedgpDev L, double *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------
-// grid = the class's entries.  in = [b0 | lam] of the CALL in the caller's entry order (nbatch_call rows of D each), wvec and small:
-// the class's part of the call's buffers (mean_tables.h).
+// The small step of the mean AND the basis calls (k_mean_small, k_basis_small: kernels_basis.h), one workgroup per entry.  D: the column
+// count of H, an argument (the view's D stays the covariate count).  in = [b0 | lam] of the CALL in the caller's entry order
+// (nbatch_call rows of D each), wvec and small: the class's part of the call's buffers (mean_tables.h with D columns).  The policy C:
+//   row0(d)  the row at which the sums of c and A over column d start (it decides the four row classes of c, so it decides bits)
+//   IMPROPER, improper(d, lam)  whether a column can be undetermined before any algebra (decided behind one __syncthreads_or)
+//   SCALED_PIVOT, pivot_floor(d0, j)  pivot j of A fails when it is NaN or not above the floor; d0: the diagonal of A before the
+//            factorisation, kept (s_d0) only where the floor depends on it
+// (no __restrict__ on the two bodies: inlined, the pointers are the kernels' own restrict arguments)
 // ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_mean_small(MedgpDev L, const double *__restrict__ G, const double *__restrict__ in, int nbatch_call,
-                                                    int mode, double *__restrict__ wvec, double *__restrict__ small) {
+template <class C>
+__device__ __forceinline__ void fe_small_body(const MedgpDev &L, const C cols, const int D, const double *G, const double *in, int nbatch_call,
+                                              int mode, double *wvec, double *small) {
     constexpr int TRI = MEAN_MAX_D * (MEAN_MAX_D + 1) / 2;
     __shared__ double Ap[TRI], Tp[TRI];
     __shared__ double s_b0[MEAN_MAX_D], s_lam[MEAN_MAX_D], s_c[MEAN_MAX_D], s_u[MEAN_MAX_D], s_dl[MEAN_MAX_D];
+    __shared__ double s_d0[C::SCALED_PIVOT ? MEAN_MAX_D : 1];
     __shared__ double red[256];
     __shared__ int s_fail;
     const int b = blockIdx.x, tid = threadIdx.x;
     if (L.status[b] < 0) return;
-    const int slot = L.bslot[b], n = L.pn[slot], ld = L.ldn, D = L.D, npad = medgp_roundup(n, 64);
+    const int slot = L.bslot[b], n = L.pn[slot], ld = L.ldn, npad = medgp_roundup(n, 64);
     const int pos = L.bpos ? L.bpos[b] : b;   // the caller's row of this entry
-    const int *seg = L.pseg + (size_t)slot * (D + 1);
     const bool marginal = mode == MEDGP_MEAN_MARGINAL;
     const double *z = L.z + (size_t)b * ld;
     double *wv = wvec + mean_vec_at(b, ld, 0);
@@ -80,14 +89,18 @@ __global__ void __launch_bounds__(256) k_mean_small(MedgpDev L, const double *__
         const double lam = marginal ? in[(size_t)nbatch_call * D + (size_t)pos * D + d] : 0.0;
         s_b0[d] = in[(size_t)pos * D + d];
         s_lam[d] = lam;
-        if (marginal && lam == 0.0 && seg[d + 1] == seg[d]) bad = 1;   // improper: nothing determines beta_d
+        if constexpr (C::IMPROPER)
+            if (marginal && cols.improper(d, lam)) bad = 1;   // nothing determines beta_d
     }
     if (tid == 0) s_fail = 0;
-    if (__syncthreads_or(bad)) {
-        if (tid == 0) L.status[b] = -1;
-        return;
-    }
-    // w = z - G b0, covariates in order
+    if constexpr (C::IMPROPER) {
+        if (__syncthreads_or(bad)) {
+            if (tid == 0) L.status[b] = -1;
+            return;
+        }
+    } else
+        __syncthreads();
+    // w = z - G b0, columns in order
     for (int i = tid; i < npad; i += 256) {
         double s = 0.0;
         if (i < n) {
@@ -97,12 +110,12 @@ __global__ void __launch_bounds__(256) k_mean_small(MedgpDev L, const double *__
         wv[i] = s;
     }
     __syncthreads();
-    // c = G^T w: four row classes per covariate, added in a fixed order (column d of G is zero above row seg[d])
+    // c = G^T w: four row classes per column, added in a fixed order
     {
         const int d = tid & 63, part = tid >> 6;
         double s = 0.0;
         if (d < D)
-            for (int i = seg[d] + part; i < n; i += 4) s += G[mean_panel_at(b, ld, i, d)] * wv[i];
+            for (int i = cols.row0(d) + part; i < n; i += 4) s += G[mean_panel_at(b, ld, i, d)] * wv[i];
         red[tid] = s;
         __syncthreads();
         if (tid < D) s_c[tid] = ((red[tid] + red[64 + tid]) + red[128 + tid]) + red[192 + tid];
@@ -115,15 +128,17 @@ __global__ void __launch_bounds__(256) k_mean_small(MedgpDev L, const double *__
             int d, e;
             tile_decode(idx, d, e);
             double s = 0.0;
-            for (int i = seg[d]; i < n; i++) s += G[mean_panel_at(b, ld, i, d)] * G[mean_panel_at(b, ld, i, e)];
+            for (int i = cols.row0(d); i < n; i++) s += G[mean_panel_at(b, ld, i, d)] * G[mean_panel_at(b, ld, i, e)];
             Ap[mean_tri_at(d, e)] = (d == e) ? s_lam[d] + s : s;
+            if constexpr (C::SCALED_PIVOT)
+                if (d == e) s_d0[d] = s_lam[d] + s;
         }
         __syncthreads();
-        // right-looking Cholesky in place (LAPACK's failure rule: a pivot <= 0 or NaN)
+        // right-looking Cholesky in place; a pivot fails when it is NaN or not above the policy's floor
         for (int j = 0; j < D; j++) {
             if (tid == 0) {
                 const double piv = Ap[mean_tri_at(j, j)];
-                if (!(piv > 0.0)) s_fail = 1;
+                if (!(piv > cols.pivot_floor(s_d0, j))) s_fail = 1;
                 Ap[mean_tri_at(j, j)] = sqrt(piv);
             }
             __syncthreads();
@@ -218,6 +233,21 @@ __global__ void __launch_bounds__(256) k_mean_small(MedgpDev L, const double *__
     }
 }
 
+// the indicator columns: column d of G is zero above row seg[d]; a covariate without observations under the flat prior is improper;
+// LAPACK's failure rule (a pivot <= 0 or NaN)
+struct MeanSmallCols {
+    static constexpr bool IMPROPER = true, SCALED_PIVOT = false;
+    const int *seg;   // the entry's D + 1 segment starts
+    __device__ __forceinline__ int row0(int d) const { return seg[d]; }
+    __device__ __forceinline__ bool improper(int d, double lam) const { return lam == 0.0 && seg[d + 1] == seg[d]; }
+    __device__ __forceinline__ double pivot_floor(const double *, int) const { return 0.0; }
+};
+// grid = the class's entries
+__global__ void __launch_bounds__(256) k_mean_small(MedgpDev L, const double *__restrict__ G, const double *__restrict__ in, int nbatch_call,
+                                                    int mode, double *__restrict__ wvec, double *__restrict__ small) {
+    fe_small_body(L, MeanSmallCols{L.pseg + (size_t)L.bslot[blockIdx.x] * (L.D + 1)}, L.D, G, in, nbatch_call, mode, wvec, small);
+}
+
 // ------------------------------------------------------------------------------------------
 // grid = (64-row blocks of the class's largest entry, entries); wave w owns the rows 16 w .. of the block, all column tiles below D.
 // MFMA operand layout as WG_CHUNK_MFMA (kernels_wgrad.h): lane (li, g) gives A[row li][k g] and B[k g][col li], accumulator element r is
@@ -304,13 +334,15 @@ __global__ void __launch_bounds__(WG_THREADS, mean_wgrad_minwaves(QT)) k_mean_wg
 }
 
 // ------------------------------------------------------------------------------------------
-// grid = the chunk's tiles (k_pjvp_solve of the same chunk left V behind the first panel of every tile's work rows).  Wave w owns the
-// rows d = 16 w .. of the D x 64 tile G^T V; mean / var: fp64, the call's point order.
+// The posterior step of the mean AND the basis calls (k_mean_post, k_basis_post: kernels_basis.h), one workgroup per tile of the chunk
+// (k_pjvp_solve of the same chunk left V behind the first panel of every tile's work rows).  ncol: the column count of H, an
+// argument -- the view's D stays the covariate count, which k** and the noise line need.  Wave w owns the rows d = 16 w .. of the
+// ncol x 64 tile G^T V; mean / var: fp64, the call's point order.  The policy's h(pt, m2, d): entry d of the basis row of point pt.
 // ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_mean_post(MedgpDev L, const PostTile *__restrict__ tiles, const int *__restrict__ meta2,
-                                                   const double *__restrict__ work, size_t work_stride, const double *__restrict__ G,
-                                                   const double *__restrict__ small, int mode, double *__restrict__ mean,
-                                                   double *__restrict__ var) {
+template <class C>
+__device__ __forceinline__ void fe_post_body(const MedgpDev &L, const C cols, const int ncol, const PostTile *tiles, const int *meta2,
+                                             const double *work, size_t work_stride, const double *G, const double *small, int mode,
+                                             double *mean, double *var) {
     __shared__ double Cs[64][65];
     __shared__ double part[2][4][64];
     const PostTile T = tiles[blockIdx.x];
@@ -324,11 +356,11 @@ __global__ void __launch_bounds__(256) k_mean_post(MedgpDev L, const PostTile *_
     const double *hyp = L.hyp + (size_t)b * L.hyp_stride, *B = hyp + hyp_off_B(L);
     const double *z = L.z + (size_t)b * ld;
     const double *Vf = work + (size_t)blockIdx.x * work_stride + (size_t)ld * 64;
-    const double *sm = small + (size_t)b * mean_small_stride(D);
+    const double *sm = small + (size_t)b * mean_small_stride(ncol);
     v4d acc[4];
 #pragma unroll
     for (int cs = 0; cs < 4; cs++) acc[cs] = (v4d){0.0, 0.0, 0.0, 0.0};
-    if (16 * w < D)   // wave-uniform
+    if (16 * w < ncol)   // wave-uniform
         for (int k = 0; k < npad; k += 4) {
             const int kk = k + g;
             const double a = G[mean_panel_at(b, ld, kk, 16 * w + li)];
@@ -353,22 +385,35 @@ __global__ void __launch_bounds__(256) k_mean_post(MedgpDev L, const PostTile *_
     }
     __syncthreads();
     if (tid < T.cnt) {
-        const size_t p = (size_t)T.p0 + tid;
-        const int m2 = meta2[p];
+        const size_t pt = (size_t)T.p0 + tid;
+        const int m2 = meta2[pt];
         const double mean0 = ((part[0][0][tid] + part[0][1][tid]) + part[0][2][tid]) + part[0][3][tid];
         const double vv = ((part[1][0][tid] + part[1][1][tid]) + part[1][2][tid]) + part[1][3][tid];
         double kss = 0.0;
         for (int q = 0; q < Q; q++) kss += B[(size_t)q * D * D + m2 * D + m2];
         const double var0 = (kss - vv) + hyp[m2];
         double dm = 0.0, extra = 0.0;
-        for (int d = 0; d < D; d++) dm += (((d == m2) ? 1.0 : 0.0) - Cs[d][tid]) * sm[mean_off_beta(D) + d];
+        for (int d = 0; d < ncol; d++) dm += (cols.h(pt, m2, d) - Cs[d][tid]) * sm[mean_off_beta(ncol) + d];
         if (mode == MEDGP_MEAN_MARGINAL)
-            for (int k = 0; k < D; k++) {
+            for (int k = 0; k < ncol; k++) {
                 double u = 0.0;
-                for (int e = 0; e <= k; e++) u += sm[mean_off_ti(D) + (size_t)k * D + e] * (((e == m2) ? 1.0 : 0.0) - Cs[e][tid]);
+                for (int e = 0; e <= k; e++) u += sm[mean_off_ti(ncol) + (size_t)k * ncol + e] * (cols.h(pt, m2, e) - Cs[e][tid]);
                 extra += u * u;
             }
-        mean[p] = mean0 + dm;
-        var[p] = var0 + extra;
+        mean[pt] = mean0 + dm;
+        var[pt] = var0 + extra;
     }
 }
+
+// the indicator row e_{m2}
+struct MeanPostRow {
+    __device__ __forceinline__ double h(size_t, int m2, int d) const { return (d == m2) ? 1.0 : 0.0; }
+};
+// grid = the chunk's tiles
+__global__ void __launch_bounds__(256) k_mean_post(MedgpDev L, const PostTile *__restrict__ tiles, const int *__restrict__ meta2,
+                                                   const double *__restrict__ work, size_t work_stride, const double *__restrict__ G,
+                                                   const double *__restrict__ small, int mode, double *__restrict__ mean,
+                                                   double *__restrict__ var) {
+    fe_post_body(L, MeanPostRow{}, L.D, tiles, meta2, work, work_stride, G, small, mode, mean, var);
+}
+

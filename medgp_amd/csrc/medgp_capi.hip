@@ -3090,27 +3090,24 @@ int mean_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots
     for (const SizeClass &k : P.cls) {
         const MedgpDev V = class_view(c, P, k);
         double *Gk = mc.G + MEAN_PW * k.off_vec;
+        double *wk = mc.vec + k.off_vec, *sk = mc.small + (size_t)k.b0 * mean_small_stride(D);
         if (basis) {
-            {
-                Launcher l(c, KID_BS_G);
-                const dim3 grid(basis_g_grid(k.nbmax), k.count);
-                const long long *hoff = buf<long long>(c, BUF_BS_OFF);
-                switch ((D + 15) / 16) {   // the column tiles of the panel that carry columns
-                case 1: hipLaunchKernelGGL(k_basis_g<1>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
-                case 2: hipLaunchKernelGGL(k_basis_g<2>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
-                case 3: hipLaunchKernelGGL(k_basis_g<3>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
-                default: hipLaunchKernelGGL(k_basis_g<4>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
-                }
+            Launcher l(c, KID_BS_G);
+            const dim3 grid(basis_g_grid(k.nbmax), k.count);
+            const long long *hoff = buf<long long>(c, BUF_BS_OFF);
+            switch ((D + 15) / 16) {   // the column tiles of the panel that carry columns
+            case 1: hipLaunchKernelGGL(k_basis_g<1>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
+            case 2: hipLaunchKernelGGL(k_basis_g<2>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
+            case 3: hipLaunchKernelGGL(k_basis_g<3>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
+            default: hipLaunchKernelGGL(k_basis_g<4>, grid, dim3(256), 0, c->stream, V, c->d_basis, hoff, D, Gk); break;
             }
-            Launcher l(c, KID_BS_SMALL);
-            hipLaunchKernelGGL(k_basis_small, dim3(k.count), dim3(256), 0, c->stream, V, Gk, mc.in, nbatch, mode, D, mc.vec + k.off_vec,
-                               mc.small + (size_t)k.b0 * mean_small_stride(D));
-            continue;
+        } else {
+            Launcher l(c, KID_MN_G);
+            hipLaunchKernelGGL(k_mean_g, dim3(mean_g_grid(k.nbmax), k.count), dim3(256), 0, c->stream, V, Gk);
         }
-        { Launcher l(c, KID_MN_G); hipLaunchKernelGGL(k_mean_g, dim3(mean_g_grid(k.nbmax), k.count), dim3(256), 0, c->stream, V, Gk); }
-        Launcher l(c, KID_MN_SMALL);
-        hipLaunchKernelGGL(k_mean_small, dim3(k.count), dim3(256), 0, c->stream, V, Gk, mc.in, nbatch, mode, mc.vec + k.off_vec,
-                           mc.small + (size_t)k.b0 * mean_small_stride(D));
+        Launcher l(c, basis ? KID_BS_SMALL : KID_MN_SMALL);   // (one body, fe_small_body, behind both)
+        if (basis) hipLaunchKernelGGL(k_basis_small, dim3(k.count), dim3(256), 0, c->stream, V, Gk, mc.in, nbatch, mode, D, wk, sk);
+        else hipLaunchKernelGGL(k_mean_small, dim3(k.count), dim3(256), 0, c->stream, V, Gk, mc.in, nbatch, mode, wk, sk);
     }
     return MEDGP_OK;
 }
@@ -3232,15 +3229,10 @@ int mean_post_impl(medgp_ctx *c, const char *who, bool basis, int nbatch, const 
             hipLaunchKernelGGL(k_pjvp_solve, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK),
                                ch.stride, 0, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), (double *)nullptr, (double *)nullptr);
         }
-        if (basis) {
-            Launcher l(c, KID_BS_POST);
-            hipLaunchKernelGGL(k_basis_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_BS_H2), buf<double>(c, BUF_WORK),
-                               ch.stride, mc.G + MEAN_PW * k.off_vec, mc.small + (size_t)k.b0 * mean_small_stride(D), mode, D, d_mean, d_var);
-            continue;
-        }
-        Launcher l(c, KID_MN_POST);
-        hipLaunchKernelGGL(k_mean_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_WORK), ch.stride,
-                           mc.G + MEAN_PW * k.off_vec, mc.small + (size_t)k.b0 * mean_small_stride(D), mode, d_mean, d_var);
+        const double *Gk = mc.G + MEAN_PW * k.off_vec, *sk = mc.small + (size_t)k.b0 * mean_small_stride(D), *work = buf<double>(c, BUF_WORK);
+        Launcher l(c, basis ? KID_BS_POST : KID_MN_POST);   // (one body, fe_post_body, behind both)
+        if (basis) hipLaunchKernelGGL(k_basis_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_BS_H2), work, ch.stride, Gk, sk, mode, D, d_mean, d_var);
+        else hipLaunchKernelGGL(k_mean_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), work, ch.stride, Gk, sk, mode, d_mean, d_var);
     }
     HIPCHK(c, hipGetLastError());
     std::vector<double> hs(mc.mb.small_doubles);
