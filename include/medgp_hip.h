@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 19: medgp_posterior_vjp_batch, medgp_posterior_vjp_moments (18: medgp_posterior_jvp_batch; 17: medgp_hess_vec; 16: medgp_fisher_vec; 15: medgp_lgo_grad; 14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 22: medgp_warp_nlml_grad, medgp_warp_posterior_batch, medgp_profile_num_kernels_ext2 (21: medgp_set_basis, medgp_basis_nlml_grad, medgp_basis_posterior_batch; 20: medgp_mean_nlml_grad, medgp_mean_posterior_batch; 19: medgp_posterior_vjp_batch, medgp_posterior_vjp_moments; 18: medgp_posterior_jvp_batch; 17: medgp_hess_vec; 16: medgp_fisher_vec; 15: medgp_lgo_grad; 14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -654,6 +654,66 @@ int medgp_basis_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots
                                 const double *h2 /* [M][p]: the basis rows of the test points */,
                                 double *mean, double *var /* fp64, [M] */, double *beta /* [nbatch][p] */, int32_t *status);
 
+/* A learned OUTPUT WARP per covariate (ABI 22).  Every other call is Gaussian in the observed value: a lab value is f + noise with
+ * symmetric error.  Covariates that are bounded below with a long right tail (INR, creatinine, lactate, bilirubin, white count) are not,
+ * also after z-scoring.  A warped GP (Snelson, Rasmussen & Ghahramani 2004) sends the observations through a monotone map g_d per
+ * covariate into a space where the GP is Gaussian, and learns the map's parameters together with theta from the exact marginal
+ * likelihood.  The family is the sinh-arcsinh transform (Jones & Pewsey 2009): three parameters psi_d = (a_d, eps_d, lambda_d), the
+ * identity at psi = 0, skew (eps) and tail weight (lambda) separately, and a closed-form inverse -- so quantiles are exact.
+ * For observation i of covariate d = m_i, with delta_d = exp(lambda_d), s_i = asinh(y_i), u_i = delta_d s_i - eps_d:
+ *   z_i = g_d(y_i) = a_d + sinh(u_i),   log g'_i = lambda_d + log cosh(u_i) - 1/2 log(1 + y_i^2),
+ *   g_d^-1(z) = sinh((asinh(z - a_d) + eps_d) / delta_d)
+ * kind[d] = MEDGP_WARP_NONE (0): covariate d is not warped -- z = y exactly, log g' = 0, its three psi entries are ignored and its
+ * three dpsi entries are 0.  MEDGP_WARP_SAS (1): the map above.  kind == NULL: all SAS.  kind is [D], shared by the call's patients;
+ * psi is [nbatch][D][3], row b for patient b (SE / SM: D = 1).  theta keeps the context's H hypers (medgp_num_hyp).
+ * With K the matrix the pipeline factored (after its jitter rounds, as everywhere), P = K^-1, w = L^-1 z, alpha~ = P z (the definition
+ * is tests/warp_truth.py, in long double):
+ *   nlml[b]   = 1/2 |w|^2 + 1/2 log|K| + 1/2 n log 2 pi - sum_i log g'_i, minus the log prior of theta as medgp_nlml_grad
+ *   grad[b]   = 1/2 tr((P - alpha~ alpha~^T) dK/dtheta_h), the prior lines and the noise lines as medgp_nlml_grad
+ *   dpsi[b][d][k] = d nlml / d psi_dk = sum_{m_i = d} (alpha~_i dz_i/dpsi_k - dlog g'_i/dpsi_k), with
+ *               dz_i/d(a, eps, lambda) = (1, -cosh u_i, delta_d s_i cosh u_i),  dlog g'_i/d(a, eps, lambda) = (0, -tanh u_i, 1 + delta_d s_i tanh u_i);
+ *               a covariate without observations: 0 exactly
+ *   logjac[b] = sum_i log g'_i
+ * At psi = 0, or with every kind NONE, it is medgp_nlml_grad to rounding (another summation order: not to bits).
+ * status[b]: jitter rounds, or -1 (n <= 2 as medgp_nlml_grad, a failed factorisation, or a warped observation that is not finite --
+ * sinh overflowed; decided on the device, batch-mates are unaffected); the entry's outputs are then NaN.
+ * flag_grad = 0: nlml, logjac and dpsi alone (dpsi needs alpha~ but no gradient pass), the same bits as with flag_grad = 1.  Every
+ * output pointer may be NULL.
+ * MEDGP_ERR_ARG before any device work: a non-finite psi entry, a kind outside {0, 1}, Q > 16.  MEDGP_ERR_CAPACITY: a call whose two
+ * per-entry matrices and four vectors exceed the memory budget (no memory waves, as the baseline calls).
+ * Blocking.  Route selection, size classes and medgp_pin_route as medgp_nlml_grad; the generic kernels (MEDGP_V0) are not honoured.
+ * No atomics: with the route pinned an entry's bits depend on the patient, theta, psi and kind alone -- not on batch-mates, position,
+ * batch size or how the call is cut into launches.
+ * Accuracy: tests/test_warp_gpu.py holds every output to the fp64 budget M_WARP max(E_programs, 2^-53) of tests/warp_truth.py.
+ * NOT provided (out of scope of these two calls): the warp under the LOO, LGO and forecast objectives and in the JVP, VJP, Fisher and
+ * Hessian calls; a warp combined with a baseline or a basis in one call; options of medgp_train / medgp_test; other warp families
+ * (sums of tanh, Box-Cox); gradients of the predictions in psi.
+ * All pointers are HOST memory. */
+#define MEDGP_WARP_NONE 0
+#define MEDGP_WARP_SAS  1
+int medgp_warp_nlml_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int32_t *kind /* [D] or NULL */,
+                         const double *psi /* [nbatch][D][3] */, int flag_grad, double *nlml, double *grad /* [nbatch][H] */,
+                         double *dpsi /* [nbatch][D][3] */, double *logjac /* [nbatch] */, int32_t *status);
+/* The warped posterior at test points (m*_j, t*_j), from ONE factorisation per patient.  With V_j = L^-1 k*_j:
+ *   zmean[j] = V_j^T w,   zvar[j] = k** - V_j^T V_j + sigma^2_{m*_j}       (the posterior call's values with w in place of L^-1 y)
+ *   quant[j][k] = g^-1_{m*_j}(zmean[j] + zq[k] sqrt(zvar[j]))              zq: nq standard-normal deviates (0: the median); exact
+ *                 quantiles of the predictive distribution of the observed value, monotone in zq
+ *   lpd[j] = -1/2 log(2 pi zvar[j]) - (g(y2[j]) - zmean[j])^2 / (2 zvar[j]) + log g'(y2[j])      when y2 is given
+ * The mean and variance of the observed value have no closed form; they are formed on the host from zmean and zvar by a Gauss-Hermite
+ * rule (medgp_amd.warp.moments).  fp64 outputs in the caller's point order; offsets / meta2 / t2 as medgp_posterior_batch (meta2 may
+ * be NULL for SE / SM and is range-checked for LMC-SM; a patient without points is allowed); no n > 2 guard, as there.  kind, psi, the
+ * non-finite rule, the argument errors and the capacity rule as medgp_warp_nlml_grad; besides MEDGP_ERR_ARG for nq < 0 or nq > 64, a
+ * non-finite zq entry, offsets that do not start at 0 or decrease, t2 (or, for LMC-SM, meta2) NULL with points, zmean and zvar not both
+ * or neither NULL, quant without nq >= 1 and zq, lpd without y2.  The work rows are chunked within MEDGP_POSTERIOR_BUDGET_GB.  The
+ * points of a patient with status[b] < 0 get NaN.  Every output pointer may be NULL.
+ * A point's bits depend on the patient, theta, psi, kind and that point alone: not on the other points or their ORDER, the tile or
+ * column it lands in, the launch chunk, or -- with the route pinned -- the batch-mates.
+ * Supported range of the time stamps: |t| <= 2^14 h, as medgp_posterior_batch.  All pointers are HOST memory. */
+int medgp_warp_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int32_t *kind,
+                               const double *psi, const int64_t *offsets, const int32_t *meta2, const float *t2,
+                               const float *y2 /* [M] or NULL */, int nq, const double *zq /* [nq] */, double *zmean,
+                               double *zvar /* [M] */, double *quant /* [M][nq] */, double *lpd /* [M] */, int32_t *status);
+
 /* Rolling-origin forecasts: every test point predicted from a LEADING block of its patient's observations, all from ONE
  * factorisation per patient -- what the model says at time t from what was known before t.
  *   ref: core/gp_regression.cpp:128-214 (GP_Regression::predict), main_one_test.cpp:269-300 (the "past" training sets of the
@@ -988,6 +1048,11 @@ int medgp_profile_num_kernels_all(void);
    k_mean_wgrad, k_mean_post (ids 50 to 54; their k_slabsum, k_epilogue and k_pjvp_solve launches likewise) -- are appended behind it: ids [medgp_profile_num_kernels_all(), medgp_profile_num_kernels_ext()) are valid
    in the same way.  A caller that wants every entry walks [0, medgp_profile_num_kernels_ext()) and does not assume its length. */
 int medgp_profile_num_kernels_ext(void);
+/* medgp_profile_num_kernels_ext is pinned in turn, at the 58 entries it had when the basis calls were added.  The warp calls' k_warp_z,
+   k_warp_solve, k_warp_small, k_warp_post (ids 58 to 61; their k_wgrad, k_slabsum, k_epilogue and k_pjvp_solve launches are accounted
+   under the existing entries) are appended behind it: ids [medgp_profile_num_kernels_ext(), medgp_profile_num_kernels_ext2()) are
+   valid in the same way. */
+int medgp_profile_num_kernels_ext2(void);
 const char *medgp_profile_kernel_name(int k);
 /* synchronises, then returns accumulated milliseconds and launch count of kernel k since the
  * last medgp_profile_reset */

@@ -15,6 +15,7 @@ KERNEL_SE, KERNEL_LMC_SM, KERNEL_SM = 0, 7, 8
 PRIOR_NONE, PRIOR_CLAMP, PRIOR_NORMAL, PRIOR_LAPLACE = -1, 0, 1, 2
 FLAG_GRAD, FLAG_KEEP_FACTOR = 1, 2   # flag_grad bits (include/medgp_hip.h)
 MEAN_MARGINAL, MEAN_FIXED = 0, 1     # mode of the baseline calls (include/medgp_hip.h)
+WARP_NONE, WARP_SAS = 0, 1           # kind of a covariate in the warp calls (include/medgp_hip.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -24,7 +25,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_posterior_jvp_batch", "medgp_posterior_vjp_batch", "medgp_posterior_vjp_moments", "medgp_mean_nlml_grad", "medgp_mean_posterior_batch", "medgp_set_basis", "medgp_basis_nlml_grad", "medgp_basis_posterior_batch", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_posterior_jvp_batch", "medgp_posterior_vjp_batch", "medgp_posterior_vjp_moments", "medgp_mean_nlml_grad", "medgp_mean_posterior_batch", "medgp_set_basis", "medgp_basis_nlml_grad", "medgp_basis_posterior_batch", "medgp_warp_nlml_grad", "medgp_warp_posterior_batch", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext", "medgp_profile_num_kernels_ext2",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at", "medgp_gmm_fit",
 ]
 
@@ -114,6 +115,10 @@ def load():
     lib.medgp_basis_nlml_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, C.c_int, dp, dp, dp, dp, dp, i32p]
     lib.medgp_basis_posterior_batch.restype = C.c_int
     lib.medgp_basis_posterior_batch.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, C.POINTER(C.c_int64), i32p, fp, dp, dp, dp, dp, i32p]
+    lib.medgp_warp_nlml_grad.restype = C.c_int
+    lib.medgp_warp_nlml_grad.argtypes = [vp, C.c_int, i32p, dp, i32p, dp, C.c_int, dp, dp, dp, dp, i32p]
+    lib.medgp_warp_posterior_batch.restype = C.c_int
+    lib.medgp_warp_posterior_batch.argtypes = [vp, C.c_int, i32p, dp, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, C.c_int, dp, dp, dp, dp, dp, i32p]
     lib.medgp_posterior_vjp_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, dp, C.c_int, dp, dp, fp, fp, dp, dp, i32p]
     lib.medgp_forecast_grad.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, C.c_int, dp, dp, i32p]
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
@@ -126,6 +131,7 @@ def load():
     lib.medgp_profile_num_kernels.restype = C.c_int
     lib.medgp_profile_num_kernels_all.restype = C.c_int
     lib.medgp_profile_num_kernels_ext.restype = C.c_int
+    lib.medgp_profile_num_kernels_ext2.restype = C.c_int
     lib.medgp_profile_kernel_name.argtypes = [C.c_int]
     lib.medgp_profile_kernel_name.restype = C.c_char_p
     lib.medgp_profile_read.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_int64)]
@@ -1101,6 +1107,85 @@ class Context:
         beta [nbatch, p], status)."""
         return self._fe_posterior(self._lib.medgp_basis_posterior_batch, True, slots, theta, meta2_list, t2_list, h2_list, b0, lam, fixed)
 
+    def _warp_args(self, nb, psi, kind):
+        """psi as [nbatch, D, 3] (one [D, 3] block serves every patient), kind as int32 [D] or None = all SAS"""
+        D = self.D if self.kernel_index == KERNEL_LMC_SM else 1
+        a = np.asarray(psi, dtype=np.float64)
+        if a.size == D * 3:
+            a = np.broadcast_to(a.reshape(1, D, 3), (nb, D, 3))
+        elif a.size != nb * D * 3:
+            raise ValueError(f"psi has {a.size} values, expected {D} x 3 or {nb} x {D} x 3")
+        if kind is not None:
+            kind = np.ascontiguousarray(kind, dtype=np.int32).ravel()
+            if kind.shape[0] != D:
+                raise ValueError(f"kind has {kind.shape[0]} entries, expected {D}")
+        return D, np.ascontiguousarray(a.reshape(nb, D, 3)), kind
+
+    def warp_nlml_grad(self, slots, theta, psi, kind=None, flag_grad=True):
+        """medgp_warp_nlml_grad: the nlml of the warped GP z = g_d(y) with the sinh-arcsinh map per covariate (medgp_amd.warp), and
+        its gradients in theta and psi.  psi: [D, 3] for every patient or [nbatch, D, 3], rows (a, eps, lambda); kind: [D] of
+        WARP_NONE / WARP_SAS, None = all SAS.  Returns dict(nlml [nbatch], grad [nbatch, H] or None, dpsi [nbatch, D, 3],
+        logjac [nbatch], status [nbatch]); a failed patient's rows (a warped observation that is not finite among them) are NaN."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        nb = slots.shape[0]
+        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
+        D, psi, kind = self._warp_args(nb, psi, kind)
+        nlml, grad = np.empty(nb), (np.empty((nb, self.H)) if flag_grad else None)
+        dpsi, logjac, st = np.empty((nb, D, 3)), np.empty(nb), np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_warp_nlml_grad(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), _ptr(kind, C.c_int32),
+                                                 _ptr(psi, C.c_double), int(bool(flag_grad)), _ptr(nlml, C.c_double), _ptr(grad, C.c_double),
+                                                 _ptr(dpsi, C.c_double), _ptr(logjac, C.c_double), _ptr(st, C.c_int32)))
+        return {"nlml": nlml, "grad": grad, "dpsi": dpsi, "logjac": logjac, "status": st}
+
+    def warp_posterior(self, slots, theta, psi, meta2_list, t2_list, y2_list=None, probs=(0.025, 0.5, 0.975), kind=None, zq=None):
+        """medgp_warp_posterior_batch: the warped posterior at test points, float64.  slots, theta, meta2_list, t2_list as
+        posterior(); psi, kind as warp_nlml_grad; y2_list: the observed values at the points (one array per patient) for lpd;
+        probs: the probabilities of the quantiles (they become standard-normal deviates on the host); zq: the deviates themselves --
+        when zq is given, probs is ignored.  Returns
+        ([dict(zmean [m], zvar [m], quant [m, len(probs)], lpd [m] or None) per patient], status)."""
+        from statistics import NormalDist
+        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
+        nb = slots.shape[0]
+        D, psi, kind = self._warp_args(nb, psi, kind)
+        if zq is None:
+            probs = [float(p) for p in probs]
+            if any(not 0.0 < p < 1.0 for p in probs):
+                raise ValueError("probs lie strictly between 0 and 1")
+            nd = NormalDist()
+            zq = [0.0 if p == 0.5 else nd.inv_cdf(p) for p in probs]
+        zq = np.ascontiguousarray(zq, dtype=np.float64).ravel()
+        nq = zq.shape[0]
+        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum(cnt)
+        M = int(offsets[-1])
+        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
+        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+        y2 = None
+        if y2_list is not None:
+            if len(y2_list) != nb:
+                raise ValueError(f"{len(y2_list)} value arrays for {nb} patients")
+            ys = [np.ascontiguousarray(y, dtype=np.float32).ravel() for y in y2_list]
+            if any(y.shape[0] != x.shape[0] for y, x in zip(ys, ts)):
+                raise ValueError("y2_list does not match t2_list")
+            y2 = np.ascontiguousarray(np.concatenate(ys) if M else np.zeros(1), dtype=np.float32)
+        Mz = max(M, 1)
+        zmean, zvar = np.empty(Mz), np.empty(Mz)
+        quant = np.empty((Mz, nq)) if nq else None
+        lpd = np.empty(Mz) if y2 is not None else None
+        st = np.empty(nb, dtype=np.int32)
+        self._chk(self._lib.medgp_warp_posterior_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), _ptr(kind, C.c_int32),
+                                                       _ptr(psi, C.c_double), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32),
+                                                       _ptr(t2, C.c_float), _ptr(y2, C.c_float), nq, _ptr(zq, C.c_double) if nq else None,
+                                                       _ptr(zmean, C.c_double), _ptr(zvar, C.c_double), _ptr(quant, C.c_double),
+                                                       _ptr(lpd, C.c_double), _ptr(st, C.c_int32)))
+        out = []
+        for b in range(nb):
+            lo, hi = int(offsets[b]), int(offsets[b + 1])
+            out.append(dict(zmean=zmean[lo:hi].copy(), zvar=zvar[lo:hi].copy(), quant=None if quant is None else quant[lo:hi].copy(),
+                            lpd=None if lpd is None else lpd[lo:hi].copy()))
+        return out, st
+
     def forecast_grad(self, slots, theta, prefixes=None, flag_grad=1):
         """medgp_forecast_grad: the negative forecast score J = - sum_i lpd_i (plus the prior term, as nlml_grad) and its gradient in
         theta.  prefixes: one int array per patient, in the order the patient was uploaded: prefixes[b][i] = the number of leading
@@ -1137,16 +1222,24 @@ class Context:
         """on: bracket every launch with HIP events; only='k_cholinv': just the launches of that kernel."""
         mode = int(bool(on))
         if on and only is not None:
-            names = [self._lib.medgp_profile_kernel_name(k).decode() for k in range(self._lib.medgp_profile_num_kernels_ext())]
+            names = [self._lib.medgp_profile_kernel_name(k).decode() for k in range(self._lib.medgp_profile_num_kernels_ext2())]
             mode = 2 + names.index(only)
         self._chk(self._lib.medgp_profile_enable(self._h, mode))
+        self._profile_only = mode - 2 if mode >= 2 else None
 
     def profile_reset(self):
         self._chk(self._lib.medgp_profile_reset(self._h))
 
-    def profile_read(self):
+    def profile_read(self, all_entries=False):
+        """{kernel name: (milliseconds, launches)} of the entries [0, medgp_profile_num_kernels_ext()), the table callers compare as a
+        whole; all_entries=True: also the entries added since (the warp calls' four kernels), up to medgp_profile_num_kernels_ext2().
+        A kernel beyond the table that profile_enable(only=...) last named is returned as well: what was asked for is never left out."""
         out = {}
-        for k in range(self._lib.medgp_profile_num_kernels_ext()):
+        ids = list(range(self._lib.medgp_profile_num_kernels_ext2() if all_entries else self._lib.medgp_profile_num_kernels_ext()))
+        only = getattr(self, "_profile_only", None)
+        if only is not None and only not in ids:
+            ids.append(only)
+        for k in ids:
             ms, cnt = C.c_double(), C.c_int64()
             self._chk(self._lib.medgp_profile_read(self._h, k, C.byref(ms), C.byref(cnt)))
             out[self._lib.medgp_profile_kernel_name(k).decode()] = (ms.value, cnt.value)

@@ -30,6 +30,7 @@
 #include "kernels_posterior_vjp.h"
 #include "kernels_mean.h"
 #include "kernels_basis.h"
+#include "kernels_warp.h"
 
 #include <algorithm>
 #include <chrono>
@@ -45,8 +46,9 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_PJ_SOLVE, KID_PJ_U, KID_PJ_DIR, KID_PV_COT, KID_PV_WGRAD, KID_PV_CROSS, KID_PV_FINISH, KID_MN_G, KID_MN_SMALL, KID_MN_PANEL, KID_MN_WGRAD, KID_MN_POST, KID_BS_G, KID_BS_SMALL, KID_BS_POST, KID_COUNT };
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue", "k_pjvp_solve", "k_pjvp_u", "k_pjvp_dir", "k_pvjp_cot", "k_pvjp_wgrad", "k_pvjp_cross", "k_pvjp_finish", "k_mean_g", "k_mean_small", "k_mean_panel", "k_mean_wgrad", "k_mean_post", "k_basis_g", "k_basis_small", "k_basis_post"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_PJ_SOLVE, KID_PJ_U, KID_PJ_DIR, KID_PV_COT, KID_PV_WGRAD, KID_PV_CROSS, KID_PV_FINISH, KID_MN_G, KID_MN_SMALL, KID_MN_PANEL, KID_MN_WGRAD, KID_MN_POST, KID_BS_G, KID_BS_SMALL, KID_BS_POST, KID_WP_Z, KID_WP_SOLVE, KID_WP_SMALL, KID_WP_POST, KID_COUNT };
+constexpr int KID_EXT_COUNT = KID_BS_POST + 1;   // what medgp_profile_num_kernels_ext is pinned at; [KID_EXT_COUNT, KID_COUNT): the _ext2 entries
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue", "k_pjvp_solve", "k_pjvp_u", "k_pjvp_dir", "k_pvjp_cot", "k_pvjp_wgrad", "k_pvjp_cross", "k_pvjp_finish", "k_mean_g", "k_mean_small", "k_mean_panel", "k_mean_wgrad", "k_mean_post", "k_basis_g", "k_basis_small", "k_basis_post", "k_warp_z", "k_warp_solve", "k_warp_small", "k_warp_post"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -114,9 +116,12 @@ struct Arena {
 //   chol(A)^-1, A^-1), BUF_MN_IN [b0 | lam] in the caller's order, BUF_MN_OUT the fp64 [mean | var] of the posterior call's points
 //   medgp_basis_nlml_grad / medgp_basis_posterior_batch (basis_tables.h): the seven buffers above in the same roles with p columns;
 //   BUF_BS_OFF the offset of every entry's rows in the resident store (caller's order), BUF_BS_H2 the basis rows of the call's points
+//   medgp_warp_nlml_grad / medgp_warp_posterior_batch (warp_tables.h): BUF_WP_VEC [z | log g' | w | alpha~], each laid out like alpha,
+//   BUF_WP_SMALL the per-entry blocks (logjac, 1/2 |w|^2, dpsi), BUF_WP_IN [psi | zq] (psi in the caller's order), BUF_WP_KIND kind[D],
+//   BUF_WP_Y2 the observed values at the call's points, BUF_WP_OUT the fp64 [zmean | zvar | lpd | quant] of the posterior call's points
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_PJ_U, BUF_PJ_OUT, BUF_PV_ENT, BUF_PV_SEG, BUF_PV_ORD, BUF_PV_IN, BUF_PV_PTS, BUF_PV_VEC, BUF_PV_SMALL, BUF_PV_OUT, BUF_MN_G, BUF_MN_PH, BUF_MN_PM, BUF_MN_VEC, BUF_MN_SMALL, BUF_MN_IN, BUF_MN_OUT, BUF_BS_OFF, BUF_BS_H2, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_PJ_U, BUF_PJ_OUT, BUF_PV_ENT, BUF_PV_SEG, BUF_PV_ORD, BUF_PV_IN, BUF_PV_PTS, BUF_PV_VEC, BUF_PV_SMALL, BUF_PV_OUT, BUF_MN_G, BUF_MN_PH, BUF_MN_PM, BUF_MN_VEC, BUF_MN_SMALL, BUF_MN_IN, BUF_MN_OUT, BUF_BS_OFF, BUF_BS_H2, BUF_WP_VEC, BUF_WP_SMALL, BUF_WP_IN, BUF_WP_KIND, BUF_WP_Y2, BUF_WP_OUT, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -1001,7 +1006,7 @@ void transpose_directions(const std::vector<double> &out, int nbatch, int nvec, 
 
 extern "C" {
 
-int medgp_abi_version(void) { return 21; }
+int medgp_abi_version(void) { return 22; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -3249,9 +3254,200 @@ int mean_post_impl(medgp_ctx *c, const char *who, bool basis, int nbatch, const 
     return MEDGP_OK;
 }
 
+// What the two warp calls share (kernels_warp.h): the argument checks, the plan, the capacity rule, the call's buffers, [psi | zq] and
+// kind to the device, ONE pipeline run in the grouped order (factor, U = L^-T; min_n as the caller's family has it) and, per size class
+// in stream order, k_warp_z (z = g(y), log g'; a non-finite z: status -1), k_warp_solve (w = U^T z, alpha~ = U w) and k_warp_small
+// (1/2 |w|^2, sum log g', dpsi, the objective -> scal[2]).  M, nq: the posterior call's points and quantiles (0, 0: the objective).
+struct WarpCall {
+    WarpBuffers wb;
+    double *vec, *small, *in;
+    const int *kind;   // device, or null = all SAS
+    int D;
+    double *role(int r, size_t need_vec, size_t off_vec) const { return vec + warp_vec_offset(r, need_vec) + off_vec; }
+};
+int warp_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots, const double *theta, const int32_t *kind, const double *psi,
+                 int min_n, size_t M, int nq, const double *zq, WarpCall &wc) {
+    if (!slots || !theta || !psi) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    int rc;
+    if ((rc = check_q16(c, who, nullptr))) return rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    const int D = c->rules.D;
+    wc.D = D;
+    if (kind)
+        for (int d = 0; d < D; d++)
+            if (kind[d] != MEDGP_WARP_NONE && kind[d] != MEDGP_WARP_SAS) return fail(c, MEDGP_ERR_ARG, "kind[%d] = %d is neither MEDGP_WARP_NONE nor MEDGP_WARP_SAS", d, kind[d]);
+    for (size_t i = 0; i < (size_t)nbatch * D * WARP_NPSI; i++)
+        if (!std::isfinite(psi[i])) return fail(c, MEDGP_ERR_ARG, "psi[%zu] = %g is not finite", i, psi[i]);
+    for (int k = 0; k < nq; k++)
+        if (!std::isfinite(zq[k])) return fail(c, MEDGP_ERR_ARG, "zq[%d] = %g is not finite", k, zq[k]);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
+    const BatchPlan &P = c->plan;
+    if ((rc = check_one_wave(c, warp_fits(P.need_mat, P.need_vec, c->rules.mem_budget), WARP_MATS, " and vectors"))) return rc;
+    wc.wb = warp_buffers(P.need_vec, nbatch, D, M, nq);
+    if ((rc = buf_ensure(c, BUF_WP_VEC, wc.wb.vec_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_WP_SMALL, wc.wb.small_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_WP_IN, wc.wb.in_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_WP_KIND, sizeof(int) * D))) return rc;
+    wc.vec = buf<double>(c, BUF_WP_VEC); wc.small = buf<double>(c, BUF_WP_SMALL); wc.in = buf<double>(c, BUF_WP_IN);
+    wc.kind = kind ? buf<int>(c, BUF_WP_KIND) : nullptr;
+    if ((rc = wait_lane0_staging(c))) return rc;
+    HIPCHK(c, hipMemcpyAsync(wc.in, psi, sizeof(double) * nbatch * D * WARP_NPSI, hipMemcpyHostToDevice, c->stream));
+    if (nq > 0) HIPCHK(c, hipMemcpyAsync(wc.in + warp_in_zq(nbatch, D), zq, sizeof(double) * nq, hipMemcpyHostToDevice, c->stream));
+    if (kind) HIPCHK(c, hipMemcpyAsync(buf<int>(c, BUF_WP_KIND), kind, sizeof(int) * D, hipMemcpyHostToDevice, c->stream));
+    if ((rc = factor_run_templated(c, nbatch, theta, min_n))) return rc;
+    for (const SizeClass &k : P.cls) {
+        const MedgpDev V = class_view(c, P, k);
+        double *zk = wc.role(WARP_VEC_Z, P.need_vec, k.off_vec), *ljk = wc.role(WARP_VEC_LJ, P.need_vec, k.off_vec);
+        double *wk = wc.role(WARP_VEC_W, P.need_vec, k.off_vec), *atk = wc.role(WARP_VEC_AT, P.need_vec, k.off_vec);
+        {
+            Launcher l(c, KID_WP_Z);
+            hipLaunchKernelGGL(k_warp_z, dim3((k.ld + 255) / 256, k.count), dim3(256), 0, c->stream, V, wc.kind, wc.in, zk, ljk);
+        }
+        {
+            Launcher l(c, KID_WP_SOLVE);
+            hipLaunchKernelGGL(k_warp_solve, dim3(k.count), dim3(WARP_SOLVE_THREADS), 0, c->stream, V, zk, wk, atk);
+        }
+        Launcher l(c, KID_WP_SMALL);
+        hipLaunchKernelGGL(k_warp_small, dim3(k.count), dim3(256), 0, c->stream, V, wc.kind, wc.in, ljk, wk, atk, wc.small + (size_t)k.b0 * warp_small_stride(D));
+    }
+    return MEDGP_OK;
+}
+
+// The warped nlml and its gradients in theta and psi (kernels_warp.h).  warp_prepare, then per size class in stream order, for a
+// gradient: the unchanged k_wgrad on a view whose alpha is alpha~ (W = P - alpha~ alpha~^T tiles -> slab, wdiag); then
+// finish_objective_class (k_slabsum, k_epilogue: the objective k_warp_small left in scal[2], to which it adds the priors on theta).
+// flag_grad = 0 runs warp_prepare and k_epilogue only.  L and U are never overwritten.
+int warp_grad_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int32_t *kind, const double *psi, int flag_grad,
+                   double *nlml, double *grad, double *dpsi, double *logjac, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
+    WarpCall wc{};
+    int rc;
+    if ((rc = warp_prepare(c, "medgp_warp_nlml_grad", nbatch, slots, theta, kind, psi, 3, 0, 0, nullptr, wc))) return rc;
+    const BatchPlan &P = c->plan;
+    const int D = wc.D;
+    for (const SizeClass &k : P.cls) {
+        MedgpDev V = class_view(c, P, k);
+        const int nb = k.count;
+        V.alpha = wc.role(WARP_VEC_AT, P.need_vec, k.off_vec);   // the gradient pass and what follows see alpha~
+        if (flag_grad) {
+            const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, k.nbmax);
+            const int pf = c->wgrad_deep >= 0 ? c->wgrad_deep : ((long)nb * wg.wg_tiles <= 16L * c->rules.num_cu ? 2 : 1);
+            launch_tiles(c, KID_WGRAD, V.Q, wg, [&](auto q, auto q0, dim3 tg, dim3 tb) {
+                constexpr int QQ = decltype(q)::value, Q0 = decltype(q0)::value;
+                if (pf >= 2) hipLaunchKernelGGL((k_wgrad<QQ, Q0, 2>), tg, tb, 0, c->stream, V, nb, wg.wg_tiles, wg.nbp);
+                else hipLaunchKernelGGL((k_wgrad<QQ, Q0, 1>), tg, tb, 0, c->stream, V, nb, wg.wg_tiles, wg.nbp);
+            });
+        }
+        finish_objective_class(c, V, nb, flag_grad);
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> hs(wc.wb.small_doubles);
+    std::vector<int32_t> st(nbatch);
+    if ((rc = download_objective(c, nbatch, flag_grad, nlml, grad, st.data(), hs.data(), wc.small, wc.wb.small_doubles * sizeof(double)))) return rc;
+    const size_t ws = warp_small_stride(D);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int i = 0; i < nbatch; i++) {   // the per-entry blocks (internal order) to the caller's rows; NaN for failed entries
+        const int b = P.order[i];
+        const double *s = hs.data() + (size_t)i * ws;
+        const bool ok = st[b] >= 0;
+        if (logjac) logjac[b] = ok ? s[warp_off_logjac()] : nan;
+        if (dpsi)
+            for (int d = 0; d < D; d++)
+                for (int k = 0; k < WARP_NPSI; k++)
+                    dpsi[warp_in_psi(b, D, d, k)] = !ok ? nan : ((kind && kind[d] == MEDGP_WARP_NONE) ? 0.0 : s[warp_off_dpsi(d, k)]);
+    }
+    if (status) std::memcpy(status, st.data(), sizeof(int32_t) * nbatch);
+    return MEDGP_OK;
+}
+
+// The warped posterior at test points (kernels_warp.h).  warp_prepare (no n > 2 guard, as medgp_posterior_batch), then per launch chunk
+// of tiles of 64 points, in stream order: the unchanged k_pjvp_solve (V = L^-1 K* behind the first panel of every tile's work rows) and
+// k_warp_post (zmean, zvar, the quantiles and lpd in fp64).  The points keep the caller's order.
+int warp_post_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int32_t *kind, const double *psi,
+                   const int64_t *offsets, const int32_t *meta2, const float *t2, const float *y2, int nq, const double *zq, double *zmean,
+                   double *zvar, double *quant, double *lpd, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    const char *who = "medgp_warp_posterior_batch";
+    if (!offsets) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    if (nbatch < 1) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d", nbatch);
+    int rc;
+    if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
+    for (int b = 0; b < nbatch; b++)
+        if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
+    const int64_t M = offsets[nbatch];
+    if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
+    if (M > 0 && !t2) return fail(c, MEDGP_ERR_ARG, "t2 is NULL");
+    if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
+    if ((zmean == nullptr) != (zvar == nullptr)) return fail(c, MEDGP_ERR_ARG, "zmean and zvar: both or neither");
+    if (nq < 0 || nq > WARP_MAX_NQ) return fail(c, MEDGP_ERR_ARG, "nq = %d outside [0, %d]", nq, WARP_MAX_NQ);
+    if (nq > 0 && !zq) return fail(c, MEDGP_ERR_ARG, "zq is NULL with nq = %d", nq);
+    if (quant && nq < 1) return fail(c, MEDGP_ERR_ARG, "quant requires nq >= 1 and zq");
+    if (lpd && !y2) return fail(c, MEDGP_ERR_ARG, "lpd requires y2");
+    std::vector<double> ht2;
+    std::vector<int> hm2;
+    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
+    WarpCall wc{};
+    if ((rc = warp_prepare(c, who, nbatch, slots, theta, kind, psi, 1, (size_t)M, nq, zq, wc))) return rc;
+    const BatchPlan &P = c->plan;
+    PointTables<PostTile> T;
+    build_pjvp_tiles(table_classes(P), P.order.data(), offsets, c->posterior_budget, T);
+    const size_t Mz = (size_t)std::max<int64_t>(M, 1);
+    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
+    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
+    if ((rc = buf_ensure(c, BUF_WP_OUT, wc.wb.out_doubles * sizeof(double)))) return rc;
+    const bool with_y2 = y2 != nullptr && M > 0;
+    if (with_y2) {   // (widened once on the host, as the observations are)
+        if ((rc = buf_ensure(c, BUF_WP_Y2, Mz * sizeof(double)))) return rc;
+        void *pin = nullptr;
+        if ((rc = pin_stage(c, sizeof(double) * Mz, &pin))) return rc;
+        for (int64_t k = 0; k < M; k++) ((double *)pin)[k] = (double)y2[k];
+        HIPCHK(c, hipMemcpyAsync(buf<double>(c, BUF_WP_Y2), pin, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+    }
+    double *d_out = buf<double>(c, BUF_WP_OUT);
+    double *d_zmean = d_out + warp_out_zmean(Mz), *d_zvar = d_out + warp_out_zvar(Mz), *d_lpd = d_out + warp_out_lpd(Mz), *d_quant = d_out + warp_out_quant(Mz);
+    for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
+        const SizeClass &k = P.cls[ch.cls];
+        const MedgpDev V = class_view(c, P, k);
+        const PostTile *tiles = buf<PostTile>(c, BUF_TILES) + ch.t0;
+        {
+            Launcher l(c, KID_PJ_SOLVE);   // (nvec = 0: no derivative output is touched)
+            hipLaunchKernelGGL(k_pjvp_solve, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK),
+                               ch.stride, 0, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), (double *)nullptr, (double *)nullptr);
+        }
+        Launcher l(c, KID_WP_POST);
+        hipLaunchKernelGGL(k_warp_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_WORK), ch.stride, wc.kind,
+                           wc.in, wc.role(WARP_VEC_W, P.need_vec, k.off_vec), with_y2 ? buf<double>(c, BUF_WP_Y2) : (const double *)nullptr, nq,
+                           wc.in + warp_in_zq(nbatch, wc.D), d_zmean, d_zvar, d_quant, d_lpd);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (M > 0 && zmean) {
+        HIPCHK(c, hipMemcpyAsync(zmean, d_zmean, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(zvar, d_zvar, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (M > 0 && quant) HIPCHK(c, hipMemcpyAsync(quant, d_quant, sizeof(double) * M * nq, hipMemcpyDeviceToHost, c->stream));
+    if (M > 0 && lpd) HIPCHK(c, hipMemcpyAsync(lpd, d_lpd, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = read_status(c, nbatch, status))) return rc;
+    free_retired(c);
+    return MEDGP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int medgp_warp_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int32_t *kind, const double *psi,
+                         int flag_grad, double *nlml, double *grad, double *dpsi, double *logjac, int32_t *status) {
+    return warp_grad_impl(c, nbatch, slots, theta, kind, psi, flag_grad, nlml, grad, dpsi, logjac, status);
+}
+
+int medgp_warp_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int32_t *kind, const double *psi,
+                               const int64_t *offsets, const int32_t *meta2, const float *t2, const float *y2, int nq, const double *zq,
+                               double *zmean, double *zvar, double *quant, double *lpd, int32_t *status) {
+    return warp_post_impl(c, nbatch, slots, theta, kind, psi, offsets, meta2, t2, y2, nq, zq, zmean, zvar, quant, lpd, status);
+}
 
 int medgp_mean_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int mode, const double *b0, const double *lam,
                          int flag_grad, double *nlml, double *grad, double *dmean, double *beta, double *beta_cov, int32_t *status) {
@@ -3483,7 +3679,8 @@ int medgp_profile_enable(medgp_ctx *c, int enable) {
 // the table existing callers index is frozen at its 23 entries (include/medgp_hip.h); entries added since are reached through the _all count
 int medgp_profile_num_kernels(void) { return KID_FORECAST + 1; }
 int medgp_profile_num_kernels_all(void) { return KID_FC_WGRAD + 1; }
-int medgp_profile_num_kernels_ext(void) { return KID_COUNT; }
+int medgp_profile_num_kernels_ext(void) { return KID_EXT_COUNT; }
+int medgp_profile_num_kernels_ext2(void) { return KID_COUNT; }
 const char *medgp_profile_kernel_name(int k) { return (k >= 0 && k < KID_COUNT) ? kKernelNames[k] : ""; }
 int medgp_profile_read(medgp_ctx *c, int k, double *ms_total, int64_t *launches) {
     if (!c || k < 0 || k >= KID_COUNT) return MEDGP_ERR_ARG;
