@@ -8,6 +8,7 @@ Fails loudly when the HIP library is missing -- there is no CPU path.
 import ctypes as C
 import weakref
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -146,6 +147,17 @@ def load():
 
 def _ptr(a, ty):
     return None if a is None else a.ctypes.data_as(C.POINTER(ty))
+
+
+def _cat(arrs, M, dtype, tail=()):
+    """the per-patient arrays of a call's M points as one array [M, *tail]; a call without points hands over one element that is never read"""
+    return np.ascontiguousarray(np.concatenate(arrs, axis=0) if M else np.zeros((1,) + tuple(tail)), dtype=dtype)
+
+
+def _split(offsets, *arrays):
+    """per patient b the copies of rows [offsets[b], offsets[b + 1]) of every array, as a tuple; a None array stays None"""
+    for a, e in zip(offsets[:-1], offsets[1:]):
+        yield tuple(None if x is None else x[int(a):int(e)].copy() for x in arrays)
 
 
 def _pack(series):
@@ -378,8 +390,7 @@ class Context:
     def nlml_grad(self, slots, theta, flag_grad=True, keep_factor=False):
         """Host-pointer operator. theta: [nbatch, H]. Returns (nlml[nbatch], grad[nbatch,H] or None, status[nbatch]).
         keep_factor: MEDGP_FLAG_KEEP_FACTOR (alpha / L^-1 available through get_factor even without gradients)."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(slots.shape[0], self.H)
+        slots, theta = self._batch_args(slots, theta)
         nb = slots.shape[0]
         nlml = np.empty(nb)
         grad = np.empty((nb, self.H)) if flag_grad else None
@@ -414,9 +425,8 @@ class Context:
 
     def factor_batch(self, slots, theta, ns):
         """medgp_factor_batch: list of (L[n,n], z[n]) per entry and the status array; ns = observations of each entry."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        slots, theta = self._batch_args(slots, theta)
         nb = slots.shape[0]
-        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
         Ls = [np.zeros((int(n), int(n))) for n in ns]
         zs = [np.zeros(int(n)) for n in ns]
         Lp = (C.POINTER(C.c_double) * nb)(*[_ptr(a, C.c_double) for a in Ls])
@@ -439,9 +449,8 @@ class Context:
 
     def fit_predict_batch(self, slots, theta, meta2, t2):
         """One test point per problem: problem b = (slots[b], theta[b], meta2[b], t2[b])."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        slots, theta = self._batch_args(slots, theta)
         nb = slots.shape[0]
-        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
         t2 = np.ascontiguousarray(t2, dtype=np.float32)
         meta2 = None if meta2 is None else np.ascontiguousarray(meta2, dtype=np.int32)
         mean = np.empty(nb, dtype=np.float32)
@@ -452,14 +461,23 @@ class Context:
                                                     _ptr(var, C.c_float), _ptr(st, C.c_int32)))
         return mean, var, st
 
-    def _posterior_args(self, slots, theta, meta2_list, t2_list):
-        """the argument checks of posterior / posterior_joint: (slots, theta [nbatch, H], covariate arrays, time arrays)"""
+    def _batch_args(self, slots, theta, check=False):
+        """(slots int32 [nbatch], theta float64 [nbatch, H]) as every batched call takes them; check: a theta of another size is
+        refused in the wrappers' own words instead of numpy's"""
         slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
         nb = slots.shape[0]
         theta = np.ascontiguousarray(theta, dtype=np.float64)
-        if theta.size != nb * self.H:
+        if check and theta.size != nb * self.H:
             raise ValueError(f"theta has {theta.size} values, expected {nb} x {self.H}")
-        theta = theta.reshape(nb, self.H)
+        return slots, theta.reshape(nb, self.H)
+
+    def _point_args(self, slots, theta, meta2_list, t2_list):
+        """The one pack of a call that takes test points, after its argument checks: slots, theta [nbatch, H]; ms / ts the covariate
+        and time arrays per patient; cnt, offsets [nbatch + 1] and M = the points per patient, their CSR and their number; m2 / t2 the
+        concatenated arrays (one never-read element when M = 0); head = (handle, nbatch, slots, theta) and pts = (offsets, meta2, t2)
+        as the C calls take them."""
+        slots, theta = self._batch_args(slots, theta, check=True)
+        nb = slots.shape[0]
         if len(t2_list) != nb:
             raise ValueError(f"{len(t2_list)} test-point arrays for {nb} patients")
         ts = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in t2_list]
@@ -474,33 +492,42 @@ class Context:
             for b, (m, x) in enumerate(zip(ms, ts)):
                 if m.shape[0] != x.shape[0]:
                     raise ValueError(f"patient {b}: {m.shape[0]} covariates for {x.shape[0]} test times")
-        return slots, theta, ms, ts
+        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum(cnt)
+        M = int(offsets[-1])
+        p = SimpleNamespace(slots=slots, theta=theta, nb=nb, ms=ms, ts=ts, cnt=cnt, offsets=offsets, M=M, Mz=max(M, 1),
+                            t2=_cat(ts, M, np.float32), m2=_cat(ms, M, np.int32), st=np.empty(nb, dtype=np.int32))
+        p.head = (self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double))
+        p.pts = (_ptr(offsets, C.c_int64), _ptr(p.m2, C.c_int32), _ptr(p.t2, C.c_float))
+        return p
+
+    @staticmethod
+    def _per_point(p, lst, dtype, what, width=None):
+        """one array per patient, matching the t2_list of the pack p, as one array of dtype: [M] of arrays [m] (width None), [M, width]
+        of arrays [m, width] (or anything of m x width values); a None list stays None"""
+        if lst is None:
+            return None
+        if len(lst) != p.nb:
+            raise ValueError(f"{len(lst)} {what} arrays for {p.nb} patients")
+        tail = () if width is None else (width,)
+        rows = [np.ascontiguousarray(x, dtype=dtype) for x in lst]
+        for b, (a, m) in enumerate(zip(rows, p.cnt)):
+            if a.size != m * (1 if width is None else width):
+                raise ValueError(f"patient {b}: {what} of shape {a.shape} for {int(m)} test points, expected {(int(m),) + tail}")
+        return _cat([a.reshape((int(m),) + tail) for a, m in zip(rows, p.cnt)], p.M, dtype, tail)
 
     def posterior(self, slots, theta, meta2_list, t2_list, parts=True):
         """medgp_posterior_batch: GP_Regression::predict / parsed_predict for many points of many patients in one call.
         slots [nbatch], theta [nbatch, H]; t2_list: one array of test times per patient (may be empty), meta2_list: one array of
         test covariates per patient (None for SE / SM).  Returns ([(mean[m], var[m], parts[m, D] or None) per patient], status)."""
-        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
-        nb = slots.shape[0]
-        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
-        offsets = np.zeros(nb + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum(cnt)
-        M = int(offsets[-1])
-        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
-        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
+        p = self._point_args(slots, theta, meta2_list, t2_list)
         D = self.D if self.kernel_index == KERNEL_LMC_SM else 1
-        mean = np.empty(max(M, 1), dtype=np.float32)
-        var = np.empty(max(M, 1), dtype=np.float32)
-        pr = np.empty((max(M, 1), D), dtype=np.float32) if parts else None
-        st = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_posterior_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
-                                                  offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
-                                                  _ptr(mean, C.c_float), _ptr(var, C.c_float), _ptr(pr, C.c_float), _ptr(st, C.c_int32)))
-        out = []
-        for b in range(nb):
-            a, e = int(offsets[b]), int(offsets[b + 1])
-            out.append((mean[a:e].copy(), var[a:e].copy(), pr[a:e].copy() if parts else None))
-        return out, st
+        mean, var = (np.empty(p.Mz, dtype=np.float32) for _ in range(2))
+        pr = np.empty((p.Mz, D), dtype=np.float32) if parts else None
+        self._chk(self._lib.medgp_posterior_batch(*p.head, *p.pts, _ptr(mean, C.c_float), _ptr(var, C.c_float), _ptr(pr, C.c_float),
+                                                  _ptr(p.st, C.c_int32)))
+        return list(_split(p.offsets, mean, var, pr)), p.st
 
     def forecast(self, slots, theta, meta2_list, t2_list, prefix_list=None, y2_list=None):
         """medgp_forecast_batch: point j of patient b predicted from the FIRST prefix_list[b][j] observations of the patient in the
@@ -508,90 +535,39 @@ class Context:
         points).  slots, theta, meta2_list, t2_list as posterior(); prefix_list: one int array per patient, values in [0, n_b]
         (None: all of the patient's data); y2_list: the observed values at the points (None: no lpd).
         Returns ([(mean[m], var[m], lpd[m] or None) per patient], status)."""
-        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
-        nb = slots.shape[0]
-        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
-        offsets = np.zeros(nb + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum(cnt)
-        M = int(offsets[-1])
-
-        def per_point(lst, dtype, what):
-            if lst is None:
-                return None
-            if len(lst) != nb:
-                raise ValueError(f"{len(lst)} {what} arrays for {nb} patients")
-            arrs = [np.ascontiguousarray(x, dtype=dtype).ravel() for x in lst]
-            for b, (a, x) in enumerate(zip(arrs, ts)):
-                if a.shape[0] != x.shape[0]:
-                    raise ValueError(f"patient {b}: {a.shape[0]} {what} values for {x.shape[0]} test times")
-            return np.ascontiguousarray(np.concatenate(arrs) if M else np.zeros(1), dtype=dtype)
-
-        pf = per_point(prefix_list, np.int32, "prefix")
-        y2 = per_point(y2_list, np.float32, "y2")
-        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
-        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
-        mean = np.empty(max(M, 1), dtype=np.float32)
-        var = np.empty(max(M, 1), dtype=np.float32)
-        lpd = np.empty(max(M, 1), dtype=np.float64) if y2 is not None else None
-        st = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_forecast_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
-                                                 offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
-                                                 _ptr(pf, C.c_int32), _ptr(y2, C.c_float), _ptr(mean, C.c_float), _ptr(var, C.c_float),
-                                                 _ptr(lpd, C.c_double), _ptr(st, C.c_int32)))
-        out = []
-        for b in range(nb):
-            a, e = int(offsets[b]), int(offsets[b + 1])
-            out.append((mean[a:e].copy(), var[a:e].copy(), lpd[a:e].copy() if lpd is not None else None))
-        return out, st
+        p = self._point_args(slots, theta, meta2_list, t2_list)
+        pf = self._per_point(p, prefix_list, np.int32, "prefix")
+        y2 = self._per_point(p, y2_list, np.float32, "y2")
+        mean, var = (np.empty(p.Mz, dtype=np.float32) for _ in range(2))
+        lpd = np.empty(p.Mz, dtype=np.float64) if y2 is not None else None
+        self._chk(self._lib.medgp_forecast_batch(*p.head, *p.pts, _ptr(pf, C.c_int32), _ptr(y2, C.c_float), _ptr(mean, C.c_float),
+                                                 _ptr(var, C.c_float), _ptr(lpd, C.c_double), _ptr(p.st, C.c_int32)))
+        return list(_split(p.offsets, mean, var, lpd)), p.st
 
     def trend(self, slots, theta, meta2_list, t2_list, cross=True):
         """medgp_trend_batch: the posterior of the latent slope f'(t*) at every test point, next to the posterior of the value.
         Arguments as posterior().  Returns ([(mean[m], var[m], dmean[m], dvar[m], cross[m] or None) per patient], status): mean /
         var are posterior(parts=False)'s, bit for bit; dmean is the slope per hour in the units of y, dvar the variance of the
         LATENT slope (no noise term), cross = cov(f(t*), f'(t*)).  medgp_amd.trend turns them into P(rising) and rate intervals."""
-        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
-        nb = slots.shape[0]
-        offsets = np.zeros(nb + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum([x.shape[0] for x in ts])
-        M = int(offsets[-1])
-        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
-        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
-        mean, var, dmean, dvar = (np.empty(max(M, 1), dtype=np.float32) for _ in range(4))
-        cr = np.empty(max(M, 1), dtype=np.float32) if cross else None
-        st = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_trend_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
-                                              offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
-                                              _ptr(mean, C.c_float), _ptr(var, C.c_float), _ptr(dmean, C.c_float), _ptr(dvar, C.c_float),
-                                              _ptr(cr, C.c_float), _ptr(st, C.c_int32)))
-        out = []
-        for b in range(nb):
-            a, e = int(offsets[b]), int(offsets[b + 1])
-            out.append((mean[a:e].copy(), var[a:e].copy(), dmean[a:e].copy(), dvar[a:e].copy(), cr[a:e].copy() if cross else None))
-        return out, st
+        p = self._point_args(slots, theta, meta2_list, t2_list)
+        mean, var, dmean, dvar = (np.empty(p.Mz, dtype=np.float32) for _ in range(4))
+        cr = np.empty(p.Mz, dtype=np.float32) if cross else None
+        self._chk(self._lib.medgp_trend_batch(*p.head, *p.pts, _ptr(mean, C.c_float), _ptr(var, C.c_float), _ptr(dmean, C.c_float),
+                                              _ptr(dvar, C.c_float), _ptr(cr, C.c_float), _ptr(p.st, C.c_int32)))
+        return list(_split(p.offsets, mean, var, dmean, dvar, cr)), p.st
 
     def components(self, slots, theta, meta2_list, t2_list, cov=True):
         """medgp_components_batch: the posterior of every spectral component f_q of the latent f = sum_q f_q at every test point.
         Arguments as posterior().  Returns ([(cmean[m, Q], cvar[m, Q], ccov[m, Q, Q] or None) per patient], status): cmean[j, q] the
         posterior mean of f_q at point j, ccov[j] the Q x Q posterior covariance of the components there (LATENT: no noise term),
         cvar[j] its diagonal.  medgp_amd.components names the components (period, length scale, weight) and sums bands of them."""
-        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
-        nb, Q = slots.shape[0], self.Q
-        offsets = np.zeros(nb + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum([x.shape[0] for x in ts])
-        M = int(offsets[-1])
-        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
-        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
-        cmean, cvar = (np.empty((max(M, 1), Q), dtype=np.float32) for _ in range(2))
-        cc = np.empty((max(M, 1), Q, Q), dtype=np.float32) if cov else None
-        st = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_components_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
-                                                   offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
-                                                   _ptr(cmean, C.c_float), _ptr(cvar, C.c_float), _ptr(cc, C.c_float), _ptr(st, C.c_int32)))
-        out = []
-        for b in range(nb):
-            a, e = int(offsets[b]), int(offsets[b + 1])
-            out.append((cmean[a:e].copy(), cvar[a:e].copy(), cc[a:e].copy() if cov else None))
-        return out, st
+        p = self._point_args(slots, theta, meta2_list, t2_list)
+        Q = self.Q
+        cmean, cvar = (np.empty((p.Mz, Q), dtype=np.float32) for _ in range(2))
+        cc = np.empty((p.Mz, Q, Q), dtype=np.float32) if cov else None
+        self._chk(self._lib.medgp_components_batch(*p.head, *p.pts, _ptr(cmean, C.c_float), _ptr(cvar, C.c_float), _ptr(cc, C.c_float),
+                                                   _ptr(p.st, C.c_int32)))
+        return list(_split(p.offsets, cmean, cvar, cc)), p.st
 
     def functionals(self, slots, theta, packed_list):
         """medgp_functional_batch: the posterior of linear functionals g = sum_k a_k f_{m_k}(t_k) of the latent function -- window
@@ -608,11 +584,7 @@ class Context:
                                                    foffsets.ctypes.data_as(i64p), toffsets.ctypes.data_as(i64p), _ptr(m2, C.c_int32),
                                                    _ptr(t2, C.c_float), _ptr(wt, C.c_double), _ptr(fmean, C.c_float), _ptr(fvar, C.c_float),
                                                    _ptr(st, C.c_int32)))
-        out = []
-        for b in range(nb):
-            a, e = int(foffsets[b]), int(foffsets[b + 1])
-            out.append((fmean[a:e].copy(), fvar[a:e].copy()))
-        return out, st
+        return list(_split(foffsets, fmean, fvar)), st
 
     def functionals_joint(self, slots, theta, packed_list):
         """medgp_functional_joint_batch: functionals() plus the posterior covariance between the functionals of each patient.
@@ -632,21 +604,14 @@ class Context:
                                                          foffsets.ctypes.data_as(i64p), toffsets.ctypes.data_as(i64p), _ptr(m2, C.c_int32),
                                                          _ptr(t2, C.c_float), _ptr(wt, C.c_double), _ptr(fmean, C.c_float),
                                                          _ptr(fvar, C.c_float), _ptr(fcov, C.c_float), _ptr(st, C.c_int32)))
-        out = []
-        for b in range(nb):
-            a, e, k = int(foffsets[b]), int(foffsets[b + 1]), int(cnt[b])
-            out.append((fmean[a:e].copy(), fvar[a:e].copy(), fcov[int(coff[b]):int(coff[b + 1])].reshape(k, k).copy()))
-        return out, st
+        blocks = [fcov[int(coff[b]):int(coff[b + 1])].reshape(int(k), int(k)).copy() for b, k in enumerate(cnt)]
+        return [mv + (c,) for mv, c in zip(_split(foffsets, fmean, fvar), blocks)], st
 
     def _functional_args(self, slots, theta, packed_list):
         """the argument checks of functionals() / functionals_joint(), raised before the library is reached: (slots, theta [nbatch, H],
         foffsets [nbatch + 1], toffsets [F + 1], meta2, t2, weight per term) as the calls take them"""
-        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        slots, theta = self._batch_args(slots, theta, check=True)
         nb = slots.shape[0]
-        theta = np.ascontiguousarray(theta, dtype=np.float64)
-        if theta.size != nb * self.H:
-            raise ValueError(f"theta has {theta.size} values, expected {nb} x {self.H}")
-        theta = theta.reshape(nb, self.H)
         if len(packed_list) != nb:
             raise ValueError(f"{len(packed_list)} packed functional lists for {nb} patients")
         multi = self.kernel_index == KERNEL_LMC_SM
@@ -678,10 +643,7 @@ class Context:
         tbase = np.concatenate([[0], np.cumsum([int(x[-1]) for x in toffs])]).astype(np.int64)
         toffsets = np.ascontiguousarray(np.concatenate([[0]] + [x[1:] + tbase[b] for b, x in enumerate(toffs)]), dtype=np.int64)
         T = int(tbase[-1])
-        t2 = np.ascontiguousarray(np.concatenate(ts) if T else np.zeros(1), dtype=np.float32)
-        m2 = np.ascontiguousarray(np.concatenate(ms) if T else np.zeros(1), dtype=np.int32)
-        wt = np.ascontiguousarray(np.concatenate(ws) if T else np.zeros(1), dtype=np.float64)
-        return slots, theta, foffsets, toffsets, m2, t2, wt
+        return slots, theta, foffsets, toffsets, _cat(ms, T, np.int32), _cat(ts, T, np.float32), _cat(ws, T, np.float64)
 
     def posterior_joint(self, slots, theta, meta2_list, t2_list, eps_list=None, cov=True):
         """medgp_posterior_joint_batch: the joint predictive distribution of every patient's test points.  Arguments as
@@ -689,8 +651,8 @@ class Context:
         all), or None for the covariance only; cov=False: samples only.  Returns ([(mean[m], var[m], cov[m, m] or None,
         samples[m, nsamp] or None) per patient], status, cov_status): cov = K** - V^T V + diag(sigma^2), whose diagonal is var;
         samples[:, s] = mean + chol(cov) eps[:, s]."""
-        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
-        nb = slots.shape[0]
+        p = self._point_args(slots, theta, meta2_list, t2_list)
+        nb, ts, cnt = p.nb, p.ts, p.cnt
         nsamp = 0
         es = None
         if eps_list is None:
@@ -709,45 +671,28 @@ class Context:
             nsamp = widths.pop()
             if nsamp < 1:
                 raise ValueError("eps arrays with nsamp = 0: pass eps_list=None for the covariance only")
-        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
-        offsets = np.zeros(nb + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum(cnt)
         coff = np.zeros(nb + 1, dtype=np.int64)
         coff[1:] = np.cumsum(cnt * cnt)
-        M = int(offsets[-1])
-        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
-        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
-        mean = np.empty(max(M, 1), dtype=np.float32)
-        var = np.empty(max(M, 1), dtype=np.float32)
+        mean, var = (np.empty(p.Mz, dtype=np.float32) for _ in range(2))
         cv = np.empty(max(int(coff[-1]), 1), dtype=np.float32) if cov else None
         eps = sm = None
         if nsamp:
-            eps = np.ascontiguousarray(np.concatenate(es, axis=0) if M else np.zeros((1, nsamp)), dtype=np.float64)
-            sm = np.empty((max(M, 1), nsamp), dtype=np.float32)
-        st = np.empty(nb, dtype=np.int32)
+            eps = _cat(es, p.M, np.float64, (nsamp,))
+            sm = np.empty((p.Mz, nsamp), dtype=np.float32)
         cst = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_posterior_joint_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
-                                                        offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
-                                                        int(nsamp), _ptr(eps, C.c_double), _ptr(mean, C.c_float), _ptr(var, C.c_float),
-                                                        _ptr(cv, C.c_float), _ptr(sm, C.c_float), _ptr(st, C.c_int32), _ptr(cst, C.c_int32)))
-        out = []
-        for b in range(nb):
-            a, e, m = int(offsets[b]), int(offsets[b + 1]), int(cnt[b])
-            out.append((mean[a:e].copy(), var[a:e].copy(), cv[int(coff[b]):int(coff[b + 1])].reshape(m, m).copy() if cov else None,
-                        sm[a:e].copy() if nsamp else None))
-        return out, st, cst
+        self._chk(self._lib.medgp_posterior_joint_batch(*p.head, *p.pts, int(nsamp), _ptr(eps, C.c_double), _ptr(mean, C.c_float),
+                                                        _ptr(var, C.c_float), _ptr(cv, C.c_float), _ptr(sm, C.c_float), _ptr(p.st, C.c_int32),
+                                                        _ptr(cst, C.c_int32)))
+        blocks = [cv[int(coff[b]):int(coff[b + 1])].reshape(int(m), int(m)).copy() if cov else None for b, m in enumerate(cnt)]
+        return [(mu, v, c, s) for (mu, v, s), c in zip(_split(p.offsets, mean, var, sm), blocks)], p.st, cst
 
     def _loo_args(self, slots, theta, groups):
         """the argument checks of loo(): (slots, theta [nbatch, H], observation counts, group ids or None, groups per patient or
         None); the observation counts and covariates of the patients are those set_patient[s] saw."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
-        nb = slots.shape[0]
-        if nb < 1:
+        if np.size(slots) < 1:
             raise ValueError("no patient")
-        theta = np.ascontiguousarray(theta, dtype=np.float64)
-        if theta.size != nb * self.H:
-            raise ValueError(f"theta has {theta.size} values, expected {nb} x {self.H}")
-        theta = theta.reshape(nb, self.H)
+        slots, theta = self._batch_args(slots, theta, check=True)
+        nb = slots.shape[0]
         missing = [int(s) for s in slots if int(s) not in self._slot_n]
         if missing:
             raise ValueError(f"slots {missing} hold no patient set through this Context")
@@ -813,8 +758,7 @@ class Context:
     def loo_grad(self, slots, theta, flag_grad=True):
         """medgp_loo_grad: the negative leave-one-out log pseudo-likelihood (plus the prior term, as nlml_grad) and its gradient
         in theta.  slots [nbatch], theta [nbatch, H].  Returns (obj[nbatch], grad[nbatch, H] or None, status[nbatch])."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(slots.shape[0], self.H)
+        slots, theta = self._batch_args(slots, theta)
         nb = slots.shape[0]
         flag = int(flag_grad)
         obj = np.empty(nb)
@@ -851,9 +795,8 @@ class Context:
         """medgp_fisher_vec: products of the Fisher information F(theta_b) = 1/2 tr(P dK_h P dK_k) of the marginal likelihood with
         directions in theta space.  slots [nbatch], theta [nbatch, H], vecs [nbatch, nvec, H] or [nbatch, H] (one direction each).
         No prior, no dependence on y.  Returns (fvec of the shape of vecs, status[nbatch]); a failed patient's rows are NaN."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        slots, theta = self._batch_args(slots, theta)
         nb = slots.shape[0]
-        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
         v = np.ascontiguousarray(vecs, dtype=np.float64)
         if v.ndim not in (2, 3) or v.shape[0] != nb or v.shape[-1] != self.H:
             raise ValueError(f"vecs of shape {v.shape} for {nb} patients of {self.H} hypers")
@@ -869,9 +812,8 @@ class Context:
         directions in theta space.  slots [nbatch], theta [nbatch, H], vecs [nbatch, nvec, H] or [nbatch, H] (one direction each).
         Returns (hvec of the shape of vecs, status[nbatch]), or with want_grad (hvec, grad[nbatch, H], status): grad is the gradient
         of L.  A failed patient's rows are NaN."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        slots, theta = self._batch_args(slots, theta)
         nb = slots.shape[0]
-        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
         v = np.ascontiguousarray(vecs, dtype=np.float64)
         if v.ndim not in (2, 3) or v.shape[0] != nb or v.shape[-1] != self.H:
             raise ValueError(f"vecs of shape {v.shape} for {nb} patients of {self.H} hypers")
@@ -890,33 +832,17 @@ class Context:
         [nbatch, nvec, H] or [nbatch, H] (one direction each), as fisher_vec takes it.
         Returns ([(mean[m], var[m], dmean[m, nvec], dvar[m, nvec]) per patient], status); mean and var are None without
         want_posterior.  A failed patient's rows are NaN."""
-        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
-        nb = slots.shape[0]
+        p = self._point_args(slots, theta, meta2_list, t2_list)
         v = np.ascontiguousarray(vecs, dtype=np.float64)
-        if v.ndim not in (2, 3) or v.shape[0] != nb or v.shape[-1] != self.H:
-            raise ValueError(f"vecs of shape {v.shape} for {nb} patients of {self.H} hypers")
+        if v.ndim not in (2, 3) or v.shape[0] != p.nb or v.shape[-1] != self.H:
+            raise ValueError(f"vecs of shape {v.shape} for {p.nb} patients of {self.H} hypers")
         nvec = 1 if v.ndim == 2 else v.shape[1]
-        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
-        offsets = np.zeros(nb + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum(cnt)
-        M = int(offsets[-1])
-        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
-        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
-        mean = np.empty(max(M, 1), dtype=np.float32) if want_posterior else None
-        var = np.empty(max(M, 1), dtype=np.float32) if want_posterior else None
-        dmean = np.empty((max(M, 1), nvec))
-        dvar = np.empty((max(M, 1), nvec))
-        st = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_posterior_jvp_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
-                                                      offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
-                                                      int(nvec), _ptr(v, C.c_double), _ptr(mean, C.c_float), _ptr(var, C.c_float),
-                                                      _ptr(dmean, C.c_double), _ptr(dvar, C.c_double), _ptr(st, C.c_int32)))
-        out = []
-        for b in range(nb):
-            a, e = int(offsets[b]), int(offsets[b + 1])
-            out.append((mean[a:e].copy() if want_posterior else None, var[a:e].copy() if want_posterior else None,
-                        dmean[a:e].copy(), dvar[a:e].copy()))
-        return out, st
+        mean, var = ((np.empty(p.Mz, dtype=np.float32) if want_posterior else None) for _ in range(2))
+        dmean, dvar = (np.empty((p.Mz, nvec)) for _ in range(2))
+        self._chk(self._lib.medgp_posterior_jvp_batch(*p.head, *p.pts, int(nvec), _ptr(v, C.c_double), _ptr(mean, C.c_float),
+                                                      _ptr(var, C.c_float), _ptr(dmean, C.c_double), _ptr(dvar, C.c_double),
+                                                      _ptr(p.st, C.c_int32)))
+        return list(_split(p.offsets, mean, var, dmean, dvar)), p.st
 
     PLOSS = {"custom": 0, "nlpd": 1, "sqerr": 2, "crps": 3}
 
@@ -930,37 +856,15 @@ class Context:
             ([(mean[m], var[m], grad[H], loss) per patient], status).
         mean and var are None without want_posterior; with fp64_posterior they are the float64 values the device formed its
         cotangents from (medgp_posterior_vjp_moments) instead of the float outputs.  A failed patient's rows are NaN."""
-        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
-        nb = slots.shape[0]
-        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
-        offsets = np.zeros(nb + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum(cnt)
-        M = int(offsets[-1])
-        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
-        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
-
-        def per_point(lst, what, width=None):
-            if len(lst) != nb:
-                raise ValueError(f"{what}: {len(lst)} arrays for {nb} patients")
-            rows = []
-            for b, x in enumerate(lst):
-                a = np.asarray(x, dtype=np.float64)
-                a = a.reshape(int(cnt[b]), -1) if cnt[b] else np.zeros((0, 0))
-                if width is not None and a.shape[1] != width and a.shape[0]:
-                    raise ValueError(f"{what}[{b}] of shape {a.shape}, expected [{int(cnt[b])}, {width}]")
-                rows.append(a)
-            w = width if width is not None else max([r.shape[1] for r in rows if r.shape[0]] or [1])
-            rows = [r if r.shape[0] else np.zeros((0, w)) for r in rows]
-            for b, r in enumerate(rows):
-                if r.shape[1] != w:
-                    raise ValueError(f"{what}[{b}] has {r.shape[1]} columns, others {w}")
-            return np.ascontiguousarray(np.concatenate(rows) if M else np.zeros((1, w))), w
-
+        p = self._point_args(slots, theta, meta2_list, t2_list)
+        nb = p.nb
         if loss is None:
             if cot_mean is None or cot_var is None or y2_list is not None or wt_list is not None:
                 raise ValueError("custom cotangents: cot_mean and cot_var are required, y2_list / wt_list are not taken")
-            cm, ncot = per_point(cot_mean, "cot_mean")
-            cv, _ = per_point(cot_var, "cot_var", ncot)
+            # ncot: the columns of the first patient that has points ([m] arrays: one set)
+            ncot = next((max(np.size(x) // int(m), 1) for x, m in zip(cot_mean, p.cnt) if m), 1)
+            cm = self._per_point(p, cot_mean, np.float64, "cot_mean", ncot)
+            cv = self._per_point(p, cot_var, np.float64, "cot_var", ncot)
             kind, y2, wt, lossv = 0, None, None, None
         else:
             if loss not in self.PLOSS or loss == "custom":
@@ -968,27 +872,19 @@ class Context:
             if y2_list is None or cot_mean is not None or cot_var is not None:
                 raise ValueError("a built-in loss takes y2_list and no cotangents")
             kind, ncot, cm, cv = self.PLOSS[loss], 1, None, None
-            y2 = per_point(y2_list, "y2_list", 1)[0]
-            wt = per_point(wt_list, "wt_list", 1)[0] if wt_list is not None else None
+            y2 = self._per_point(p, y2_list, np.float64, "y2_list")
+            wt = self._per_point(p, wt_list, np.float64, "wt_list")
             lossv = np.empty(nb)
-        mean = np.empty(max(M, 1), dtype=np.float32) if want_posterior else None
-        var = np.empty(max(M, 1), dtype=np.float32) if want_posterior else None
+        mean, var = ((np.empty(p.Mz, dtype=np.float32) if want_posterior else None) for _ in range(2))
         grad = np.empty((nb, ncot, self.H))
-        st = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_posterior_vjp_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double),
-                                                      offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float),
-                                                      kind, _ptr(y2, C.c_double), _ptr(wt, C.c_double), int(ncot), _ptr(cm, C.c_double),
-                                                      _ptr(cv, C.c_double), _ptr(mean, C.c_float), _ptr(var, C.c_float),
-                                                      _ptr(lossv, C.c_double), _ptr(grad, C.c_double), _ptr(st, C.c_int32)))
+        self._chk(self._lib.medgp_posterior_vjp_batch(*p.head, *p.pts, kind, _ptr(y2, C.c_double), _ptr(wt, C.c_double), int(ncot),
+                                                      _ptr(cm, C.c_double), _ptr(cv, C.c_double), _ptr(mean, C.c_float), _ptr(var, C.c_float),
+                                                      _ptr(lossv, C.c_double), _ptr(grad, C.c_double), _ptr(p.st, C.c_int32)))
         if want_posterior and fp64_posterior:
-            mean, var = np.empty(max(M, 1)), np.empty(max(M, 1))
-            self._chk(self._lib.medgp_posterior_vjp_moments(self._h, M, _ptr(mean, C.c_double), _ptr(var, C.c_double)))
-        out = []
-        for b in range(nb):
-            a, e = int(offsets[b]), int(offsets[b + 1])
-            mv = (mean[a:e].copy(), var[a:e].copy()) if want_posterior else (None, None)
-            out.append(mv + ((grad[b].copy(),) if loss is None else (grad[b, 0].copy(), float(lossv[b]))))
-        return out, st
+            mean, var = np.empty(p.Mz), np.empty(p.Mz)
+            self._chk(self._lib.medgp_posterior_vjp_moments(self._h, p.M, _ptr(mean, C.c_double), _ptr(var, C.c_double)))
+        tails = [(grad[b].copy(),) if loss is None else (grad[b, 0].copy(), float(lossv[b])) for b in range(nb)]
+        return [mv + t for mv, t in zip(_split(p.offsets, mean, var), tails)], p.st
 
     def _mean_args(self, nb, b0, lam, fixed, ncol=None):
         """(mode, b0 [nb, D], lam [nb, D] or None) of the baseline calls; a vector [D] serves every patient (ncol: the basis calls' p)"""
@@ -1019,9 +915,8 @@ class Context:
     def _fe_nlml_grad(self, fn, dkey, basis, slots, theta, b0, lam, fixed, flag_grad):
         """mean_nlml_grad and basis_nlml_grad: fn the C entry point, dkey the result's key of d nlml / d b0; basis: the column count
         is the p of b0 and lam, not D"""
-        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        slots, theta = self._batch_args(slots, theta)
         nb = slots.shape[0]
-        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
         mode, b0, lam = self._mean_args(nb, b0, lam, fixed, self._basis_cols(b0, lam, nb) if basis else None)
         D = b0.shape[1]
         nlml, grad = np.empty(nb), (np.empty((nb, self.H)) if flag_grad else None)
@@ -1040,28 +935,14 @@ class Context:
     def _fe_posterior(self, fn, basis, slots, theta, meta2_list, t2_list, h2_list, b0, lam, fixed):
         """mean_posterior and basis_posterior: fn the C entry point; basis: the column count is the p of b0 and lam, not D, and the
         points' rows h2 ([M, p], from h2_list) go in behind t2"""
-        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
-        nb = slots.shape[0]
-        mode, b0, lam = self._mean_args(nb, b0, lam, fixed, self._basis_cols(b0, lam, nb) if basis else None)
-        p = b0.shape[1]
-        if basis and len(h2_list) != nb:
-            raise ValueError(f"{len(h2_list)} basis arrays for {nb} patients")
-        hs = [np.asarray(h, dtype=np.float64).reshape(x.shape[0], p) for h, x in zip(h2_list, ts)] if basis else None
-        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
-        offsets = np.zeros(nb + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum(cnt)
-        M = int(offsets[-1])
-        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
-        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
-        h2 = [np.ascontiguousarray(np.concatenate(hs, axis=0) if M else np.zeros((1, p)))] if basis else []
-        mean, var = np.empty(max(M, 1)), np.empty(max(M, 1))
+        p = self._point_args(slots, theta, meta2_list, t2_list)
+        mode, b0, lam = self._mean_args(p.nb, b0, lam, fixed, self._basis_cols(b0, lam, p.nb) if basis else None)
+        h2 = [self._per_point(p, list(h2_list), np.float64, "basis", b0.shape[1])] if basis else []
+        mean, var = np.empty(p.Mz), np.empty(p.Mz)
         beta = np.empty(b0.shape)
-        st = np.empty(nb, dtype=np.int32)
-        self._chk(fn(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), mode, _ptr(b0, C.c_double), _ptr(lam, C.c_double),
-                     offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32), _ptr(t2, C.c_float), *[_ptr(h, C.c_double) for h in h2],
-                     _ptr(mean, C.c_double), _ptr(var, C.c_double), _ptr(beta, C.c_double), _ptr(st, C.c_int32)))
-        out = [(mean[int(offsets[b]):int(offsets[b + 1])].copy(), var[int(offsets[b]):int(offsets[b + 1])].copy()) for b in range(nb)]
-        return out, beta, st
+        self._chk(fn(*p.head, mode, _ptr(b0, C.c_double), _ptr(lam, C.c_double), *p.pts, *[_ptr(h, C.c_double) for h in h2],
+                     _ptr(mean, C.c_double), _ptr(var, C.c_double), _ptr(beta, C.c_double), _ptr(p.st, C.c_int32)))
+        return list(_split(p.offsets, mean, var)), beta, p.st
 
     def set_basis(self, slots, H_list):
         """medgp_set_basis: a resident basis per slot.  H_list: one [n, p] array per slot, rows in the order the patient was uploaded
@@ -1126,9 +1007,8 @@ class Context:
         its gradients in theta and psi.  psi: [D, 3] for every patient or [nbatch, D, 3], rows (a, eps, lambda); kind: [D] of
         WARP_NONE / WARP_SAS, None = all SAS.  Returns dict(nlml [nbatch], grad [nbatch, H] or None, dpsi [nbatch, D, 3],
         logjac [nbatch], status [nbatch]); a failed patient's rows (a warped observation that is not finite among them) are NaN."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        slots, theta = self._batch_args(slots, theta)
         nb = slots.shape[0]
-        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(nb, self.H)
         D, psi, kind = self._warp_args(nb, psi, kind)
         nlml, grad = np.empty(nb), (np.empty((nb, self.H)) if flag_grad else None)
         dpsi, logjac, st = np.empty((nb, D, 3)), np.empty(nb), np.empty(nb, dtype=np.int32)
@@ -1144,9 +1024,8 @@ class Context:
         when zq is given, probs is ignored.  Returns
         ([dict(zmean [m], zvar [m], quant [m, len(probs)], lpd [m] or None) per patient], status)."""
         from statistics import NormalDist
-        slots, theta, ms, ts = self._posterior_args(slots, theta, meta2_list, t2_list)
-        nb = slots.shape[0]
-        D, psi, kind = self._warp_args(nb, psi, kind)
+        p = self._point_args(slots, theta, meta2_list, t2_list)
+        D, psi, kind = self._warp_args(p.nb, psi, kind)
         if zq is None:
             probs = [float(p) for p in probs]
             if any(not 0.0 < p < 1.0 for p in probs):
@@ -1155,36 +1034,14 @@ class Context:
             zq = [0.0 if p == 0.5 else nd.inv_cdf(p) for p in probs]
         zq = np.ascontiguousarray(zq, dtype=np.float64).ravel()
         nq = zq.shape[0]
-        cnt = np.array([x.shape[0] for x in ts], dtype=np.int64)
-        offsets = np.zeros(nb + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum(cnt)
-        M = int(offsets[-1])
-        t2 = np.ascontiguousarray(np.concatenate(ts) if M else np.zeros(1), dtype=np.float32)
-        m2 = np.ascontiguousarray(np.concatenate(ms) if M else np.zeros(1), dtype=np.int32)
-        y2 = None
-        if y2_list is not None:
-            if len(y2_list) != nb:
-                raise ValueError(f"{len(y2_list)} value arrays for {nb} patients")
-            ys = [np.ascontiguousarray(y, dtype=np.float32).ravel() for y in y2_list]
-            if any(y.shape[0] != x.shape[0] for y, x in zip(ys, ts)):
-                raise ValueError("y2_list does not match t2_list")
-            y2 = np.ascontiguousarray(np.concatenate(ys) if M else np.zeros(1), dtype=np.float32)
-        Mz = max(M, 1)
-        zmean, zvar = np.empty(Mz), np.empty(Mz)
-        quant = np.empty((Mz, nq)) if nq else None
-        lpd = np.empty(Mz) if y2 is not None else None
-        st = np.empty(nb, dtype=np.int32)
-        self._chk(self._lib.medgp_warp_posterior_batch(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), _ptr(kind, C.c_int32),
-                                                       _ptr(psi, C.c_double), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(m2, C.c_int32),
-                                                       _ptr(t2, C.c_float), _ptr(y2, C.c_float), nq, _ptr(zq, C.c_double) if nq else None,
-                                                       _ptr(zmean, C.c_double), _ptr(zvar, C.c_double), _ptr(quant, C.c_double),
-                                                       _ptr(lpd, C.c_double), _ptr(st, C.c_int32)))
-        out = []
-        for b in range(nb):
-            lo, hi = int(offsets[b]), int(offsets[b + 1])
-            out.append(dict(zmean=zmean[lo:hi].copy(), zvar=zvar[lo:hi].copy(), quant=None if quant is None else quant[lo:hi].copy(),
-                            lpd=None if lpd is None else lpd[lo:hi].copy()))
-        return out, st
+        y2 = self._per_point(p, y2_list, np.float32, "y2")
+        zmean, zvar = np.empty(p.Mz), np.empty(p.Mz)
+        quant = np.empty((p.Mz, nq)) if nq else None
+        lpd = np.empty(p.Mz) if y2 is not None else None
+        self._chk(self._lib.medgp_warp_posterior_batch(*p.head, _ptr(kind, C.c_int32), _ptr(psi, C.c_double), *p.pts, _ptr(y2, C.c_float), nq,
+                                                       _ptr(zq, C.c_double) if nq else None, _ptr(zmean, C.c_double), _ptr(zvar, C.c_double),
+                                                       _ptr(quant, C.c_double), _ptr(lpd, C.c_double), _ptr(p.st, C.c_int32)))
+        return [dict(zmean=a, zvar=v, quant=q, lpd=l) for a, v, q, l in _split(p.offsets, zmean, zvar, quant, lpd)], p.st
 
     def forecast_grad(self, slots, theta, prefixes=None, flag_grad=1):
         """medgp_forecast_grad: the negative forecast score J = - sum_i lpd_i (plus the prior term, as nlml_grad) and its gradient in
@@ -1192,8 +1049,7 @@ class Context:
         observations observation i is predicted from (0 <= p <= i), or -1 = not scored (medgp_amd.forecast.training_prefix builds it
         from times and a horizon); None = every observation from all before it, the chain rule of the likelihood.
         Returns (obj[nbatch], grad[nbatch, H] or None, status[nbatch])."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(slots.shape[0], self.H)
+        slots, theta = self._batch_args(slots, theta)
         nb = slots.shape[0]
         flag = int(flag_grad)
         offsets = prefix = None

@@ -1,5 +1,5 @@
 // call_plan.h -- the plan of a call: internal order, size classes, memory waves, arena offsets and needs, factorisation routes, the
-// look-ahead scratch layout, the chunks of medgp_screen and the grid of the gradient kernels.
+// look-ahead scratch layout, the chunks of medgp_screen, the grid of the gradient kernels and the scatter of per-entry result blocks to the caller's rows.
 // Plain C++ on plain data (no HIP header, no kernel, no context): medgp_capi.hip includes it for the planning functions,
 // kernels_cholinv_la.h for the look-ahead constants, and call_plan_test.cpp compiles it alone with the host compiler, under sanitizers,
 // against brute-force restatements.  This arithmetic decides which memory a workgroup touches.
@@ -7,6 +7,8 @@
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <initializer_list>
+#include <limits>
 #include <vector>
 
 #ifndef MEDGP_HD
@@ -312,4 +314,24 @@ inline void screen_cut(const PlanRules &r, const std::vector<int> &walk_n, int n
         lf = nf; ll = nl; lc = ch.e1 - ch.e0;
     }
     S.cap_mat = cap.mat; S.cap_vec = cap.vec; S.cap_tab = cap.tab; S.cap_part = cap.la_part; S.cap_small = cap.la_small;
+}
+
+// ---- per-entry result blocks, internal order -> the caller's rows -------------------------------------------------------------
+// A call's kernels leave one block of `stride` doubles per entry, in the plan's internal order (entry i at src + i * stride).  A piece
+// of the block -- `count` doubles from offset `off` -- is one row of a caller array `dst` of nbatch rows of `count` doubles (null: the
+// caller did not ask for it).  Entry i is the caller's row order[i]; the rows of an entry whose status (the caller's order, as the
+// calls return it) is negative are NaN.
+struct BlockPiece { size_t off, count; double *dst; };
+inline void scatter_entry_blocks(const int *order, const int *status, int nbatch, const double *src, size_t stride,
+                                 std::initializer_list<BlockPiece> pieces) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int i = 0; i < nbatch; i++) {
+        const int b = order[i];
+        for (const BlockPiece &p : pieces) {
+            if (!p.dst) continue;
+            double *row = p.dst + (size_t)b * p.count;
+            if (status[b] >= 0) std::copy_n(src + (size_t)i * stride + p.off, p.count, row);
+            else std::fill_n(row, p.count, nan);
+        }
+    }
 }

@@ -360,6 +360,29 @@ void test_epilogue_parts() {
 }
 }  // namespace
 
+// scatter_entry_blocks against the loop it replaced: a non-identity order, a failed entry (NaN rows, also where the device left
+// numbers), D = 1 (pieces of one double), a null destination, and exactly-sized destinations (ASan sees a row too many)
+void test_scatter() {
+    for (int D : {1, 2, 5}) {
+        const int nbatch = 4, order[nbatch] = {2, 0, 3, 1}, status[nbatch] = {0, -1, 0, 2};   // (status: the caller's order; 2 = jitter rounds)
+        const size_t stride = 3 + (size_t)D + (size_t)D * D, off_a = 1, off_m = 3 + (size_t)D;
+        std::vector<double> src(nbatch * stride);
+        for (size_t x = 0; x < src.size(); x++) src[x] = 1000.0 + (double)x;
+        std::vector<double> a((size_t)nbatch * D, -1.0), m((size_t)nbatch * D * D, -1.0), one(nbatch, -1.0);
+        scatter_entry_blocks(order, status, nbatch, src.data(), stride,
+                             {{off_a, (size_t)D, a.data()}, {0, 5, nullptr}, {off_m, (size_t)D * D, m.data()}, {0, 1, one.data()}});
+        for (int i = 0; i < nbatch; i++) {
+            const int b = order[i];
+            const bool ok = status[b] >= 0;
+            for (int d = 0; d < D; d++) CHECK(ok ? a[(size_t)b * D + d] == src[i * stride + off_a + d] : a[(size_t)b * D + d] != a[(size_t)b * D + d]);
+            for (int x = 0; x < D * D; x++) CHECK(ok ? m[(size_t)b * D * D + x] == src[i * stride + off_m + x] : m[(size_t)b * D * D + x] != m[(size_t)b * D * D + x]);
+            CHECK(ok ? one[b] == src[i * stride] : one[b] != one[b]);
+        }
+        CHECK(a[(size_t)1 * D] != a[(size_t)1 * D] && one[0] == src[1 * stride]);   // caller row 1 failed; caller row 0 is internal entry 1
+    }
+    scatter_entry_blocks(nullptr, nullptr, 0, nullptr, 0, {{0, 1, nullptr}});   // an empty call touches nothing
+}
+
 int main(int argc, char **argv) {
     std::vector<int> cohort;
     for (int i = 1; i < argc; i++) cohort.push_back(std::atoi(argv[i]));
@@ -372,6 +395,7 @@ int main(int argc, char **argv) {
     test_screen();
     test_wgrad_grid();
     test_epilogue_parts();
+    test_scatter();
     std::printf("call_plan ok (cohort of %d sizes)\n", (int)cohort.size());
     return 0;
 }

@@ -84,7 +84,10 @@ struct Arena {
 // blocks, replaced when a call outgrows them (buf_ensure), freed by free_all.  The calls block and run in stream order, so buffers of
 // one role are shared between them:
 //   per-point inputs / outputs of the call, the tile table, the work rows of one launch chunk (at most posterior_budget bytes unless
-//   one tile needs more; medgp_fit_predict*: the k* rows); the forecast's prefix and y2; lpd (forecast: per point, LOO: per group);
+//   one tile needs more; medgp_fit_predict*: the k* rows) -- BUF_T2, BUF_META2, BUF_MEAN, BUF_VAR, BUF_TILES and BUF_WORK, which every
+//   call that takes test points (or the terms of functionals) fills in ONE step, upload_point_call, reads through launch_pjvp_solve /
+//   for_solved_chunks where it starts from V = L^-1 K*, and brings home through download_pair (unsort_pair where the device's point
+//   order is not the caller's); the forecast's prefix and y2; lpd (forecast: per point, LOO: per group);
 //   joint posterior: the patient / tile-pair / row-block tables of the call, C and the float covariance blocks of one launch chunk, the
 //   call's eps and samples, cov_status -- LOO: its group / tile-pair / job tables, the blocks of one launch chunk, group_status;
 //   LOO: the singleton table and the index lists; BUF_GVEC: the per-entry vectors [u | s | v | log p] of medgp_loo_grad;
@@ -396,6 +399,19 @@ template <class F>
 void launch_tiles(medgp_ctx *c, int kid, int Q, const WgradGrid &wg, F &&f) {
     Launcher l(c, kid);
     with_q16(Q, [&](auto q, auto q0) { f(q, q0, dim3(wg.grid), dim3(WG_THREADS)); });
+}
+// k_wgrad over the tiles of wg for the nb entries of the view V (kernels_wgrad.h), under the caller's Launcher: two launches for 9 .. 16
+// components, each reducing its own components into its own slab planes.  The one home of the prefetch-depth rule: few large patients
+// (the launch fills the chip less than four times) prefetch their operands two chunks ahead and walk the tiles in serpentine order.
+// False: Q > 16, nothing was launched (the nlml gradient then takes its generic route).
+bool launch_wgrad(medgp_ctx *c, hipStream_t stream, const MedgpDev &V, int nb, const WgradGrid &wg) {
+    const int pf = c->wgrad_deep >= 0 ? c->wgrad_deep : ((long)nb * wg.wg_tiles <= 16L * c->rules.num_cu ? 2 : 1);
+    const dim3 tg(wg.grid), tb(WG_THREADS);
+    return with_q16(V.Q, [&](auto q, auto q0) {
+        constexpr int QQ = decltype(q)::value, Q0 = decltype(q0)::value;
+        if (pf >= 2) hipLaunchKernelGGL((k_wgrad<QQ, Q0, 2>), tg, tb, 0, stream, V, nb, wg.wg_tiles, wg.nbp);
+        else hipLaunchKernelGGL((k_wgrad<QQ, Q0, 1>), tg, tb, 0, stream, V, nb, wg.wg_tiles, wg.nbp);
+    });
 }
 
 int drain_events(medgp_ctx *c) {
@@ -734,18 +750,8 @@ int run_pipeline_one(medgp_ctx *c, hipStream_t stream, const MedgpDev &L, int nb
     if (getenv("MEDGP_DBG_NOWGRAD")) { HIPCHK(c, hipGetLastError()); return MEDGP_OK; }
 #endif
     if (flag_grad) {
-        const int wg_tiles = wg.wg_tiles, nbp = wg.nbp;
-        const dim3 tg(wg.grid), tb(WG_THREADS);
         Launcher lw(c, KID_WGRAD, stream);
-        // few large patients (the launch fills the chip less than four times): operand prefetch two chunks ahead + serpentine tile order (kernels_wgrad.h)
-        const int pf = c->wgrad_deep >= 0 ? c->wgrad_deep : ((long)nbatch * wg_tiles <= 16L * c->rules.num_cu ? 2 : 1);
-        // 9 .. 16 components: two launches, each reducing its own components into its own slab planes (kernels_wgrad.h);
-        // Q > 16 (or MEDGP_V0): generic kernels below
-        from_slab = !c->rules.use_v0 && with_q16(L.Q, [&](auto q, auto q0) {
-            constexpr int QQ = decltype(q)::value, Q0 = decltype(q0)::value;
-            if (pf >= 2) hipLaunchKernelGGL((k_wgrad<QQ, Q0, 2>), tg, tb, 0, stream, L, nbatch, wg_tiles, nbp);
-            else hipLaunchKernelGGL((k_wgrad<QQ, Q0, 1>), tg, tb, 0, stream, L, nbatch, wg_tiles, nbp);
-        });
+        from_slab = !c->rules.use_v0 && launch_wgrad(c, stream, L, nbatch, wg);   // Q > 16 (or MEDGP_V0): generic kernels below
         if (!from_slab) lw.kid = -1;   // nothing was launched under this label: its events go back to the pool unread
         lw.finish();
         if (!from_slab) {
@@ -833,33 +839,41 @@ int check_call(medgp_ctx *c, int nbatch, const int32_t *slots) {
     return MEDGP_OK;
 }
 
-// the test points of a call: patient b owns points [offsets[b], offsets[b + 1]) of meta2 / t2 / mean / var (or the two per-point
-// outputs the call requires in their place, named by `outs`)
-int check_points(medgp_ctx *c, int nbatch, const int64_t *offsets, const int32_t *meta2, const float *t2, const float *mean, const float *var,
-                 const char *outs = "mean / var") {
+// ---- what every call that takes test points shares: check_points, stage_points, upload_point_call, launch_pjvp_solve /
+// ---- for_solved_chunks (the calls that start from V = L^-1 K*), download_pair / unsort_pair; call_plan.h: scatter_entry_blocks ------
+// the covariates of n points (or terms) lie in [0, D); SE / SM read none
+int check_meta2(medgp_ctx *c, int64_t n, const int32_t *meta2) {
+    if (!meta2 || c->kidx != MEDGP_KERNEL_LMC_SM) return MEDGP_OK;
+    for (int64_t j = 0; j < n; j++)
+        if (meta2[j] < 0 || meta2[j] >= c->rules.D) return fail(c, MEDGP_ERR_ARG, "meta2[%lld] = %d outside [0, %d)", (long long)j, meta2[j], c->rules.D);
+    return MEDGP_OK;
+}
+
+// The test points of a call: patient b owns points [offsets[b], offsets[b + 1]) of meta2 / t2 and of the call's per-point arrays.
+// Returns their number M, or the (negative) error code.  missing: one of the per-point arrays the call REQUIRES is null, `outs` names
+// them for the message; outs null: the call's per-point outputs are optional and t2 alone is named.
+int64_t check_points(medgp_ctx *c, int nbatch, const int64_t *offsets, const int32_t *meta2, const float *t2, bool missing, const char *outs) {
     if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
     for (int b = 0; b < nbatch; b++)
         if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
     const int64_t M = offsets[nbatch];
     if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
-    if (M > 0 && (!t2 || !mean || !var)) return fail(c, MEDGP_ERR_ARG, "t2 / %s is NULL", outs);
+    if (M > 0 && (!t2 || missing)) return outs ? fail(c, MEDGP_ERR_ARG, "t2 / %s is NULL", outs) : fail(c, MEDGP_ERR_ARG, "t2 is NULL");
     if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
-    return MEDGP_OK;
+    const int rc = check_meta2(c, M, meta2);
+    return rc ? rc : M;
 }
 
-// the M test points as the device takes them (double times, int outputs): device point k is the caller's point src[k] (null: k)
-int stage_points(medgp_ctx *c, int64_t M, const int32_t *meta2, const float *t2, const int64_t *src, std::vector<double> &ht2, std::vector<int> &hm2) {
+// the M checked test points as the device takes them (double times, int outputs): device point k is the caller's point src[k] (null: k)
+void stage_points(medgp_ctx *c, int64_t M, const int32_t *meta2, const float *t2, const int64_t *src, std::vector<double> &ht2, std::vector<int> &hm2) {
     ht2.resize(M);
     hm2.assign(M, 0);
+    const bool lmc = meta2 && c->kidx == MEDGP_KERNEL_LMC_SM;
     for (int64_t k = 0; k < M; k++) {
         const int64_t j = src ? src[k] : k;
         ht2[k] = (double)t2[j];
-        if (meta2 && c->kidx == MEDGP_KERNEL_LMC_SM) {
-            if (meta2[j] < 0 || meta2[j] >= c->rules.D) return fail(c, MEDGP_ERR_ARG, "meta2[%lld] = %d outside [0, %d)", (long long)j, meta2[j], c->rules.D);
-            hm2[k] = meta2[j];
-        }
+        if (lmc) hm2[k] = meta2[j];
     }
-    return MEDGP_OK;
 }
 
 // theta to the device and the ONE pipeline run of an inference call: factor and z = L^-1 y of every entry, with U = L^-T and
@@ -889,21 +903,6 @@ std::vector<TableClass> table_classes(const BatchPlan &P) {
     for (const SizeClass &k : P.cls) v.push_back({k.b0, k.count, k.ld});
     return v;
 }
-// the per-point buffers of a posterior / forecast call of M points, and the staged points on their way into them
-int upload_points(medgp_ctx *c, int64_t M, const std::vector<double> &ht2, const std::vector<int> &hm2) {
-    const size_t Mz = (size_t)std::max<int64_t>(M, 1);
-    int rc;
-    if ((rc = buf_ensure(c, BUF_T2, Mz * sizeof(double)))) return rc;
-    if ((rc = buf_ensure(c, BUF_META2, Mz * sizeof(int)))) return rc;
-    if ((rc = buf_ensure(c, BUF_MEAN, Mz * sizeof(float)))) return rc;
-    if ((rc = buf_ensure(c, BUF_VAR, Mz * sizeof(float)))) return rc;
-    if (M > 0) {
-        HIPCHK(c, hipMemcpyAsync(buf<double>(c, BUF_T2), ht2.data(), sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(buf<int>(c, BUF_META2), hm2.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
-    }
-    return MEDGP_OK;
-}
-
 // host table -> buffer `id` (grown as needed); an empty table uploads nothing
 template <class T>
 int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
@@ -914,8 +913,68 @@ int upload_table(medgp_ctx *c, int id, const std::vector<T> &v) {
     return MEDGP_OK;
 }
 
+// The upload step of a call of M points: the per-point buffers (BUF_T2, BUF_META2, BUF_MEAN, BUF_VAR) and the staged points on their
+// way into them, the tile table into BUF_TILES and work_need bytes of work rows in BUF_WORK.  A call without tiles still gets a
+// BUF_WORK block (buf_ensure's 256-byte minimum: the kernels of medgp_posterior_vjp_batch take the pointer even then); for the other
+// calls that is one small allocation on a context that never had points, nothing on any later call.
+template <class Tile>
+int upload_point_call(medgp_ctx *c, int64_t M, const std::vector<double> &ht2, const std::vector<int> &hm2, const std::vector<Tile> &tiles,
+                      size_t work_need) {
+    const size_t Mz = (size_t)std::max<int64_t>(M, 1);
+    int rc;
+    if ((rc = buf_ensure(c, BUF_T2, Mz * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_META2, Mz * sizeof(int)))) return rc;
+    if ((rc = buf_ensure(c, BUF_MEAN, Mz * sizeof(float)))) return rc;
+    if ((rc = buf_ensure(c, BUF_VAR, Mz * sizeof(float)))) return rc;
+    if (M > 0) {
+        HIPCHK(c, hipMemcpyAsync(buf<double>(c, BUF_T2), ht2.data(), sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(buf<int>(c, BUF_META2), hm2.data(), sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
+    }
+    if ((rc = upload_table(c, BUF_TILES, tiles))) return rc;
+    return buf_ensure(c, BUF_WORK, work_need);   // (0 for a call without tiles)
+}
+
+// k_pjvp_solve on nt tiles of the view V (kernels_posterior_jvp.h): W = P K* and V = L^-1 K* into the tiles' work rows, the fp32 mean
+// and var into BUF_MEAN / BUF_VAR.  nvec = 0 (and null pointers): no derivative output is touched.
+void launch_pjvp_solve(medgp_ctx *c, const MedgpDev &V, const PostTile *tiles, int nt, size_t stride, int nvec, double *d_dmean, double *d_dvar) {
+    Launcher l(c, KID_PJ_SOLVE);
+    hipLaunchKernelGGL(k_pjvp_solve, dim3(nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK),
+                       stride, nvec, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), d_dmean, d_dvar);
+}
+// "solve, then the family's kernel": per launch chunk of T (build_pjvp_tiles), in stream order -- the chunks reuse the work rows --
+// k_pjvp_solve with nvec = 0, then f(chunk, its size class, the class view, its tiles on the device) launches what reads V
+template <class F>
+void for_solved_chunks(medgp_ctx *c, const BatchPlan &P, const PointTables<PostTile> &T, F &&f) {
+    for (const TileChunk &ch : T.chunks) {
+        const SizeClass &k = P.cls[ch.cls];
+        const MedgpDev V = class_view(c, P, k);
+        const PostTile *tiles = buf<PostTile>(c, BUF_TILES) + ch.t0;
+        launch_pjvp_solve(c, V, tiles, ch.nt, ch.stride, 0, nullptr, nullptr);
+        f(ch, k, V, tiles);
+    }
+}
+
+// Two per-point arrays of n values each (fp32 [mean | var] from BUF_MEAN / BUF_VAR, an fp64 pair from a buffer of the call) on their
+// way home; a call without points, or one the caller wants nothing of (a null), queues nothing.  sorted: the device's point order is
+// not the caller's (forecast, VJP) -- the values land there, and once the stream has been waited for unsort_pair carries value k to the
+// caller's point src[k].
+template <class T>
+int download_pair(medgp_ctx *c, int64_t n, const T *d_a, const T *d_b, T *a, T *b, std::vector<T> *sorted = nullptr) {
+    if (n <= 0 || !a) return MEDGP_OK;
+    if (sorted) { sorted->resize(2 * (size_t)n); a = sorted->data(); b = a + n; }
+    HIPCHK(c, hipMemcpyAsync(a, d_a, sizeof(T) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b, d_b, sizeof(T) * n, hipMemcpyDeviceToHost, c->stream));
+    return MEDGP_OK;
+}
+template <class T>
+void unsort_pair(const std::vector<T> &sorted, const int64_t *src, T *a, T *b) {
+    const size_t n = sorted.size() / 2;
+    for (size_t k = 0; k < n; k++) { a[src[k]] = sorted[k]; b[src[k]] = sorted[n + k]; }
+}
+
 // ---- what the derivative entry points share on top of that (the gradient objectives, Fisher / Hessian products, posterior JVP / VJP,
-// ---- the baseline and basis calls; launch_slabsum, launch_epilogue, finish_objective_class and launch_tiles stand next to Launcher) --
+// ---- the baseline, basis and warp calls; launch_slabsum, launch_epilogue, finish_objective_class, launch_tiles and launch_wgrad stand
+// ---- next to Launcher; the test-point side of the calls that have one is the block above: check_points ... unsort_pair) ----------
 // The tile kernels of these calls are instantiated for Q <= 16 only.  why: what the generic route would break in the call (null: nothing said).
 static_assert(PJVP_MAX_Q == 16, "the column tables of the JVP / VJP tile kernels are sized for what check_q16 lets through");
 int check_q16(medgp_ctx *c, const char *who, const char *why) {
@@ -1810,17 +1869,13 @@ static int fit_predict_impl(medgp_ctx *c, int nbatch, const int32_t *slots, cons
     const int ntot = nbatch * nstar;
     std::vector<double> ht2;
     std::vector<int> hm2;
-    if ((rc = stage_points(c, ntot, meta2, t2, nullptr, ht2, hm2))) return rc;
-    if ((rc = buf_ensure(c, BUF_T2, ntot * sizeof(double)))) return rc;
-    if ((rc = buf_ensure(c, BUF_META2, ntot * sizeof(int)))) return rc;
-    if ((rc = buf_ensure(c, BUF_MEAN, ntot * sizeof(float)))) return rc;
-    if ((rc = buf_ensure(c, BUF_VAR, ntot * sizeof(float)))) return rc;
-    if ((rc = buf_ensure(c, BUF_WORK, (size_t)ntot * c->ldn * sizeof(double)))) return rc;   // k* -> v = L^-1 k* work rows
+    if ((rc = check_meta2(c, ntot, meta2))) return rc;
+    stage_points(c, ntot, meta2, t2, nullptr, ht2, hm2);
+    // (no tile table: one workgroup of k_predict per point; its work rows are k* -> v = L^-1 k*, one column per point)
+    if ((rc = upload_point_call(c, ntot, ht2, hm2, std::vector<PostTile>(), (size_t)ntot * c->ldn * sizeof(double)))) return rc;
     // patients are used in the caller's order when that differs from the grouped one?  No: mean / var are permutation
     // invariant, the grouped copy serves.
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;   // (the diagonal blocks U_kk live in Linv)
-    HIPCHK(c, hipMemcpyAsync(buf<double>(c, BUF_T2), ht2.data(), sizeof(double) * ntot, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(buf<int>(c, BUF_META2), hm2.data(), sizeof(int) * ntot, hipMemcpyHostToDevice, c->stream));
     // factor + z = L^-1 y only (no inverse): k* rides along as one more right-hand side in k_predict
     if ((rc = factor_run(c, nbatch, theta, false, true))) return rc;
     for (const SizeClass &k : c->plan.cls) {   // (behind the join of the classes' chains: one launch per class view)
@@ -1829,8 +1884,7 @@ static int fit_predict_impl(medgp_ctx *c, int nbatch, const int32_t *slots, cons
                            buf<double>(c, BUF_WORK), buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR));
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(mean, buf<float>(c, BUF_MEAN), sizeof(float) * ntot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(var, buf<float>(c, BUF_VAR), sizeof(float) * ntot, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = download_pair(c, ntot, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), mean, var))) return rc;
     return read_status(c, nbatch, status);
 }
 
@@ -1969,8 +2023,8 @@ int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     if (!slots || !theta || !offsets || nbatch < 1) return fail(c, MEDGP_ERR_ARG, "bad argument");
     int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
-    if ((rc = check_points(c, nbatch, offsets, meta2, t2, mean, var))) return rc;
-    const int64_t M = offsets[nbatch];
+    const int64_t M = check_points(c, nbatch, offsets, meta2, t2, !mean || !var, "mean / var");
+    if (M < 0) return (int)M;
     const bool want_cov = jq && jq->cov, want_samp = jq && jq->nsamp > 0;
     if (jq) {
         if (jq->nsamp < 0) return fail(c, MEDGP_ERR_ARG, "nsamp = %d", jq->nsamp);
@@ -1983,7 +2037,7 @@ int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     if (want_cov) { size_t o = 0; for (int b = 0; b < nbatch; b++) { cov_off[b] = o; const size_t m = (size_t)(offsets[b + 1] - offsets[b]); o += m * m; } }
     std::vector<double> ht2;
     std::vector<int> hm2;
-    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
+    stage_points(c, M, meta2, t2, nullptr, ht2, hm2);
     HIPCHK(c, hipSetDevice(c->device));
     // the parts, like mean and var, are invariant under a permutation of the training observations: the grouped copy serves
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
@@ -1998,10 +2052,8 @@ int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
             return fail(c, MEDGP_ERR_CAPACITY, "patient %d: the joint posterior of %lld points on %d observations needs %zu MB at once, the budget is %zu MB (MEDGP_POSTERIOR_BUDGET_GB)",
                         e.b, e.m, c->plan.en[e.entry], e.need >> 20, c->posterior_budget >> 20);
     }
-    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if ((rc = upload_point_call(c, M, ht2, hm2, T.tiles, T.work_need))) return rc;
     if (with_parts && (rc = buf_ensure(c, BUF_PARTS, (size_t)std::max<int64_t>(M, 1) * D * sizeof(float)))) return rc;
-    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
-    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
     if (jq) {
         if ((rc = buf_ensure(c, BUF_CSTAT, sizeof(int) * nbatch))) return rc;
         HIPCHK(c, hipMemsetAsync(buf<int>(c, BUF_CSTAT), 0, sizeof(int) * nbatch, c->stream));
@@ -2055,9 +2107,8 @@ int posterior_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
             }
     }
     HIPCHK(c, hipGetLastError());
+    if ((rc = download_pair(c, M, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), mean, var))) return rc;
     if (M > 0) {
-        HIPCHK(c, hipMemcpyAsync(mean, buf<float>(c, BUF_MEAN), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(var, buf<float>(c, BUF_VAR), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
         if (with_parts) HIPCHK(c, hipMemcpyAsync(parts, buf<float>(c, BUF_PARTS), sizeof(float) * M * D, hipMemcpyDeviceToHost, c->stream));
         if (want_samp) HIPCHK(c, hipMemcpyAsync(jq->samples, buf<float>(c, BUF_SAMP), sizeof(float) * (size_t)M * jq->nsamp, hipMemcpyDeviceToHost, c->stream));
     }
@@ -2079,8 +2130,8 @@ int forecast_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *
     if ((y2 == nullptr) != (lpd == nullptr)) return fail(c, MEDGP_ERR_ARG, "y2 and lpd must both be given or both be NULL");
     int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
-    if ((rc = check_points(c, nbatch, offsets, meta2, t2, mean, var))) return rc;
-    const int64_t M = offsets[nbatch];
+    const int64_t M = check_points(c, nbatch, offsets, meta2, t2, !mean || !var, "mean / var");
+    if (M < 0) return (int)M;
     // the device order of the points: inside each patient stably sorted by prefix (src[k] = the caller's index of device point k)
     std::vector<int64_t> src(M);
     std::vector<int> hpf(M);
@@ -2097,7 +2148,7 @@ int forecast_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *
     }
     std::vector<double> ht2, hy2(y2 ? M : 0);
     std::vector<int> hm2;
-    if ((rc = stage_points(c, M, meta2, t2, src.data(), ht2, hm2))) return rc;
+    stage_points(c, M, meta2, t2, src.data(), ht2, hm2);
     for (int64_t k = 0; y2 && k < M; k++) hy2[k] = (double)y2[src[k]];
     HIPCHK(c, hipSetDevice(c->device));
     // "the first p observations" is the caller's order: a patient not uploaded grouped by output is factored on its caller-order copy
@@ -2106,12 +2157,10 @@ int forecast_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *
     static_assert(sizeof(ForeTile) == sizeof(PostTile), "the forecast tiles travel in the posterior call's tile buffer");
     PointTables<ForeTile> T;
     build_point_tiles(table_classes(c->plan), c->plan.order.data(), offsets, hpf.data(), 0, c->posterior_budget, T);
-    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if ((rc = upload_point_call(c, M, ht2, hm2, T.tiles, T.work_need))) return rc;
     if ((rc = upload_table(c, BUF_PREFIX, hpf))) return rc;
     if (y2 && (rc = upload_table(c, BUF_Y2, hy2))) return rc;
     if (y2 && (rc = buf_ensure(c, BUF_LPD, (size_t)std::max<int64_t>(M, 1) * sizeof(double)))) return rc;
-    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
-    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
     // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
     if ((rc = factor_run(c, nbatch, theta, false, true))) return rc;
     const double log2pi = std::log(2.0 * c->pi);
@@ -2120,19 +2169,13 @@ int forecast_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *
         launch_forecast(c, class_view(c, c->plan, c->plan.cls[ch.cls]), ch.nt, buf<ForeTile>(c, BUF_TILES) + ch.t0, ch.stride, y2 != nullptr, log2pi);
     }
     HIPCHK(c, hipGetLastError());
-    std::vector<float> hmean(M), hvar(M);
+    std::vector<float> hmv;
     std::vector<double> hlpd(y2 ? M : 0);
-    if (M > 0) {
-        HIPCHK(c, hipMemcpyAsync(hmean.data(), buf<float>(c, BUF_MEAN), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(hvar.data(), buf<float>(c, BUF_VAR), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        if (y2) HIPCHK(c, hipMemcpyAsync(hlpd.data(), buf<double>(c, BUF_LPD), sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
-    }
+    if ((rc = download_pair(c, M, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), mean, var, &hmv))) return rc;
+    if (M > 0 && y2) HIPCHK(c, hipMemcpyAsync(hlpd.data(), buf<double>(c, BUF_LPD), sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
     if ((rc = read_status(c, nbatch, status))) return rc;
-    for (int64_t k = 0; k < M; k++) {   // sorted order -> the caller's
-        mean[src[k]] = hmean[k];
-        var[src[k]] = hvar[k];
-        if (y2) lpd[src[k]] = hlpd[k];
-    }
+    unsort_pair(hmv, src.data(), mean, var);   // sorted order -> the caller's
+    for (int64_t k = 0; y2 && k < M; k++) lpd[src[k]] = hlpd[k];
     return MEDGP_OK;
 }
 
@@ -2145,21 +2188,19 @@ int trend_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *the
     if (!dmean || !dvar) return fail(c, MEDGP_ERR_ARG, "dmean / dvar is NULL");
     int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
-    if ((rc = check_points(c, nbatch, offsets, meta2, t2, mean, var))) return rc;
-    const int64_t M = offsets[nbatch];
+    const int64_t M = check_points(c, nbatch, offsets, meta2, t2, !mean || !var, "mean / var");
+    if (M < 0) return (int)M;
     const size_t Mz = (size_t)std::max<int64_t>(M, 1);
     std::vector<double> ht2;
     std::vector<int> hm2;
-    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
+    stage_points(c, M, meta2, t2, nullptr, ht2, hm2);
     HIPCHK(c, hipSetDevice(c->device));
     // the five outputs are invariant under a permutation of the training observations: the grouped copy serves, as for the posterior
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     PointTables<PostTile> T;
     build_trend_tiles(table_classes(c->plan), c->plan.order.data(), offsets, c->posterior_budget, T);
-    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if ((rc = upload_point_call(c, M, ht2, hm2, T.tiles, T.work_need))) return rc;
     if ((rc = buf_ensure(c, BUF_SLOPE, 3 * Mz * sizeof(float)))) return rc;
-    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
-    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
     // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
     if ((rc = factor_run(c, nbatch, theta, false, true))) return rc;
     float *d_dmean = buf<float>(c, BUF_SLOPE), *d_dvar = d_dmean + Mz, *d_cross = d_dvar + Mz;
@@ -2173,13 +2214,9 @@ int trend_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *the
         });
     }
     HIPCHK(c, hipGetLastError());
-    if (M > 0) {
-        HIPCHK(c, hipMemcpyAsync(mean, buf<float>(c, BUF_MEAN), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(var, buf<float>(c, BUF_VAR), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dmean, d_dmean, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dvar, d_dvar, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        if (cross) HIPCHK(c, hipMemcpyAsync(cross, d_cross, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-    }
+    if ((rc = download_pair(c, M, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), mean, var))) return rc;
+    if ((rc = download_pair<float>(c, M, d_dmean, d_dvar, dmean, dvar))) return rc;
+    if (M > 0 && cross) HIPCHK(c, hipMemcpyAsync(cross, d_cross, sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
     return read_status(c, nbatch, status);
 }
 
@@ -2195,21 +2232,19 @@ int components_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     if (Q > 64) return fail(c, MEDGP_ERR_ARG, "medgp_components_batch supports Q <= 64 (Q = %d): the component columns of a point share one 64-column tile", Q);
     int rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
-    if ((rc = check_points(c, nbatch, offsets, meta2, t2, cmean, cvar, "cmean / cvar"))) return rc;
-    const int64_t M = offsets[nbatch];
+    const int64_t M = check_points(c, nbatch, offsets, meta2, t2, false, "cmean / cvar");   // (cmean / cvar: checked above)
+    if (M < 0) return (int)M;
     const size_t MQ = (size_t)std::max<int64_t>(M, 1) * Q;
     std::vector<double> ht2;
     std::vector<int> hm2;
-    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
+    stage_points(c, M, meta2, t2, nullptr, ht2, hm2);
     HIPCHK(c, hipSetDevice(c->device));
     // the outputs are invariant under a permutation of the training observations: the grouped copy serves, as for the posterior
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     PointTables<PostTile> T;
     build_components_tiles(table_classes(c->plan), c->plan.order.data(), offsets, Q, ccov != nullptr, c->posterior_budget, T);
-    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
+    if ((rc = upload_point_call(c, M, ht2, hm2, T.tiles, T.work_need))) return rc;
     if ((rc = buf_ensure(c, BUF_COMP, MQ * (2 + (ccov ? (size_t)Q : 0)) * sizeof(float)))) return rc;
-    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
-    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
     // factor + z = L^-1 y + the diagonal-block inverses U_kk (no inverse): the ONE pipeline run of the call
     if ((rc = factor_run(c, nbatch, theta, false, true))) return rc;
     float *d_cmean = buf<float>(c, BUF_COMP), *d_cvar = d_cmean + MQ, *d_ccov = d_cvar + MQ;
@@ -2220,11 +2255,8 @@ int components_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
                            d_cmean, d_cvar, ccov ? d_ccov : nullptr);
     }
     HIPCHK(c, hipGetLastError());
-    if (M > 0) {
-        HIPCHK(c, hipMemcpyAsync(cmean, d_cmean, sizeof(float) * M * Q, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(cvar, d_cvar, sizeof(float) * M * Q, hipMemcpyDeviceToHost, c->stream));
-        if (ccov) HIPCHK(c, hipMemcpyAsync(ccov, d_ccov, sizeof(float) * M * Q * Q, hipMemcpyDeviceToHost, c->stream));
-    }
+    if ((rc = download_pair<float>(c, M * Q, d_cmean, d_cvar, cmean, cvar))) return rc;
+    if (M > 0 && ccov) HIPCHK(c, hipMemcpyAsync(ccov, d_ccov, sizeof(float) * M * Q * Q, hipMemcpyDeviceToHost, c->stream));
     return read_status(c, nbatch, status);
 }
 
@@ -2262,7 +2294,8 @@ int functional_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     const size_t Fz = (size_t)std::max<int64_t>(F, 1), Tz = (size_t)std::max<int64_t>(Tn, 1), Q = (size_t)c->rules.Q;
     std::vector<double> ht2;
     std::vector<int> hm2;
-    if ((rc = stage_points(c, Tn, meta2, t2, nullptr, ht2, hm2))) return rc;   // (the terms' covariates are range-checked as the posterior call's points)
+    if ((rc = check_meta2(c, Tn, meta2))) return rc;   // (the terms' covariates are range-checked as the posterior call's points)
+    stage_points(c, Tn, meta2, t2, nullptr, ht2, hm2);
     HIPCHK(c, hipSetDevice(c->device));
     // the outputs are invariant under a permutation of the training observations: the grouped copy serves, as for the posterior
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
@@ -2277,7 +2310,7 @@ int functional_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
     }
     std::vector<size_t> cov_off(joint ? nbatch : 0);   // start of patient b's block in fcov (floats)
     if (joint) { size_t o = 0; for (int b = 0; b < nbatch; b++) { cov_off[b] = o; const size_t Fb = (size_t)(foffsets[b + 1] - foffsets[b]); o += Fb * Fb; } }
-    if ((rc = upload_points(c, Tn, ht2, hm2))) return rc;
+    if ((rc = upload_point_call(c, Tn, ht2, hm2, T.tiles, T.work_need))) return rc;
     if ((rc = buf_ensure(c, BUF_MEAN, Fz * sizeof(float)))) return rc;   // (per functional, not per term)
     if ((rc = buf_ensure(c, BUF_VAR, Fz * sizeof(float)))) return rc;
     if ((rc = buf_ensure(c, BUF_FUNC_D, (2 * Tz + Fz + 2 * Tz * Q) * sizeof(double)))) return rc;
@@ -2289,8 +2322,6 @@ int functional_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
         HIPCHK(c, hipMemcpyAsync(d_w, weight, sizeof(double) * Tn, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(d_fun, S.fun.data(), sizeof(int) * Tn, hipMemcpyHostToDevice, c->stream));
     }
-    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
-    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
     if (joint && !T.pats.empty()) {
         if ((rc = upload_table(c, BUF_PATS, T.pats))) return rc;
         if ((rc = upload_table(c, BUF_PAIRS, T.pairs))) return rc;
@@ -2324,10 +2355,7 @@ int functional_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double
         }
     }
     HIPCHK(c, hipGetLastError());
-    if (F > 0) {
-        HIPCHK(c, hipMemcpyAsync(fmean, buf<float>(c, BUF_MEAN), sizeof(float) * F, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(fvar, buf<float>(c, BUF_VAR), sizeof(float) * F, hipMemcpyDeviceToHost, c->stream));
-    }
+    if ((rc = download_pair(c, F, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), fmean, fvar))) return rc;
     return read_status(c, nbatch, status);
 }
 }  // namespace
@@ -2817,11 +2845,11 @@ int medgp_posterior_jvp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
     if ((rc = check_q16(c, "medgp_posterior_jvp_batch", nullptr))) return rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
     // (mean / var are optional here: the per-point outputs the call requires are dmean / dvar, checked above)
-    if ((rc = check_points(c, nbatch, offsets, meta2, t2, (const float *)dmean, (const float *)dvar, "dmean / dvar"))) return rc;
-    const int64_t M = offsets[nbatch];
+    const int64_t M = check_points(c, nbatch, offsets, meta2, t2, false, "dmean / dvar");
+    if (M < 0) return (int)M;
     std::vector<double> ht2;
     std::vector<int> hm2;
-    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
+    stage_points(c, M, meta2, t2, nullptr, ht2, hm2);
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const BatchPlan &P = c->plan;
@@ -2830,9 +2858,7 @@ int medgp_posterior_jvp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
     const PjvpBuffers pb = pjvp_buffers(P.need_mat, P.need_vec, nbatch, nvec, (int)H, c->rules.Q, c->rules.D, M);
     PointTables<PostTile> T;
     build_pjvp_tiles(table_classes(P), P.order.data(), offsets, c->posterior_budget, T);
-    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
-    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
-    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
+    if ((rc = upload_point_call(c, M, ht2, hm2, T.tiles, T.work_need))) return rc;
     if ((rc = buf_ensure(c, BUF_FI_KDOT, pb.mat_doubles * sizeof(double)))) return rc;
     if ((rc = buf_ensure(c, BUF_FI_COEF, pb.coef_doubles * sizeof(double)))) return rc;
     if ((rc = buf_ensure(c, BUF_FI_DIR, pb.dir_doubles * sizeof(double)))) return rc;
@@ -2848,11 +2874,7 @@ int medgp_posterior_jvp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
         const int nb = k.count, nt64 = k.nbmax;
         const PostTile *tiles = buf<PostTile>(c, BUF_TILES) + ch.t0;
         double *Kd = kdot + k.off_mat, *cf = coef + (size_t)k.b0 * V.hyp_stride, *u = uvec + k.off_vec;
-        {
-            Launcher l(c, KID_PJ_SOLVE);
-            hipLaunchKernelGGL(k_pjvp_solve, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK),
-                               ch.stride, nvec, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), d_dmean, d_dvar);
-        }
+        launch_pjvp_solve(c, V, tiles, ch.nt, ch.stride, nvec, d_dmean, d_dvar);
         for (int j = 0; j < nvec; j++) {
             launch_kdot(c, V, k, d_dir, nvec, j, cf, Kd);
             { Launcher l(c, KID_PJ_U); hipLaunchKernelGGL(k_pjvp_u, dim3(pjvp_u_grid(nt64), nb), dim3(256), 0, c->stream, V, Kd, u); }
@@ -2862,15 +2884,8 @@ int medgp_posterior_jvp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
         }
     }
     HIPCHK(c, hipGetLastError());
-    if (M > 0) {
-        const size_t nout = (size_t)M * nvec;
-        HIPCHK(c, hipMemcpyAsync(dmean, d_dmean, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dvar, d_dvar, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
-        if (mean) {
-            HIPCHK(c, hipMemcpyAsync(mean, buf<float>(c, BUF_MEAN), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(var, buf<float>(c, BUF_VAR), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        }
-    }
+    if ((rc = download_pair<double>(c, M * nvec, d_dmean, d_dvar, dmean, dvar))) return rc;
+    if ((rc = download_pair(c, M, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), mean, var))) return rc;
     return read_status(c, nbatch, status);
 }
 
@@ -2899,15 +2914,12 @@ int medgp_posterior_vjp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
     int rc;
     if ((rc = check_q16(c, "medgp_posterior_vjp_batch", nullptr))) return rc;
     if ((rc = check_call(c, nbatch, slots))) return rc;
-    // (mean / var are optional here: the per-point inputs the call requires stand in their place)
-    const float *need_a = (const float *)(builtin ? y2 : cot_mean), *need_b = (const float *)(builtin ? y2 : cot_var);
-    if ((rc = check_points(c, nbatch, offsets, meta2, t2, need_a, need_b, builtin ? "y2" : "cot_mean / cot_var"))) return rc;
-    const int64_t M = offsets[nbatch];
+    // (mean / var are optional here; the per-point inputs the call requires, named for the message, were checked above; the covariates
+    //  are range-checked here, before the tables sort by them)
+    const int64_t M = check_points(c, nbatch, offsets, meta2, t2, false, builtin ? "y2" : "cot_mean / cot_var");
+    if (M < 0) return (int)M;
     const int D = c->rules.D, Q = c->rules.Q;
     const bool lmc = c->kidx == MEDGP_KERNEL_LMC_SM;
-    if (lmc && meta2)
-        for (int64_t j = 0; j < M; j++)
-            if (meta2[j] < 0 || meta2[j] >= D) return fail(c, MEDGP_ERR_ARG, "meta2[%lld] = %d outside [0, %d)", (long long)j, meta2[j], D);
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
     const BatchPlan &P = c->plan;
@@ -2919,7 +2931,7 @@ int medgp_posterior_vjp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
                     terr.b, terr.m, terr.need >> 20, c->posterior_budget >> 20);
     std::vector<double> ht2;
     std::vector<int> hm2;
-    if ((rc = stage_points(c, M, meta2, t2, T.src.data(), ht2, hm2))) return rc;
+    stage_points(c, M, meta2, t2, T.src.data(), ht2, hm2);
     const size_t H = c->H, Mz = pvjp_mz(M);
     const PvjpBuffers pb = pvjp_buffers(P.need_vec, nbatch, ncot, (int)H, Q, D, M);
     // the caller's per-point inputs in the device's point order, the cotangent sets set-major
@@ -2935,15 +2947,12 @@ int medgp_posterior_vjp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
                 hin[((size_t)ncot + s) * Mz + (size_t)k] = cot_var[(size_t)j * ncot + s];
             }
     }
-    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
-    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
+    if ((rc = upload_point_call(c, M, ht2, hm2, T.tiles, T.work_need))) return rc;
     if ((rc = upload_table(c, BUF_PV_ENT, T.ents))) return rc;
     if ((rc = upload_table(c, BUF_PV_SEG, T.pseg))) return rc;
     if ((rc = upload_table(c, BUF_PV_ORD, T.dev_of))) return rc;
     if ((rc = upload_table(c, BUF_PV_IN, hin))) return rc;
-    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
-    if ((rc = buf_ensure(c, BUF_WORK, 256))) return rc;   // (a call without points: the kernels still take the pointer)
-    if ((rc = buf_ensure(c, BUF_PV_ORD, sizeof(int)))) return rc;
+    if ((rc = buf_ensure(c, BUF_PV_ORD, sizeof(int)))) return rc;   // (a call without points: the kernels still take the pointer)
     if ((rc = buf_ensure(c, BUF_PV_PTS, pb.pts_doubles * sizeof(double)))) return rc;
     if ((rc = buf_ensure(c, BUF_PV_VEC, pb.vec_doubles * sizeof(double)))) return rc;
     if ((rc = buf_ensure(c, BUF_PV_SMALL, pb.small_doubles * sizeof(double)))) return rc;
@@ -2963,11 +2972,7 @@ int medgp_posterior_vjp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
         const size_t row0 = Vc.bpos ? 0 : (size_t)ch.e0;
         const PvjpEnt *ents = d_ents + k.b0 + ch.e0;
         double *small = d_small + (size_t)(k.b0 + ch.e0) * (D + 2), *cvec = d_cvec + k.off_vec + (size_t)ch.e0 * k.ld;
-        if (ch.nt > 0) {
-            Launcher l(c, KID_PJ_SOLVE);   // (nvec = 0: no derivative output is touched)
-            hipLaunchKernelGGL(k_pjvp_solve, dim3(ch.nt), dim3(256), 0, c->stream, V, buf<PostTile>(c, BUF_TILES) + ch.t0, d_meta2, d_t2, d_work, ch.stride, 0,
-                               buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), (double *)nullptr, (double *)nullptr);
-        }
+        if (ch.nt > 0) launch_pjvp_solve(c, V, buf<PostTile>(c, BUF_TILES) + ch.t0, ch.nt, ch.stride, 0, nullptr, nullptr);
         const WgradGrid wg = wgrad_grid(P.en.data() + k.b0 + ch.e0, nb, nt64);
         for (int s = 0; s < ncot; s++) {
             double *g = d_out + ((size_t)s * nbatch + row0) * H;
@@ -2992,21 +2997,18 @@ int medgp_posterior_vjp_batch(medgp_ctx *c, int nbatch, const int32_t *slots, co
     }
     HIPCHK(c, hipGetLastError());
     std::vector<double> out, hsmall(pb.small_doubles);
-    std::vector<float> hmean, hvar;
+    std::vector<float> hmv;
+    std::vector<int32_t> st(nbatch);
     if ((rc = download_directions(c, d_out, pb.out_doubles, out))) return rc;
     if (builtin) HIPCHK(c, hipMemcpyAsync(hsmall.data(), d_small, pb.small_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (M > 0 && mean) {
-        hmean.resize((size_t)M); hvar.resize((size_t)M);
-        HIPCHK(c, hipMemcpyAsync(hmean.data(), buf<float>(c, BUF_MEAN), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(hvar.data(), buf<float>(c, BUF_VAR), sizeof(float) * M, hipMemcpyDeviceToHost, c->stream));
-    }
-    if ((rc = read_status(c, nbatch, status))) return rc;
+    if ((rc = download_pair(c, M, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), mean, var, &hmv))) return rc;
+    if ((rc = read_status(c, nbatch, st.data()))) return rc;
     free_retired(c);
     transpose_directions(out, nbatch, ncot, H, grad);
-    if (builtin)
-        for (int i = 0; i < nbatch; i++) loss[P.order[i]] = hsmall[(size_t)i * (D + 2) + D];
-    if (M > 0 && mean)
-        for (int64_t k = 0; k < M; k++) { mean[T.src[(size_t)k]] = hmean[(size_t)k]; var[T.src[(size_t)k]] = hvar[(size_t)k]; }
+    // (the loss of a failed entry is the NaN k_pvjp_cot left in its block: the scatter's NaN has the same bits)
+    if (builtin) scatter_entry_blocks(P.order.data(), st.data(), nbatch, hsmall.data(), (size_t)D + 2, {{(size_t)D, 1, loss}});
+    unsort_pair(hmv, T.src.data(), mean, var);
+    if (status) std::memcpy(status, st.data(), sizeof(int32_t) * nbatch);
     c->pv_src = std::move(T.src);
     c->pv_valid = true;
     return MEDGP_OK;
@@ -3024,7 +3026,7 @@ int medgp_posterior_vjp_moments(medgp_ctx *c, int64_t M, double *mean, double *v
     const double *d = buf<double>(c, BUF_PV_PTS) + pvjp_moments_offset(c->rules.Q, M);
     HIPCHK(c, hipMemcpyAsync(h.data(), d, 2 * (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int64_t k = 0; k < M; k++) { mean[c->pv_src[(size_t)k]] = h[(size_t)k]; var[c->pv_src[(size_t)k]] = h[(size_t)M + (size_t)k]; }
+    unsort_pair(h, c->pv_src.data(), mean, var);
     return MEDGP_OK;
 }
 
@@ -3119,19 +3121,9 @@ int mean_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots
 
 // beta, dmean and beta_cov of the call from the downloaded per-entry blocks (internal order) to the caller's rows; NaN for failed entries
 void mean_scatter(const BatchPlan &P, const std::vector<double> &hs, const int32_t *st, int nbatch, int D, double *dmean, double *beta, double *beta_cov) {
-    const size_t ms = mean_small_stride(D);
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int i = 0; i < nbatch; i++) {
-        const int b = P.order[i];
-        const double *s = hs.data() + (size_t)i * ms;
-        const bool ok = st[b] >= 0;
-        for (int d = 0; d < D; d++) {
-            if (beta) beta[(size_t)b * D + d] = ok ? s[mean_off_beta(D) + d] : nan;
-            if (dmean) dmean[(size_t)b * D + d] = ok ? s[mean_off_dmean(D) + d] : nan;
-        }
-        if (beta_cov)
-            for (int x = 0; x < D * D; x++) beta_cov[(size_t)b * D * D + x] = ok ? s[mean_off_cov(D) + x] : nan;
-    }
+    const size_t n = (size_t)D;
+    scatter_entry_blocks(P.order.data(), st, nbatch, hs.data(), mean_small_stride(D),
+                         {{mean_off_beta(D), n, beta}, {mean_off_dmean(D), n, dmean}, {mean_off_cov(D), n * n, beta_cov}});
 }
 
 // The nlml with a constant baseline per covariate, fixed or integrated out, and its gradients (kernels_mean.h).  mean_prepare, then per
@@ -3190,17 +3182,12 @@ int mean_post_impl(medgp_ctx *c, const char *who, bool basis, int nbatch, const 
     if (!offsets) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if (nbatch < 1) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d", nbatch);
     int rc;
-    if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
-    for (int b = 0; b < nbatch; b++)
-        if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
-    const int64_t M = offsets[nbatch];
-    if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
-    if (M > 0 && !t2) return fail(c, MEDGP_ERR_ARG, "t2 is NULL");
-    if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
+    const int64_t M = check_points(c, nbatch, offsets, meta2, t2, false, nullptr);   // (mean / var are optional)
+    if (M < 0) return (int)M;
     if ((mean == nullptr) != (var == nullptr)) return fail(c, MEDGP_ERR_ARG, "mean and var: both or neither");
     std::vector<double> ht2;
     std::vector<int> hm2;
-    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
+    stage_points(c, M, meta2, t2, nullptr, ht2, hm2);
     MeanCall mc{};
     if (basis && M > 0) {   // (p from the first slot's basis; mean_prepare refuses what is wrong with the slots)
         if (!h2) return fail(c, MEDGP_ERR_ARG, "h2 is NULL");
@@ -3220,32 +3207,19 @@ int mean_post_impl(medgp_ctx *c, const char *who, bool basis, int nbatch, const 
     PointTables<PostTile> T;
     build_pjvp_tiles(table_classes(P), P.order.data(), offsets, c->posterior_budget, T);
     const size_t Mz = (size_t)std::max<int64_t>(M, 1);
-    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
-    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
-    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
+    if ((rc = upload_point_call(c, M, ht2, hm2, T.tiles, T.work_need))) return rc;
     if ((rc = buf_ensure(c, BUF_MN_OUT, 2 * Mz * sizeof(double)))) return rc;
     double *d_mean = buf<double>(c, BUF_MN_OUT), *d_var = d_mean + Mz;
-    for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
-        const SizeClass &k = P.cls[ch.cls];
-        const MedgpDev V = class_view(c, P, k);
-        const PostTile *tiles = buf<PostTile>(c, BUF_TILES) + ch.t0;
-        {
-            Launcher l(c, KID_PJ_SOLVE);   // (nvec = 0: no derivative output is touched)
-            hipLaunchKernelGGL(k_pjvp_solve, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK),
-                               ch.stride, 0, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), (double *)nullptr, (double *)nullptr);
-        }
+    for_solved_chunks(c, P, T, [&](const TileChunk &ch, const SizeClass &k, const MedgpDev &V, const PostTile *tiles) {
         const double *Gk = mc.G + MEAN_PW * k.off_vec, *sk = mc.small + (size_t)k.b0 * mean_small_stride(D), *work = buf<double>(c, BUF_WORK);
         Launcher l(c, basis ? KID_BS_POST : KID_MN_POST);   // (one body, fe_post_body, behind both)
         if (basis) hipLaunchKernelGGL(k_basis_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_BS_H2), work, ch.stride, Gk, sk, mode, D, d_mean, d_var);
         else hipLaunchKernelGGL(k_mean_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), work, ch.stride, Gk, sk, mode, d_mean, d_var);
-    }
+    });
     HIPCHK(c, hipGetLastError());
     std::vector<double> hs(mc.mb.small_doubles);
     std::vector<int32_t> st(nbatch);
-    if (M > 0 && mean) {
-        HIPCHK(c, hipMemcpyAsync(mean, d_mean, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(var, d_var, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
-    }
+    if ((rc = download_pair<double>(c, M, d_mean, d_var, mean, var))) return rc;
     HIPCHK(c, hipMemcpyAsync(hs.data(), mc.small, mc.mb.small_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if ((rc = read_status(c, nbatch, st.data()))) return rc;
     free_retired(c);
@@ -3332,13 +3306,8 @@ int warp_grad_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
         const int nb = k.count;
         V.alpha = wc.role(WARP_VEC_AT, P.need_vec, k.off_vec);   // the gradient pass and what follows see alpha~
         if (flag_grad) {
-            const WgradGrid wg = wgrad_grid(P.en.data() + k.b0, nb, k.nbmax);
-            const int pf = c->wgrad_deep >= 0 ? c->wgrad_deep : ((long)nb * wg.wg_tiles <= 16L * c->rules.num_cu ? 2 : 1);
-            launch_tiles(c, KID_WGRAD, V.Q, wg, [&](auto q, auto q0, dim3 tg, dim3 tb) {
-                constexpr int QQ = decltype(q)::value, Q0 = decltype(q0)::value;
-                if (pf >= 2) hipLaunchKernelGGL((k_wgrad<QQ, Q0, 2>), tg, tb, 0, c->stream, V, nb, wg.wg_tiles, wg.nbp);
-                else hipLaunchKernelGGL((k_wgrad<QQ, Q0, 1>), tg, tb, 0, c->stream, V, nb, wg.wg_tiles, wg.nbp);
-            });
+            Launcher l(c, KID_WGRAD);   // (Q <= 16 was checked)
+            launch_wgrad(c, c->stream, V, nb, wgrad_grid(P.en.data() + k.b0, nb, k.nbmax));
         }
         finish_objective_class(c, V, nb, flag_grad);
     }
@@ -3346,18 +3315,13 @@ int warp_grad_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     std::vector<double> hs(wc.wb.small_doubles);
     std::vector<int32_t> st(nbatch);
     if ((rc = download_objective(c, nbatch, flag_grad, nlml, grad, st.data(), hs.data(), wc.small, wc.wb.small_doubles * sizeof(double)))) return rc;
-    const size_t ws = warp_small_stride(D);
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int i = 0; i < nbatch; i++) {   // the per-entry blocks (internal order) to the caller's rows; NaN for failed entries
-        const int b = P.order[i];
-        const double *s = hs.data() + (size_t)i * ws;
-        const bool ok = st[b] >= 0;
-        if (logjac) logjac[b] = ok ? s[warp_off_logjac()] : nan;
-        if (dpsi)
-            for (int d = 0; d < D; d++)
-                for (int k = 0; k < WARP_NPSI; k++)
-                    dpsi[warp_in_psi(b, D, d, k)] = !ok ? nan : ((kind && kind[d] == MEDGP_WARP_NONE) ? 0.0 : s[warp_off_dpsi(d, k)]);
-    }
+    // the per-entry blocks (internal order) to the caller's rows, NaN for failed entries (warp_tables.h: a block's dpsi is laid out
+    // [d][k] as the caller's row); an unwarped covariate has no dpsi
+    scatter_entry_blocks(P.order.data(), st.data(), nbatch, hs.data(), warp_small_stride(D),
+                         {{warp_off_logjac(), 1, logjac}, {warp_off_dpsi(0, 0), (size_t)D * WARP_NPSI, dpsi}});
+    for (int b = 0; dpsi && kind && b < nbatch; b++)
+        for (int d = 0; d < D && st[b] >= 0; d++)
+            if (kind[d] == MEDGP_WARP_NONE) std::fill_n(dpsi + warp_in_psi(b, D, d, 0), WARP_NPSI, 0.0);
     if (status) std::memcpy(status, st.data(), sizeof(int32_t) * nbatch);
     return MEDGP_OK;
 }
@@ -3373,13 +3337,8 @@ int warp_post_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     if (!offsets) return fail(c, MEDGP_ERR_ARG, "NULL argument");
     if (nbatch < 1) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d", nbatch);
     int rc;
-    if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
-    for (int b = 0; b < nbatch; b++)
-        if (offsets[b + 1] < offsets[b]) return fail(c, MEDGP_ERR_ARG, "offsets decrease at %d", b);
-    const int64_t M = offsets[nbatch];
-    if (M > (int64_t)INT32_MAX - POST_TW) return fail(c, MEDGP_ERR_ARG, "%lld test points in one call (at most %d)", (long long)M, INT32_MAX - POST_TW);
-    if (M > 0 && !t2) return fail(c, MEDGP_ERR_ARG, "t2 is NULL");
-    if (M > 0 && c->kidx == MEDGP_KERNEL_LMC_SM && !meta2) return fail(c, MEDGP_ERR_ARG, "meta2 is NULL for the multi-output kernel");
+    const int64_t M = check_points(c, nbatch, offsets, meta2, t2, false, nullptr);   // (zmean / zvar are optional)
+    if (M < 0) return (int)M;
     if ((zmean == nullptr) != (zvar == nullptr)) return fail(c, MEDGP_ERR_ARG, "zmean and zvar: both or neither");
     if (nq < 0 || nq > WARP_MAX_NQ) return fail(c, MEDGP_ERR_ARG, "nq = %d outside [0, %d]", nq, WARP_MAX_NQ);
     if (nq > 0 && !zq) return fail(c, MEDGP_ERR_ARG, "zq is NULL with nq = %d", nq);
@@ -3387,16 +3346,14 @@ int warp_post_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     if (lpd && !y2) return fail(c, MEDGP_ERR_ARG, "lpd requires y2");
     std::vector<double> ht2;
     std::vector<int> hm2;
-    if ((rc = stage_points(c, M, meta2, t2, nullptr, ht2, hm2))) return rc;
+    stage_points(c, M, meta2, t2, nullptr, ht2, hm2);
     WarpCall wc{};
     if ((rc = warp_prepare(c, who, nbatch, slots, theta, kind, psi, 1, (size_t)M, nq, zq, wc))) return rc;
     const BatchPlan &P = c->plan;
     PointTables<PostTile> T;
     build_pjvp_tiles(table_classes(P), P.order.data(), offsets, c->posterior_budget, T);
     const size_t Mz = (size_t)std::max<int64_t>(M, 1);
-    if ((rc = upload_points(c, M, ht2, hm2))) return rc;
-    if ((rc = upload_table(c, BUF_TILES, T.tiles))) return rc;
-    if (!T.tiles.empty() && (rc = buf_ensure(c, BUF_WORK, T.work_need))) return rc;
+    if ((rc = upload_point_call(c, M, ht2, hm2, T.tiles, T.work_need))) return rc;
     if ((rc = buf_ensure(c, BUF_WP_OUT, wc.wb.out_doubles * sizeof(double)))) return rc;
     const bool with_y2 = y2 != nullptr && M > 0;
     if (with_y2) {   // (widened once on the host, as the observations are)
@@ -3408,25 +3365,14 @@ int warp_post_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     }
     double *d_out = buf<double>(c, BUF_WP_OUT);
     double *d_zmean = d_out + warp_out_zmean(Mz), *d_zvar = d_out + warp_out_zvar(Mz), *d_lpd = d_out + warp_out_lpd(Mz), *d_quant = d_out + warp_out_quant(Mz);
-    for (const TileChunk &ch : T.chunks) {   // chunks reuse the work rows in stream order
-        const SizeClass &k = P.cls[ch.cls];
-        const MedgpDev V = class_view(c, P, k);
-        const PostTile *tiles = buf<PostTile>(c, BUF_TILES) + ch.t0;
-        {
-            Launcher l(c, KID_PJ_SOLVE);   // (nvec = 0: no derivative output is touched)
-            hipLaunchKernelGGL(k_pjvp_solve, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_T2), buf<double>(c, BUF_WORK),
-                               ch.stride, 0, buf<float>(c, BUF_MEAN), buf<float>(c, BUF_VAR), (double *)nullptr, (double *)nullptr);
-        }
+    for_solved_chunks(c, P, T, [&](const TileChunk &ch, const SizeClass &k, const MedgpDev &V, const PostTile *tiles) {
         Launcher l(c, KID_WP_POST);
         hipLaunchKernelGGL(k_warp_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_WORK), ch.stride, wc.kind,
                            wc.in, wc.role(WARP_VEC_W, P.need_vec, k.off_vec), with_y2 ? buf<double>(c, BUF_WP_Y2) : (const double *)nullptr, nq,
                            wc.in + warp_in_zq(nbatch, wc.D), d_zmean, d_zvar, d_quant, d_lpd);
-    }
+    });
     HIPCHK(c, hipGetLastError());
-    if (M > 0 && zmean) {
-        HIPCHK(c, hipMemcpyAsync(zmean, d_zmean, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(zvar, d_zvar, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
-    }
+    if ((rc = download_pair<double>(c, M, d_zmean, d_zvar, zmean, zvar))) return rc;
     if (M > 0 && quant) HIPCHK(c, hipMemcpyAsync(quant, d_quant, sizeof(double) * M * nq, hipMemcpyDeviceToHost, c->stream));
     if (M > 0 && lpd) HIPCHK(c, hipMemcpyAsync(lpd, d_lpd, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
     if ((rc = read_status(c, nbatch, status))) return rc;

@@ -317,6 +317,26 @@ def test_argument_and_capacity_errors():
     # every output pointer may be NULL
     assert ctx._lib.medgp_mean_nlml_grad(ctx._h, 2, _ptr(sl, C.c_int32), _ptr(th, C.c_double), 0, _ptr(b0, C.c_double), _ptr(lam, C.c_double), 1,
                                          None, None, None, None, None, None) == 0
+    # the raw posterior call: the offset and NULL rules of the test points, refused before any device work (no launch, no allocation)
+    m2, t2 = np.zeros(4, np.int32), np.linspace(1.0, 9.0, 4).astype(np.float32)
+    mu, var, beta = np.zeros(4), np.zeros(4), np.zeros((2, 3))
+
+    def raw(off, m2=m2, t2=t2, mu=mu, var=var):
+        off = None if off is None else np.array(off, np.int64)
+        return ctx._lib.medgp_mean_posterior_batch(ctx._h, 2, _ptr(sl, C.c_int32), _ptr(th, C.c_double), 0, _ptr(b0, C.c_double), _ptr(lam, C.c_double),
+                                                   _ptr(off, C.c_int64), _ptr(m2, C.c_int32), _ptr(t2, C.c_float), _ptr(mu, C.c_double), _ptr(var, C.c_double),
+                                                   _ptr(beta, C.c_double), _ptr(st, C.c_int32))
+    assert raw([0, 1, 4]) == 0 and np.all(st == 0) and np.all(np.isfinite(mu)) and np.all(var > 0)
+    ctx.profile_enable(True)
+    ctx.profile_reset()
+    allocs = ctx.alloc_stats()[1]
+    assert raw([1, 1, 4]) == -1 and raw([0, 3, 2]) == -1                  # offsets[0] != 0; offsets that decrease
+    assert raw(None) == -1 and raw([0, 1, 4], t2=None) == -1 and raw([0, 1, 4], m2=None) == -1
+    assert raw([0, 1, 4], var=None) == -1 and raw([0, 1, 4], mu=None) == -1   # mean and var: both or neither
+    assert raw([0, 1, 4], m2=np.array([0, 3, 0, 0], np.int32)) == -1      # a covariate outside [0, D)
+    assert sum(v[1] for v in ctx.profile_read(all_entries=True).values()) == 0 and ctx.alloc_stats()[1] == allocs
+    assert raw([0, 1, 4], mu=None, var=None) == 0                         # the per-point outputs may be NULL together
+    ctx.profile_enable(False)
     r = ctx.mean_nlml_grad([1, 2], th, b0, lam)                           # the context stays usable
     assert np.all(r["status"] == 0) and np.all(np.isfinite(r["grad"]))
     ctx.close()

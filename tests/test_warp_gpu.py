@@ -308,6 +308,16 @@ def test_argument_and_capacity_errors(monkeypatch):
     assert raw() == 0 and np.all(st == 0)
     assert raw(nq=-1) == -1 and raw(nq=65) == -1
     assert raw(off=np.array([1, 24, 48], np.int64)) == -1 and raw(off=np.array([0, 30, 24], np.int64)) == -1
+    # ... refused before any device work: offsets[0] != 0, offsets that decrease and a covariate outside [0, D) launch and allocate nothing
+    ctx.profile_enable(True)
+    ctx.profile_reset()
+    allocs = ctx.alloc_stats()[1]
+    assert raw(off=np.array([1, 24, 48], np.int64)) == -1 and raw(off=np.array([0, 30, 24], np.int64)) == -1 and raw(off=np.array([0, 48, 47], np.int64)) == -1
+    bad_m2 = m2.copy()
+    bad_m2[47] = 3
+    assert raw(m2=bad_m2) == -1 and raw(t2=None) == -1
+    assert sum(v[1] for v in ctx.profile_read(all_entries=True).values()) == 0 and ctx.alloc_stats()[1] == allocs
+    ctx.profile_enable(False)
     assert raw(off=None) == -1 and raw(t2=None) == -1 and raw(m2=None) == -1
     assert raw(zv=None) == -1 and raw(zm=None) == -1                    # zmean and zvar: both or neither
     assert raw(zq=None) == -1 and raw(nq=0) == -1                       # quant requires nq >= 1 and zq
