@@ -9,7 +9,7 @@
 // are its per-functional fvar.  Nothing is factored: no fp64 copy of the block is kept.
 #pragma once
 #include "kernels_functional.h"
-#include "kernels_posterior_joint.h"   // pj_vtv, PJ_KC; JointPat / JointTile: inference_tables.h
+#include "kernels_posterior_joint.h"   // pj_vtv, POST_KC; JointPat / JointTile: inference_tables.h
 
 // ------------------------------------------------------------------------------------------
 // One workgroup per lower 64 x 64 tile pair (I >= J) of a patient's tiles of functionals (JointPat: p0 = its first functional of the
@@ -29,7 +29,7 @@
 __global__ void __launch_bounds__(256) k_funccov(MedgpDev L, const JointPat *__restrict__ pats, const JointTile *__restrict__ pairs, FuncTerms F,
                                                  const double *__restrict__ work, size_t work_stride, const float *__restrict__ var,
                                                  float *__restrict__ cov) {
-    __shared__ double Vs[PJ_KC * POST_LS];
+    __shared__ double Vs[POST_KC * POST_LS];
     __shared__ double Rs[64 * POST_LS];
     __shared__ int rowk0[64], rowk1[64];
     const JointTile T = pairs[blockIdx.x];

@@ -13,8 +13,8 @@
 //   k_lgo_prep    Tt = P diag(s): the singleton columns of Tt = P S, zeros in every other column (id -1, padding; the columns of larger
 //                 groups are written by k_lgo_t afterwards)
 //   k_lgo_inv     behind k_loo_gram / k_postfactor / k_loo_solve (R in the group's first block, w behind the second): one workgroup per
-//                 64-column tile of X = R^-1, block row by block row on fp64 MFMA with the 64 x 64 triangular solves by substitution --
-//                 k_loo_solve's column job, which keeps every block row of X but the last and stores variances instead
+//                 64-column tile of X = R^-1: loo_block_column_inverse (kernels_loo.h), the function k_loo_solve's column job calls,
+//                 here with every block row stored and no variances
 //   k_lgo_s       one workgroup per (group, lower tile pair I >= J): S_g = X^T X + r_g r_g^T on fp64 MFMA, the contraction from block row
 //                 I on (X is lower triangular); r_g = X^T w in fp64, scattered to the entry's r by the diagonal tiles.  S_g is stored as a
 //                 full symmetric block over R (dead behind k_lgo_inv and the vector solves).
@@ -56,81 +56,31 @@ __global__ void __launch_bounds__(256) k_lgo_prep(MedgpDev L, const double *__re
     Tm[at] = L.Kmat[at] * sv[i];   // (s = 0 on every row that is no singleton group)
 }
 
-// ------------------------------------------------------------------------------------------
-// X = R^-1, columns 64 c .. 64 c + 63 (job.I = c), block row by block row from the tile's own diagonal block:
-//   X_k = R_kk^-1 (E_kc - sum_{c <= j < k} R_kj X_j)
-// the sum on fp64 MFMA (the rows of X_j staged through LDS, those of R_kj streamed), the 64 x 64 solve by substitution, one column per
-// lane of wave 0 -- the arithmetic of k_loo_solve's column job, with every block row stored.  X has exact zeros above the diagonal of
-// its diagonal blocks and the identity on the padding; the blocks above the diagonal are never written and never read.
-// ------------------------------------------------------------------------------------------
+// X = R^-1, columns 64 c .. 64 c + 63 (job.I = c): loo_block_column_inverse (kernels_loo.h) with every block row stored and nothing
+// summed.  X has exact zeros above the diagonal of its diagonal blocks and the identity on the padding; the blocks above the diagonal
+// are never written and never read.
 __global__ void __launch_bounds__(256) k_lgo_inv(MedgpDev L, const JointPat *__restrict__ groups, const JointTile *__restrict__ jobs,
                                                  double *__restrict__ Mbuf, const int *__restrict__ gstat) {
     __shared__ LooSolveSmem sm;
     const JointTile T = jobs[blockIdx.x];
     const JointPat P = groups[T.pat];
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, g = lane >> 4;
-    const int b = P.e, mpad = medgp_roundup(P.m, 64), nb = mpad / 64, c = T.I;
+    const int b = P.e, mpad = medgp_roundup(P.m, 64);
     if (L.status[b] < 0 || gstat[P.b] < 0) return;
     const double *R = Mbuf + P.coff;
-    double *X = Mbuf + P.coff + (size_t)mpad * mpad;
-    for (int k = c; k < nb; k++) {
-        v4d acc[4];
-#pragma unroll
-        for (int cs = 0; cs < 4; cs++) acc[cs] = v4d{0.0, 0.0, 0.0, 0.0};
-        const double *Ar = R + (size_t)(64 * k + 16 * w + li) * mpad;
-        for (int kk = 64 * c; kk < 64 * k; kk += PJ_KC) {
-            __syncthreads();   // Bs is free; X_j of the previous steps is in memory
-#pragma unroll
-            for (int x = tid; x < PJ_KC * 64; x += 256) sm.Bs[(x >> 6) * POST_LS + (x & 63)] = X[(size_t)(kk + (x >> 6)) * mpad + 64 * c + (x & 63)];
-            double a[PJ_KC / 4];
-#pragma unroll
-            for (int s = 0; s < PJ_KC / 4; s++) a[s] = Ar[kk + 4 * s + g];
-            __syncthreads();
-#pragma unroll
-            for (int s = 0; s < PJ_KC / 4; s++)
-#pragma unroll
-                for (int cs = 0; cs < 4; cs++)
-                    acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], sm.Bs[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, MFMA_NEGA);
-        }
-        __syncthreads();   // Dk / Rk are free
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int cs = 0; cs < 4; cs++) {
-                const int row = 16 * w + 4 * r + g, col = 16 * cs + li;
-                sm.Dk[row * POST_LS + col] = acc[cs][r] + ((k == c && row == col) ? 1.0 : 0.0);
-            }
-        for (int x = tid; x < 64 * 64; x += 256) sm.Rk[(x >> 6) * POST_LS + (x & 63)] = R[(size_t)(64 * k + (x >> 6)) * mpad + 64 * k + (x & 63)];
-        __syncthreads();
-        if (tid < 64) {   // R_kk x = d for column tid: x_l, then the rows below it (the column lives in registers, as in k_loo_solve)
-            double s[64];
-#pragma unroll
-            for (int i = 0; i < 64; i++) s[i] = sm.Dk[i * POST_LS + tid];
-#pragma unroll
-            for (int l = 0; l < 64; l++) {
-                const double x = s[l] / sm.Rk[l * POST_LS + l];
-                s[l] = x;
-#pragma unroll
-                for (int i = l + 1; i < 64; i++) s[i] -= sm.Rk[i * POST_LS + l] * x;
-            }
-#pragma unroll
-            for (int i = 0; i < 64; i++) sm.Dk[i * POST_LS + tid] = s[i];
-        }
-        __syncthreads();
-        for (int x = tid; x < 64 * 64; x += 256) X[(size_t)(64 * k + (x >> 6)) * mpad + 64 * c + (x & 63)] = sm.Dk[(x >> 6) * POST_LS + (x & 63)];
-    }
+    loo_block_column_inverse<true, false>(sm, R, Mbuf + P.coff + (size_t)mpad * mpad, mpad, T.I, tid, w, li, g);
 }
 
 // ------------------------------------------------------------------------------------------
 // S_IJ = sum_{k >= 64 I} X[k][I cols]^T X[k][J cols] + r_I r_J^T for the tile pair (I, J), I >= J, of a group.  Both operands are rows of
-// X: those of the J columns are staged through LDS PJ_KC rows at a time, those of the I columns read from memory (16 adjacent doubles per
+// X: those of the J columns are staged through LDS POST_KC rows at a time, those of the I columns read from memory (16 adjacent doubles per
 // quarter wave).  r_I and r_J (128 columns, one thread each, rows in order: the same bits in every tile) first.  The tile and, off the
 // diagonal, its mirror image go to the group's first block.
 // ------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_lgo_s(MedgpDev L, const JointPat *__restrict__ groups, const JointTile *__restrict__ pairs,
                                                const LooRow *__restrict__ rows, double *__restrict__ Mbuf, const int *__restrict__ gstat,
                                                double *__restrict__ vec) {
-    __shared__ double Vs[PJ_KC * POST_LS];
+    __shared__ double Vs[POST_KC * POST_LS];
     __shared__ double rs[128];
     const JointTile T = pairs[blockIdx.x];
     const JointPat P = groups[T.pat];
@@ -149,20 +99,8 @@ __global__ void __launch_bounds__(256) k_lgo_s(MedgpDev L, const JointPat *__res
 #pragma unroll
     for (int cs = 0; cs < 4; cs++) acc[cs] = v4d{0.0, 0.0, 0.0, 0.0};
     const double *Xa = X + 64 * I + 16 * w + li;
-    for (int kk = 64 * I; kk < mpad; kk += PJ_KC) {
-        __syncthreads();   // Vs is free (first pass: rs is written)
-#pragma unroll
-        for (int x = tid; x < PJ_KC * 64; x += 256) Vs[(x >> 6) * POST_LS + (x & 63)] = X[(size_t)(kk + (x >> 6)) * mpad + 64 * J + (x & 63)];
-        double a[PJ_KC / 4];
-#pragma unroll
-        for (int s = 0; s < PJ_KC / 4; s++) a[s] = Xa[(size_t)(kk + 4 * s + g) * mpad];
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < PJ_KC / 4; s++)
-#pragma unroll
-            for (int cs = 0; cs < 4; cs++)
-                acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], Vs[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, 0);
-    }
+    panel_product<0>(acc, Vs, 64 * I, mpad, li, g,   // (its first barrier: rs is written)
+                     [&](int kk) { panel_stage_rows(Vs, X + 64 * J, kk, mpad, tid); }, [&](int k) { return Xa[(size_t)k * mpad]; });
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int ti = 16 * w + 4 * r + g;
@@ -180,12 +118,12 @@ __global__ void __launch_bounds__(256) k_lgo_s(MedgpDev L, const JointPat *__res
 // ------------------------------------------------------------------------------------------
 // Tt[64 rb + i][B[p]] = sum_{k < m} P[B[k]][64 rb + i] S_g[k][p] for row block rb (job.I) of the entry and every column p of the group,
 // 64 columns at a time.  Wave w owns the rows 16 w .. 16 w + 15 and all four 16-column strips; the rows k of S_g are staged through LDS
-// (PJ_KC x POST_LS, row-major: no transposed store).  Rows and columns of the group's padding are masked (S_g holds the identity there).
+// (POST_KC x POST_LS, row-major: no transposed store).  Rows and columns of the group's padding are masked (S_g holds the identity there).
 // ------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_lgo_t(MedgpDev L, const JointPat *__restrict__ groups, const JointTile *__restrict__ jobs,
                                                const LooRow *__restrict__ rows, const double *__restrict__ Mbuf, const int *__restrict__ gstat,
                                                double *__restrict__ Tm) {
-    __shared__ double Vs[PJ_KC * POST_LS];
+    __shared__ double Vs[POST_KC * POST_LS];
     const JointTile T = jobs[blockIdx.x];
     const JointPat P = groups[T.pat];
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, g = lane >> 4;
@@ -201,23 +139,8 @@ __global__ void __launch_bounds__(256) k_lgo_t(MedgpDev L, const JointPat *__res
         v4d acc[4];
 #pragma unroll
         for (int cs = 0; cs < 4; cs++) acc[cs] = v4d{0.0, 0.0, 0.0, 0.0};
-        for (int kk = 0; kk < mpad; kk += PJ_KC) {
-            __syncthreads();   // Vs is free
-#pragma unroll
-            for (int x = tid; x < PJ_KC * 64; x += 256) Vs[(x >> 6) * POST_LS + (x & 63)] = Sg[(size_t)(kk + (x >> 6)) * mpad + 64 * J + (x & 63)];
-            double a[PJ_KC / 4];
-#pragma unroll
-            for (int s = 0; s < PJ_KC / 4; s++) {
-                const int k = kk + 4 * s + g;
-                a[s] = k < m ? Pm[(size_t)rw[k].r * ld] : 0.0;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int s = 0; s < PJ_KC / 4; s++)
-#pragma unroll
-                for (int cs = 0; cs < 4; cs++)
-                    acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], Vs[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, 0);
-        }
+        panel_product<0>(acc, Vs, 0, mpad, li, g, [&](int kk) { panel_stage_rows(Vs, Sg + 64 * J, kk, mpad, tid); },
+                         [&](int k) { return k < m ? Pm[(size_t)rw[k].r * ld] : 0.0; });
 #pragma unroll
         for (int cs = 0; cs < 4; cs++) {
             const int p = 64 * J + 16 * cs + li;

@@ -50,13 +50,13 @@ __global__ void __launch_bounds__(256) k_loo_diag(MedgpDev L, const LooSingle *_
 // ------------------------------------------------------------------------------------------
 // M_IJ = sum_k U[r_I][k] U[r_J][k] for the rows r of tiles I >= J of a group's index list.  U is upper triangular and the list
 // ascending, so the contraction starts at the first row index of tile I (rounded down to the staging step) and ends at n: no
-// work on the structural zeros left of it.  The rows r_J are staged through LDS PJ_KC columns at a time, the rows r_I streamed
+// work on the structural zeros left of it.  The rows r_J are staged through LDS POST_KC columns at a time, the rows r_I streamed
 // from memory (wave w owns output rows 16 w .. 16 w + 15 and all four 16-column strips).  Elements left of a row's diagonal
 // and the rows of the padding are masked to zero; the block gets the identity on rows / columns [m, mpad).
 // ------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_loo_gram(MedgpDev L, const JointPat *__restrict__ groups, const JointTile *__restrict__ pairs,
                                                   const LooRow *__restrict__ rows, double *__restrict__ Mbuf) {
-    __shared__ double Vs[PJ_KC * POST_LS];
+    __shared__ double Vs[POST_KC * POST_LS];
     __shared__ int rI[64], rJ[64];
     const JointTile T = pairs[blockIdx.x];
     const JointPat P = groups[T.pat];
@@ -75,26 +75,15 @@ __global__ void __launch_bounds__(256) k_loo_gram(MedgpDev L, const JointPat *__
     v4d acc[4];
 #pragma unroll
     for (int cs = 0; cs < 4; cs++) acc[cs] = v4d{0.0, 0.0, 0.0, 0.0};
-    for (int kk = rI[0] & ~(PJ_KC - 1); kk < n; kk += PJ_KC) {
-        __syncthreads();   // Vs is free
+    panel_product<0>(acc, Vs, rI[0] & ~(POST_KC - 1), n, li, g,   // (the last step is a full one too: both callables mask k >= n)
+                     [&](int kk) {   // the rows r_J, gathered transposed
 #pragma unroll
-        for (int x = tid; x < 64 * PJ_KC; x += 256) {
-            const int c = x / PJ_KC, k = kk + x % PJ_KC, r = rJ[c];
-            Vs[(x % PJ_KC) * POST_LS + c] = (r >= 0 && k >= r && k < n) ? U[(size_t)r * ld + k] : 0.0;
-        }
-        double a[PJ_KC / 4];
-#pragma unroll
-        for (int s = 0; s < PJ_KC / 4; s++) {
-            const int k = kk + 4 * s + g;
-            a[s] = (ra >= 0 && k >= ra && k < n) ? Ua[k] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < PJ_KC / 4; s++)
-#pragma unroll
-            for (int cs = 0; cs < 4; cs++)
-                acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], Vs[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, 0);
-    }
+                         for (int x = tid; x < 64 * POST_KC; x += 256) {
+                             const int c = x / POST_KC, k = kk + x % POST_KC, r = rJ[c];
+                             Vs[(x % POST_KC) * POST_LS + c] = (r >= 0 && k >= r && k < n) ? U[(size_t)r * ld + k] : 0.0;
+                         }
+                     },
+                     [&](int k) { return (ra >= 0 && k >= ra && k < n) ? Ua[k] : 0.0; });
     double *Mp = Mbuf + P.coff;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -110,22 +99,69 @@ __global__ void __launch_bounds__(256) k_loo_gram(MedgpDev L, const JointPat *__
 // ------------------------------------------------------------------------------------------
 // Behind k_postfactor (R lower in the group's block, exact zeros above the diagonal of the diagonal blocks, identity on the
 // padding).  Two kinds of workgroup (4 waves):
-//   column tile c (J == 0): X = R^-1 E_c, the columns 64 c .. 64 c + 63 of R^-1, block row by block row from the tile's own
-//     diagonal block:   X_k = R_kk^-1 (E_kc - sum_{c <= j < k} R_kj X_j)
-//     the sum on fp64 MFMA (the rows of X_j staged through LDS, those of R_kj streamed; X_j kept in the group's second block),
-//     the 64 x 64 triangular solve by substitution, one column per lane of wave 0.  var_i = sum_k X[k][i]^2, rows in order.
+//   column tile c (J == 0): the columns 64 c .. 64 c + 63 of X = R^-1 by loo_block_column_inverse (X_j kept in the group's second
+//     block, the last block row not stored), var_i = sum_k X[k][i]^2, rows in order.
 //   vector solves (J == 1): w = R^-1 alpha_B forward, u = R^-T w backward over the 64-row blocks (the block's off-diagonal
 //     part by all four waves, partial sums added in a fixed order; the diagonal block by substitution across the lanes of
 //     wave 0), then mean = y_B - u and lpd = -1/2 w^T w + sum_j log R_jj - m/2 log 2 pi.
 // A group whose factorisation failed (gstat < 0) or whose patient has no factor keeps the NaN fill of its outputs.
 // ------------------------------------------------------------------------------------------
 struct LooSolveSmem {
-    double Bs[PJ_KC * POST_LS];   // staged rows of X_j
+    double Bs[POST_KC * POST_LS];   // staged rows of X_j
     double Dk[64 * POST_LS];      // right-hand side -> X_k
     double Rk[64 * POST_LS];      // R_kk
     double red[4][64];
     double rhs[64];
 };
+// X = R^-1 E_c, the columns 64 c .. 64 c + 63 of the inverse of the lower triangular R ([mpad][mpad], exact zeros above the diagonal of
+// its diagonal blocks), block row by block row from the tile's own diagonal block:
+//   X_k = R_kk^-1 (E_kc - sum_{c <= j < k} R_kj X_j)
+// the sum by panel_product (the rows of X_j staged through sm.Bs from X, where the earlier steps stored them; those of R_kj streamed), then
+// the right-hand side to sm.Dk and R_kk to sm.Rk, the 64 x 64 solve by substitution with one column per lane of wave 0, held in 64
+// registers, and X_k from sm.Dk to X.  STORE_LAST: the last block row is stored too (nothing below reads it).  SUMSQ: returns, for
+// tid < 64, the sum of x^2 down column 64 c + tid, rows in order (0 otherwise).  One workgroup of 4 waves; starts without a barrier (sm is
+// free) and ends on the one behind the last solve, before the last store.
+template <bool STORE_LAST, bool SUMSQ>
+__device__ __forceinline__ double loo_block_column_inverse(LooSolveSmem &sm, const double *R, double *X, int mpad, int c, int tid, int w, int li, int g) {
+    const int nb = mpad / 64;
+    double csq = 0.0;
+    for (int k = c; k < nb; k++) {
+        v4d acc[4];
+#pragma unroll
+        for (int cs = 0; cs < 4; cs++) acc[cs] = v4d{0.0, 0.0, 0.0, 0.0};
+        const double *Ar = R + (size_t)(64 * k + 16 * w + li) * mpad;
+        panel_product<MFMA_NEGA>(acc, sm.Bs, 64 * c, 64 * k, li, g, [&](int kk) { panel_stage_rows(sm.Bs, X + 64 * c, kk, mpad, tid); }, [&](int j) { return Ar[j]; });
+        __syncthreads();   // Dk / Rk are free
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int cs = 0; cs < 4; cs++) {
+                const int row = 16 * w + 4 * r + g, col = 16 * cs + li;
+                sm.Dk[row * POST_LS + col] = acc[cs][r] + ((k == c && row == col) ? 1.0 : 0.0);
+            }
+        for (int x = tid; x < 64 * 64; x += 256) sm.Rk[(x >> 6) * POST_LS + (x & 63)] = R[(size_t)(64 * k + (x >> 6)) * mpad + 64 * k + (x & 63)];
+        __syncthreads();
+        if (tid < 64) {   // R_kk x = d for column tid: x_l, then the rows below it
+            double s[64];
+#pragma unroll
+            for (int i = 0; i < 64; i++) s[i] = sm.Dk[i * POST_LS + tid];
+#pragma unroll
+            for (int l = 0; l < 64; l++) {
+                const double x = s[l] / sm.Rk[l * POST_LS + l];
+                s[l] = x;
+                if constexpr (SUMSQ) csq += x * x;
+#pragma unroll
+                for (int i = l + 1; i < 64; i++) s[i] -= sm.Rk[i * POST_LS + l] * x;
+            }
+#pragma unroll
+            for (int i = 0; i < 64; i++) sm.Dk[i * POST_LS + tid] = s[i];
+        }
+        __syncthreads();
+        if (STORE_LAST || k + 1 < nb)
+            for (int x = tid; x < 64 * 64; x += 256) X[(size_t)(64 * k + (x >> 6)) * mpad + 64 * c + (x & 63)] = sm.Dk[(x >> 6) * POST_LS + (x & 63)];
+    }
+    return csq;
+}
 __global__ void __launch_bounds__(256) k_loo_solve(MedgpDev L, const JointPat *__restrict__ groups, const JointTile *__restrict__ jobs,
                                                    const LooRow *__restrict__ rows, double *__restrict__ Mbuf, const int *__restrict__ gstat,
                                                    double log2pi, float *__restrict__ mean, float *__restrict__ var, double *__restrict__ lpd) {
@@ -140,55 +176,7 @@ __global__ void __launch_bounds__(256) k_loo_solve(MedgpDev L, const JointPat *_
     if (T.J == 0) {
         if (!var) return;
         const int c = T.I;
-        double csq = 0.0;   // (tid < 64: column 64 c + tid)
-        for (int k = c; k < nb; k++) {
-            v4d acc[4];
-#pragma unroll
-            for (int cs = 0; cs < 4; cs++) acc[cs] = v4d{0.0, 0.0, 0.0, 0.0};
-            const double *Ar = R + (size_t)(64 * k + 16 * w + li) * mpad;
-            for (int kk = 64 * c; kk < 64 * k; kk += PJ_KC) {
-                __syncthreads();   // Bs is free; X_j of the previous steps is in memory
-#pragma unroll
-                for (int x = tid; x < PJ_KC * 64; x += 256) sm.Bs[(x >> 6) * POST_LS + (x & 63)] = X[(size_t)(kk + (x >> 6)) * mpad + 64 * c + (x & 63)];
-                double a[PJ_KC / 4];
-#pragma unroll
-                for (int s = 0; s < PJ_KC / 4; s++) a[s] = Ar[kk + 4 * s + g];
-                __syncthreads();
-#pragma unroll
-                for (int s = 0; s < PJ_KC / 4; s++)
-#pragma unroll
-                    for (int cs = 0; cs < 4; cs++)
-                        acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], sm.Bs[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, MFMA_NEGA);
-            }
-            __syncthreads();   // Dk / Rk are free
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-#pragma unroll
-                for (int cs = 0; cs < 4; cs++) {
-                    const int row = 16 * w + 4 * r + g, col = 16 * cs + li;
-                    sm.Dk[row * POST_LS + col] = acc[cs][r] + ((k == c && row == col) ? 1.0 : 0.0);
-                }
-            for (int x = tid; x < 64 * 64; x += 256) sm.Rk[(x >> 6) * POST_LS + (x & 63)] = R[(size_t)(64 * k + (x >> 6)) * mpad + 64 * k + (x & 63)];
-            __syncthreads();
-            if (tid < 64) {   // R_kk x = d for column tid: x_l, then the rows below it
-                double s[64];
-#pragma unroll
-                for (int i = 0; i < 64; i++) s[i] = sm.Dk[i * POST_LS + tid];
-#pragma unroll
-                for (int l = 0; l < 64; l++) {
-                    const double x = s[l] / sm.Rk[l * POST_LS + l];
-                    s[l] = x;
-                    csq += x * x;
-#pragma unroll
-                    for (int i = l + 1; i < 64; i++) s[i] -= sm.Rk[i * POST_LS + l] * x;
-                }
-#pragma unroll
-                for (int i = 0; i < 64; i++) sm.Dk[i * POST_LS + tid] = s[i];
-            }
-            __syncthreads();
-            if (k + 1 < nb)
-                for (int x = tid; x < 64 * 64; x += 256) X[(size_t)(64 * k + (x >> 6)) * mpad + 64 * c + (x & 63)] = sm.Dk[(x >> 6) * POST_LS + (x & 63)];
-        }
+        const double csq = loo_block_column_inverse<false, true>(sm, R, X, mpad, c, tid, w, li, g);   // (tid < 64: column 64 c + tid)
         if (tid < 64 && 64 * c + tid < m) var[rw[64 * c + tid].out] = (float)csq;
         return;
     }

@@ -14,6 +14,42 @@
 #define POST_PARTS_LDS_MAX_D 32   // up to this D the per-covariate accumulators of a tile live in LDS, beyond it in the work rows
 
 // ------------------------------------------------------------------------------------------
+// The staged 64-column product of every family behind the factorisation (users: DESIGN 4.7v):
+//   acc += A[rows 16 w .. 16 w + 15 of a 64-row slab][k0 .. k1) B[k0 .. k1)][0 .. 63]     (NEG: the MFMA's negation bits; 1 subtracts)
+// on v_mfma_f64_16x16x4_f64, k in order, in steps kk = k0, k0 + KC, ... < k1 of KC each (a last step that reaches beyond k1 is a full
+// one: the callables mask).  Wave w owns 16 output rows and all four 16-column strips: acc[cs][r] is row 16 w + 4 r + g, column
+// 16 cs + li.  B is a [k][64] operand that `stage(kk)` puts into Vs as
+// Vs[r * POST_LS + c] = B[kk + r][c] (r < KC; called by all 256 threads; it masks what it must).  A is streamed: `aval(k)` returns this
+// lane's value A[row 16 w + li][k].  acc starts from what the caller hands in.
+// Barriers: every step STARTS on one (Vs is free, and what the workgroup stored to memory before the call or in the caller's previous
+// step is visible to stage) and has one between staging and the MFMAs; the function ENDS WITHOUT one and leaves the last KC staged rows
+// in Vs: the caller synchronises before it writes Vs, or anything that shares its memory, again.  With k0 >= k1 it does nothing, no
+// barrier either.
+// ------------------------------------------------------------------------------------------
+template <int NEG, int KC = POST_KC, class LDS, class STAGE, class AVAL>
+__device__ __forceinline__ void panel_product(v4d (&acc)[4], LDS *Vs, int k0, int k1, int li, int g, STAGE stage, AVAL aval) {
+    for (int kk = k0; kk < k1; kk += KC) {
+        __syncthreads();
+        stage(kk);
+        double a[KC / 4];
+#pragma unroll
+        for (int s = 0; s < KC / 4; s++) a[s] = aval(kk + 4 * s + g);
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < KC / 4; s++)
+#pragma unroll
+            for (int cs = 0; cs < 4; cs++)
+                acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], Vs[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, NEG);
+    }
+}
+// The row-major stage: Vs[r * POST_LS + c] = src[(k + r) * ldsrc + c], r < KC, c < 64 (src points at the operand's first column).
+template <int KC = POST_KC, class LDS>
+__device__ __forceinline__ void panel_stage_rows(LDS *Vs, const double *src, int k, size_t ldsrc, int tid) {
+#pragma unroll
+    for (int x = tid; x < KC * 64; x += 256) Vs[(x >> 6) * POST_LS + (x & 63)] = src[(size_t)(k + (x >> 6)) * ldsrc + (x & 63)];
+}
+
+// ------------------------------------------------------------------------------------------
 // alpha = K^-1 y = L^-T z by blocked back substitution over the 64-wide panels, last panel first:
 //   alpha_k = U_kk (z_k - sum_{j > k} L_jk^T alpha_j),   U_kk = L_kk^-T (stored by the factorisation)
 // One workgroup per entry of the view.  Wave w sums the rows m = w (mod 4) of L below the panel (each row read as one
@@ -193,27 +229,13 @@ __device__ __forceinline__ PostAcc post_kstar(const PostCtx C, const PostCols<NP
 
 // R_k = K*_k - L[C_k, 0:c0] V[0:c0]
 __device__ __forceinline__ PostAcc post_sub_lv(const PostCtx C, int c0, const PostAcc in) {
-    const int tid = C.tid, w = C.w, li = C.li, g = C.g, ld = C.ld;
-    ld_t *Vs = C.Vs;
-    const double *V = C.V;
     v4d acc[4] = {in.a[0], in.a[1], in.a[2], in.a[3]};
-    const int arow = c0 + 16 * w + li;
+    const int arow = c0 + 16 * C.w + C.li;
     const bool aok = arow < C.n;
-    const double *Lr = C.Lm + (size_t)arow * ld;
-    for (int kk = 0; kk < c0; kk += POST_KC) {
-        __syncthreads();   // Vs is free
-#pragma unroll
-        for (int x = tid; x < POST_KC * 64; x += 256) Vs[(x >> 6) * POST_LS + (x & 63)] = V[(size_t)(kk + (x >> 6)) * 64 + (x & 63)];
-        double a[POST_KC / 4];
-#pragma unroll
-        for (int s = 0; s < POST_KC / 4; s++) a[s] = aok ? Lr[kk + 4 * s + g] : 0.0;
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < POST_KC / 4; s++)
-#pragma unroll
-            for (int cs = 0; cs < 4; cs++)
-                acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], Vs[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, 1);   // acc -= a b
-    }
+    const double *Lr = C.Lm + (size_t)arow * C.ld;
+    panel_product<1>(acc, C.Vs, 0, c0, C.li, C.g,   // acc -= a b
+                     [&](int kk) { panel_stage_rows(C.Vs, C.V, kk, 64, C.tid); },
+                     [&](int k) { return aok ? Lr[k] : 0.0; });
     return PostAcc{{acc[0], acc[1], acc[2], acc[3]}};
 }
 

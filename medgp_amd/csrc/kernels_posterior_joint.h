@@ -15,30 +15,30 @@
 #pragma once
 #include "kernels_posterior.h"
 
-#define PJ_KC 32   // k-rows staged in LDS per step of the products
 #define PJ_BS 34   // LDS row stride (doubles) of the staged rows of L in k_postfactor
 
 // JointPat (one patient of a joint call) and JointTile (one workgroup of k_postcov / k_postdraw): inference_tables.h
 
 // acc = V_I^T V_J over the rows [0, npad) of two tiles' work rows ([npad][64] each) on fp64 MFMA, rows in order: the rows of V_J staged
-// through Vs (PJ_KC x POST_LS doubles of LDS) PJ_KC at a time, those of V_I streamed from memory.  Wave w owns output rows
+// through Vs (POST_KC x POST_LS doubles of LDS) POST_KC at a time, those of V_I streamed from memory.  Wave w owns output rows
 // 16 w .. 16 w + 15 and all four 16-column strips (acc[cs][r]: row 16 w + 4 r + g, column 16 cs + li).  Shared by k_postcov and
-// k_funccov (kernels_functional_joint.h).  Ends without a barrier: the caller synchronises before it reuses Vs.
+// k_funccov (kernels_functional_joint.h).  The sequence and the barrier contract are panel_product's (kernels_posterior.h): starts on
+// a barrier, ends without one.  Kept as a loop of its own: on panel_product k_funccov measured 1.9 % slower.
 __device__ __forceinline__ void pj_vtv(v4d (&acc)[4], const double *__restrict__ VI, const double *__restrict__ VJ, int npad, double *Vs,
                                        int tid, int w, int li, int g) {
 #pragma unroll
     for (int cs = 0; cs < 4; cs++) acc[cs] = v4d{0.0, 0.0, 0.0, 0.0};
     const double *Ar = VI + 16 * w + li;
-    for (int kk = 0; kk < npad; kk += PJ_KC) {
+    for (int kk = 0; kk < npad; kk += POST_KC) {
         __syncthreads();   // Vs is free
 #pragma unroll
-        for (int x = tid; x < PJ_KC * 64; x += 256) Vs[(x >> 6) * POST_LS + (x & 63)] = VJ[(size_t)(kk + (x >> 6)) * 64 + (x & 63)];
-        double a[PJ_KC / 4];
+        for (int x = tid; x < POST_KC * 64; x += 256) Vs[(x >> 6) * POST_LS + (x & 63)] = VJ[(size_t)(kk + (x >> 6)) * 64 + (x & 63)];
+        double a[POST_KC / 4];
 #pragma unroll
-        for (int s = 0; s < PJ_KC / 4; s++) a[s] = Ar[(size_t)(kk + 4 * s + g) * 64];
+        for (int s = 0; s < POST_KC / 4; s++) a[s] = Ar[(size_t)(kk + 4 * s + g) * 64];
         __syncthreads();
 #pragma unroll
-        for (int s = 0; s < PJ_KC / 4; s++)
+        for (int s = 0; s < POST_KC / 4; s++)
 #pragma unroll
             for (int cs = 0; cs < 4; cs++)
                 acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], Vs[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, 0);
@@ -47,7 +47,7 @@ __device__ __forceinline__ void pj_vtv(v4d (&acc)[4], const double *__restrict__
 
 // ------------------------------------------------------------------------------------------
 // C_IJ = K**_IJ - V_I^T V_J (+ sigma^2 on the diagonal; identity on rows / columns [m, mpad)).  acc = V_I^T V_J over the
-// rows of V on fp64 MFMA: the rows of V_J staged through LDS PJ_KC at a time, those of V_I streamed from memory (wave w
+// rows of V on fp64 MFMA: the rows of V_J staged through LDS POST_KC at a time, those of V_I streamed from memory (wave w
 // owns output rows 16 w .. 16 w + 15 and all four 16-column strips).  K** in the separable form of k_posterior<Q> for
 // Q <= 8 (cos / sin of the test times per component in LDS, one exp_neg per (pair, component)), per element as k_predict
 // for the generic kernel.  A diagonal tile is mirrored from its lower triangle, an off-diagonal tile written to cov in
@@ -58,9 +58,9 @@ __global__ void __launch_bounds__(256) k_postcov(MedgpDev L, const JointPat *__r
                                                  const int *__restrict__ meta2, const double *__restrict__ t2,
                                                  const double *__restrict__ work, size_t work_stride, double *__restrict__ Cbuf,
                                                  float *__restrict__ cov) {
-    __shared__ double Vs[PJ_KC * POST_LS];
+    __shared__ double Vs[POST_KC * POST_LS];
     __shared__ double Rs[64 * POST_LS];
-    static_assert(4 * (QT > 0 ? QT : 1) * 64 <= PJ_KC * POST_LS, "the cos / sin tables reuse the staging buffer");
+    static_assert(4 * (QT > 0 ? QT : 1) * 64 <= POST_KC * POST_LS, "the cos / sin tables reuse the staging buffer");
     typedef double tab_t[64];
     tab_t *rowc = (tab_t *)Vs, *rows = rowc + (QT > 0 ? QT : 1), *colc = rows + (QT > 0 ? QT : 1), *cols = colc + (QT > 0 ? QT : 1);   // after the product
     const JointTile T = pairs[blockIdx.x];
@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(256) k_postcov(MedgpDev L, const JointPat *__r
 struct PostFactorSmem {
     union {                    // never live at the same time (a barrier separates the uses)
         double Dk[64][CI_S];   // R_kk -> L_kk, then R_Ik of the blocks below
-        double Bs[64][PJ_BS];  // staged L[64 k + row][kk .. kk + PJ_KC)
+        double Bs[64][PJ_BS];  // staged L[64 k + row][kk .. kk + POST_KC)
     };
     double Xk[64][CI_S];       // L_kk^-1 (lower, exact zeros above the diagonal)
     alignas(16) double dv[64 + 128];
@@ -194,17 +194,17 @@ __global__ void __launch_bounds__(256) k_postfactor(MedgpDev L, const JointPat *
                 for (int cs = 0; cs < 4; cs++) acc[cs][r] = src[16 * cs];
             }
             const double *Ar = Cp + (size_t)(64 * I + 16 * w + li) * mpad;
-            for (int kk = 0; kk < 64 * k; kk += PJ_KC) {
+            for (int kk = 0; kk < 64 * k; kk += POST_KC) {
                 __syncthreads();   // Bs is free
 #pragma unroll
-                for (int x = tid; x < 64 * PJ_KC; x += 256)
-                    sm.Bs[x / PJ_KC][x % PJ_KC] = Cp[(size_t)(64 * k + x / PJ_KC) * mpad + kk + x % PJ_KC];
-                double a[PJ_KC / 4];
+                for (int x = tid; x < 64 * POST_KC; x += 256)
+                    sm.Bs[x / POST_KC][x % POST_KC] = Cp[(size_t)(64 * k + x / POST_KC) * mpad + kk + x % POST_KC];
+                double a[POST_KC / 4];
 #pragma unroll
-                for (int s = 0; s < PJ_KC / 4; s++) a[s] = Ar[kk + 4 * s + g];
+                for (int s = 0; s < POST_KC / 4; s++) a[s] = Ar[kk + 4 * s + g];
                 __syncthreads();
 #pragma unroll
-                for (int s = 0; s < PJ_KC / 4; s++)
+                for (int s = 0; s < POST_KC / 4; s++)
 #pragma unroll
                     for (int cs = 0; cs < 4; cs++)
                         acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], sm.Bs[16 * cs + li][4 * s + g], acc[cs], 0, 0, MFMA_NEGA);
@@ -252,7 +252,7 @@ __global__ void __launch_bounds__(256) k_postfactor(MedgpDev L, const JointPat *
 
 // ------------------------------------------------------------------------------------------
 // samples[i][s] = mean_i + sum_{j <= i} Lc[i][j] eps[j][s] for the rows of one 64-row block of a patient: a lower-triangular
-// (m x m) x (m x nsamp) product on fp64 MFMA, eps staged through LDS PJ_KC rows at a time, the rows of Lc streamed.  mean_i
+// (m x m) x (m x nsamp) product on fp64 MFMA, eps staged through LDS POST_KC rows at a time, the rows of Lc streamed.  mean_i
 // is the fp64 sum k_posterior rounds to `mean` (V^T z over the rows in order), taken again from the resident work rows
 // so that a sample carries one float rounding, not two.  Writes float.
 // ------------------------------------------------------------------------------------------
@@ -260,7 +260,7 @@ __global__ void __launch_bounds__(256) k_postdraw(MedgpDev L, const JointPat *__
                                                   const double *__restrict__ work, size_t work_stride, const double *__restrict__ Cbuf,
                                                   const int *__restrict__ cstat, const double *__restrict__ eps, int nsamp,
                                                   float *__restrict__ samples) {
-    __shared__ double Es[PJ_KC * POST_LS];
+    __shared__ double Es[POST_KC * POST_LS];
     __shared__ double mu[64];
     const JointTile T = blks[blockIdx.x];
     const JointPat P = pats[T.pat];
@@ -285,23 +285,15 @@ __global__ void __launch_bounds__(256) k_postdraw(MedgpDev L, const JointPat *__
         v4d acc[4];
 #pragma unroll
         for (int cs = 0; cs < 4; cs++) acc[cs] = v4d{0.0, 0.0, 0.0, 0.0};
-        for (int kk = 0; kk < 64 * (I + 1); kk += PJ_KC) {
-            __syncthreads();   // Es is free; mu is written
+        panel_product<0>(acc, Es, 0, 64 * (I + 1), li, g,   // (its first barrier: mu is written)
+                         [&](int kk) {
 #pragma unroll
-            for (int x = tid; x < PJ_KC * 64; x += 256) {
-                const int j = kk + (x >> 6), s = s0 + (x & 63);
-                Es[(x >> 6) * POST_LS + (x & 63)] = (j < m && s < nsamp) ? ep[(size_t)j * nsamp + s] : 0.0;
-            }
-            double a[PJ_KC / 4];
-#pragma unroll
-            for (int s = 0; s < PJ_KC / 4; s++) a[s] = Ar[kk + 4 * s + g];
-            __syncthreads();
-#pragma unroll
-            for (int s = 0; s < PJ_KC / 4; s++)
-#pragma unroll
-                for (int cs = 0; cs < 4; cs++)
-                    acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], Es[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, 0);
-        }
+                             for (int x = tid; x < POST_KC * 64; x += 256) {
+                                 const int j = kk + (x >> 6), s = s0 + (x & 63);
+                                 Es[(x >> 6) * POST_LS + (x & 63)] = (j < m && s < nsamp) ? ep[(size_t)j * nsamp + s] : 0.0;
+                             }
+                         },
+                         [&](int k) { return Ar[k]; });
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int row = 16 * w + 4 * r + g;

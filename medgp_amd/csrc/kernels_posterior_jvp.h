@@ -34,37 +34,23 @@
 //   MODE 0  A[i][k] = M[k][i], k <= i      (U^T: M = U, upper triangle)
 //   MODE 1  A[i][k] = M[i][k], k >= i      (U)
 //   MODE 2  A[i][k] = M[k][i]              (a symmetric matrix stored in full: Kdot)
-// Rows and columns beyond n are taken as zeros, whatever M holds there.  Starts on a barrier (Vs is free, earlier global stores of the
-// workgroup are visible) and leaves the last staged rows in Vs.
+// Rows and columns beyond n are taken as zeros, whatever M holds there.  Barriers: panel_product's (kernels_posterior.h).
 template <int MODE>
 __device__ __forceinline__ PostAcc pjvp_mm(const PostCtx C, const double *__restrict__ M, const double *X, int c0, int k0, int k1) {
-    const int tid = C.tid, w = C.w, li = C.li, g = C.g, ld = C.ld, n = C.n;
-    ld_t *Vs = C.Vs;
+    const int ld = C.ld, n = C.n;
     v4d acc[4];
 #pragma unroll
     for (int cs = 0; cs < 4; cs++) acc[cs] = v4d{0.0, 0.0, 0.0, 0.0};
-    const int i = c0 + 16 * w + li;
+    const int i = c0 + 16 * C.w + C.li;
     const bool iok = i < n;
-    for (int kk = k0; kk < k1; kk += POST_KC) {
-        __syncthreads();
-#pragma unroll
-        for (int x = tid; x < POST_KC * 64; x += 256) Vs[(x >> 6) * POST_LS + (x & 63)] = X[(size_t)(kk + (x >> 6)) * 64 + (x & 63)];
-        double a[POST_KC / 4];
-#pragma unroll
-        for (int s = 0; s < POST_KC / 4; s++) {
-            const int k = kk + 4 * s + g;
-            bool ok = iok && k < n;
-            if constexpr (MODE == 0) ok = ok && k <= i;
-            if constexpr (MODE == 1) ok = ok && k >= i;
-            a[s] = ok ? (MODE == 1 ? M[(size_t)i * ld + k] : M[(size_t)k * ld + i]) : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < POST_KC / 4; s++)
-#pragma unroll
-            for (int cs = 0; cs < 4; cs++)
-                acc[cs] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], Vs[(4 * s + g) * POST_LS + 16 * cs + li], acc[cs], 0, 0, 0);
-    }
+    panel_product<0>(acc, C.Vs, k0, k1, C.li, C.g,
+                     [&](int kk) { panel_stage_rows(C.Vs, X, kk, 64, C.tid); },
+                     [&](int k) {
+                         bool ok = iok && k < n;
+                         if constexpr (MODE == 0) ok = ok && k <= i;
+                         if constexpr (MODE == 1) ok = ok && k >= i;
+                         return ok ? (MODE == 1 ? M[(size_t)i * ld + k] : M[(size_t)k * ld + i]) : 0.0;
+                     });
     return PostAcc{{acc[0], acc[1], acc[2], acc[3]}};
 }
 
