@@ -54,7 +54,7 @@ typedef struct medgp_ctx medgp_ctx;
 #define MEDGP_FLAG_KEEP_FACTOR 2
 
 /* ABI version, bumped on any signature change */
-int medgp_abi_version(void);   /* 22: medgp_warp_nlml_grad, medgp_warp_posterior_batch, medgp_profile_num_kernels_ext2 (21: medgp_set_basis, medgp_basis_nlml_grad, medgp_basis_posterior_batch; 20: medgp_mean_nlml_grad, medgp_mean_posterior_batch; 19: medgp_posterior_vjp_batch, medgp_posterior_vjp_moments; 18: medgp_posterior_jvp_batch; 17: medgp_hess_vec; 16: medgp_fisher_vec; 15: medgp_lgo_grad; 14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
+int medgp_abi_version(void);   /* 23: medgp_set_noise_scale, medgp_hetero_nlml_grad, medgp_hetero_posterior_batch, medgp_robust_nlml_grad, medgp_profile_num_kernels_ext3, medgp_profile_kernel_name_ext3 (22: medgp_warp_nlml_grad, medgp_warp_posterior_batch, medgp_profile_num_kernels_ext2; 21:medgp_set_basis, medgp_basis_nlml_grad, medgp_basis_posterior_batch; 20: medgp_mean_nlml_grad, medgp_mean_posterior_batch; 19: medgp_posterior_vjp_batch, medgp_posterior_vjp_moments; 18: medgp_posterior_jvp_batch; 17: medgp_hess_vec; 16: medgp_fisher_vec; 15: medgp_lgo_grad; 14: medgp_forecast_grad; 13: medgp_gmm_fit; 12: medgp_functional_joint_batch; 11: medgp_functional_batch; 10: medgp_components_batch; 9: medgp_trend_batch; 8: medgp_forecast_batch; 7: medgp_loo_grad; 6: medgp_loo_batch; 5: medgp_posterior_joint_batch; 4: medgp_posterior_batch; 3: medgp_reserve_plan, medgp_alloc_stats) */
 
 /* number of visible HIP devices (0 if none; never initialises a context) */
 int medgp_device_count(void);
@@ -714,6 +714,59 @@ int medgp_warp_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots,
                                const float *y2 /* [M] or NULL */, int nq, const double *zq /* [nq] */, double *zmean,
                                double *zvar /* [M] */, double *quant /* [M][nq] */, double *lpd /* [M] */, int32_t *status);
 
+/* Per-observation noise scales and Student-t robust training (kernels_hetero.h; the definition is tests/hetero_truth.py).
+ * Every other call gives all observations of covariate d the noise variance sigma^2_d.  Here row i (covariate d = m_i; SE / SM: D = 1)
+ * carries a scale s_i > 0: the mean of k monitor readings has s = 1 / k, a second device its own variance ratio, a flagged value a
+ * large s.  With r jitter rounds the factored noise is N_i = (1 + r) sigma^2_d s_i (a jitter round adds the SCALED noise vector
+ * again), K_s = K + diag(N), P = K_s^-1, alpha = P y:
+ *   nlml   = 1/2 y^T alpha + 1/2 log|K_s| + 1/2 n log 2 PI                  (+ the priors on theta, as medgp_nlml_grad)
+ *   grad_h = 1/2 tr((P - alpha alpha^T) dK_s / d theta_h): the usual lines for the covariance hypers; for the noise hyper of covariate d
+ *            medgp_nlml_grad's line with s_i W_ii in the place of W_ii, sigma^2_d sum_{m_i = d} s_i W_ii
+ *   resid_i = y_i - E f_i = N_i alpha_i,   fvar_i = var f_i = N_i - N_i^2 P_ii        (per training row, fp64)
+ * status as medgp_nlml_grad (n <= 2: -1, else the jitter rounds).
+ *
+ * medgp_set_noise_scale makes scales resident: slot slots[k] gets scale[offsets[k] .. offsets[k + 1]), one per observation in the order
+ * the patient was uploaded (offsets[0] = 0; the count must equal the patient's n).  scale == NULL drops the tables of the slots
+ * (offsets is not read).  A scale must be finite and lie in [2^-40, 2^40], else MEDGP_ERR_ARG naming the index.  A later
+ * medgp_set_patient[s] on a slot drops its table.  ONLY medgp_hetero_nlml_grad and medgp_hetero_posterior_batch read the tables (a slot
+ * without one counts as all ones); EVERY OTHER CALL IGNORES THEM, medgp_robust_nlml_grad included (it takes scale0).  No device wait. */
+int medgp_set_noise_scale(medgp_ctx *ctx, int nslots, const int32_t *slots, const int64_t *offsets,
+                          const double *scale /* caller's row order; NULL drops the tables */);
+/* The heteroscedastic nlml, its gradient (flag_grad = 1) and the row statistics, under the slots' resident scales.  resid and fvar are
+ * packed by entry in the caller's row order (entry b owns sum_{b' < b} n_b' onward); each may be NULL; the rows of an entry with
+ * status < 0 get NaN.  With all scales 1 (no table, or a table of ones) nlml, grad and status are bit-equal to medgp_nlml_grad's.
+ * MEDGP_ERR_ARG for Q > 16 (as the warp calls), unknown bits in flag_grad, a slot without a patient; MEDGP_ERR_CAPACITY when the two
+ * matrices of every entry and the call's vectors exceed the memory budget (split the call).  All pointers are HOST memory. */
+int medgp_hetero_nlml_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, int flag_grad, double *nlml,
+                           double *grad /* [nbatch][H] */, double *resid, double *fvar /* packed by entry, caller's row order, optional */,
+                           int32_t *status);
+/* The posterior at test points (m*_j, t*_j) under the slots' resident scales, with V_j = L^-1 k*_j, z = L^-1 y and an optional scale
+ * s2[j] of the point's own noise (NULL: 1 for every point; 0: the latent f; finite, in [0, 2^40]):
+ *   mean[j] = V_j^T z,   var[j] = k** - V_j^T V_j + sigma^2_{m*_j} s2[j]
+ * fp64 outputs in the caller's point order; offsets / meta2 / t2 and their errors as medgp_posterior_batch; no n > 2 guard, as there;
+ * mean and var both or neither NULL.  The points of a patient with status[b] < 0 get NaN. */
+int medgp_hetero_posterior_batch(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                                 const int32_t *meta2, const float *t2, const double *s2 /* [M] or NULL */, double *mean, double *var,
+                                 int32_t *status);
+/* Student-t observation noise by variational reweighting: eps_i | tau_i ~ N(0, sigma^2_d / tau_i), tau_i ~ Gamma(nu_d / 2, nu_d / 2),
+ * q(tau_i) = Gamma(a_d, a_d s_i) with a_d = (nu_d + 1) / 2, so E tau_i = 1 / s_i.  With q(f) optimal for the given s the negative
+ * evidence bound is
+ *   J(theta, nu, s) = nlml_het(theta; s) + sum_i kappa(nu_{m_i}, s_i),   kappa(nu, s) = C(nu) + c (log s + 1 / s),   c = nu / 2,
+ *   C(nu) = psi(a) / 2 - lgamma(a) + lgamma(c) + c log(a / c) - a - (psi(a) - log a) / 2,
+ * J >= the exact Student-t nlml, and at fixed s dJ / dtheta is the heteroscedastic gradient exactly.  One E-step from a factorisation
+ * at s is  e_i = (resid_i^2 + fvar_i) / sigma^2_{m_i},  s_i <- (nu_d + e_i) / (nu_d + 1).
+ * The call starts from scale0 (packed by entry in the caller's row order, range as medgp_set_noise_scale; NULL = ones -- the resident
+ * tables are NOT read), makes `sweeps` E-steps (0 .. 64) and evaluates obj = J, grad, resid and fvar at the last scales, which it
+ * returns in `scale`: sweeps + 1 factorisations, queued without a host read-back in between.  sweeps = 0 with ones is the Gaussian nlml
+ * plus sum_d n_d (C(nu_d) + c_d).  delta[b] = max_i |s_new - s_old| / s_new of the last E-step (0 with sweeps = 0).  nu: [nbatch][D]
+ * (SE / SM: D = 1), finite and > 0, else MEDGP_ERR_ARG naming the index; nu is not learned here (medgp_amd.robust.select_nu scans a
+ * grid in one call).  status[b]: the jitter rounds of the final evaluation, or -1 (n <= 2, or a factorisation that failed in ANY sweep);
+ * such an entry's outputs are NaN and its batch-mates are unaffected.  Every output pointer may be NULL.  Errors and the capacity rule
+ * as medgp_hetero_nlml_grad.  All pointers are HOST memory. */
+int medgp_robust_nlml_grad(medgp_ctx *ctx, int nbatch, const int32_t *slots, const double *theta, const double *nu /* [nbatch][D] */,
+                           int sweeps /* 0..64 */, const double *scale0 /* packed, or NULL = ones */, int flag_grad, double *obj,
+                           double *grad, double *scale, double *resid, double *fvar, double *delta, int32_t *status);
+
 /* Rolling-origin forecasts: every test point predicted from a LEADING block of its patient's observations, all from ONE
  * factorisation per patient -- what the model says at time t from what was known before t.
  *   ref: core/gp_regression.cpp:128-214 (GP_Regression::predict), main_one_test.cpp:269-300 (the "past" training sets of the
@@ -1053,6 +1106,13 @@ int medgp_profile_num_kernels_ext(void);
    under the existing entries) are appended behind it: ids [medgp_profile_num_kernels_ext(), medgp_profile_num_kernels_ext2()) are
    valid in the same way. */
 int medgp_profile_num_kernels_ext2(void);
+/* medgp_profile_num_kernels_ext2 is pinned in turn, at its 62 entries, and so is medgp_profile_kernel_name: it answers "" from id 62 on
+   (callers test the end of the table that way).  The heteroscedastic calls' k_het_load, k_het_rows, k_het_estep, k_het_obj, k_het_post
+   (ids 62 to 66; their k_wgrad, k_slabsum, k_epilogue and k_pjvp_solve launches are accounted under the existing entries) are appended
+   behind it: ids [medgp_profile_num_kernels_ext2(), medgp_profile_num_kernels_ext3()) are valid for medgp_profile_read and
+   medgp_profile_enable(ctx, 2 + id); medgp_profile_kernel_name_ext3 names every id below medgp_profile_num_kernels_ext3(). */
+int medgp_profile_num_kernels_ext3(void);
+const char *medgp_profile_kernel_name_ext3(int k);
 const char *medgp_profile_kernel_name(int k);
 /* synchronises, then returns accumulated milliseconds and launch count of kernel k since the
  * last medgp_profile_reset */

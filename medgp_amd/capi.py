@@ -26,7 +26,7 @@ SYMBOLS = [
     "medgp_num_hyp", "medgp_set_pi", "medgp_set_stream", "medgp_reserve", "medgp_reserve_plan", "medgp_alloc_stats", "medgp_set_patient",
     "medgp_set_patients", "medgp_set_prior", "medgp_set_priors", "medgp_host_alloc", "medgp_host_free", "medgp_nlml_grad_async",
     "medgp_wait", "medgp_nlml_grad", "medgp_screen", "medgp_nlml_grad_device", "medgp_get_factor",
-    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_posterior_jvp_batch", "medgp_posterior_vjp_batch", "medgp_posterior_vjp_moments", "medgp_mean_nlml_grad", "medgp_mean_posterior_batch", "medgp_set_basis", "medgp_basis_nlml_grad", "medgp_basis_posterior_batch", "medgp_warp_nlml_grad", "medgp_warp_posterior_batch", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext", "medgp_profile_num_kernels_ext2",
+    "medgp_factor", "medgp_factor_batch", "medgp_pin_route", "medgp_last_plan", "medgp_fit_predict", "medgp_fit_predict_batch", "medgp_posterior_batch", "medgp_posterior_joint_batch", "medgp_loo_batch", "medgp_loo_grad", "medgp_lgo_grad", "medgp_fisher_vec", "medgp_hess_vec", "medgp_posterior_jvp_batch", "medgp_posterior_vjp_batch", "medgp_posterior_vjp_moments", "medgp_mean_nlml_grad", "medgp_mean_posterior_batch", "medgp_set_basis", "medgp_basis_nlml_grad", "medgp_basis_posterior_batch", "medgp_warp_nlml_grad", "medgp_warp_posterior_batch", "medgp_set_noise_scale", "medgp_hetero_nlml_grad", "medgp_hetero_posterior_batch", "medgp_robust_nlml_grad", "medgp_forecast_batch", "medgp_forecast_grad", "medgp_trend_batch", "medgp_components_batch", "medgp_functional_batch", "medgp_functional_joint_batch", "medgp_synchronize", "medgp_profile_enable", "medgp_profile_num_kernels", "medgp_profile_num_kernels_all", "medgp_profile_num_kernels_ext", "medgp_profile_num_kernels_ext2", "medgp_profile_num_kernels_ext3", "medgp_profile_kernel_name_ext3",
     "medgp_profile_kernel_name", "medgp_profile_read", "medgp_profile_reset", "medgp_kde_mode", "medgp_kde_mode_at", "medgp_gmm_fit",
 ]
 
@@ -120,6 +120,17 @@ def load():
     lib.medgp_warp_nlml_grad.argtypes = [vp, C.c_int, i32p, dp, i32p, dp, C.c_int, dp, dp, dp, dp, i32p]
     lib.medgp_warp_posterior_batch.restype = C.c_int
     lib.medgp_warp_posterior_batch.argtypes = [vp, C.c_int, i32p, dp, i32p, dp, C.POINTER(C.c_int64), i32p, fp, fp, C.c_int, dp, dp, dp, dp, dp, i32p]
+    lib.medgp_set_noise_scale.restype = C.c_int
+    lib.medgp_set_noise_scale.argtypes = [vp, C.c_int, i32p, C.POINTER(C.c_int64), dp]
+    lib.medgp_hetero_nlml_grad.restype = C.c_int
+    lib.medgp_hetero_nlml_grad.argtypes = [vp, C.c_int, i32p, dp, C.c_int, dp, dp, dp, dp, i32p]
+    lib.medgp_hetero_posterior_batch.restype = C.c_int
+    lib.medgp_hetero_posterior_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, dp, dp, dp, i32p]
+    lib.medgp_robust_nlml_grad.restype = C.c_int
+    lib.medgp_robust_nlml_grad.argtypes = [vp, C.c_int, i32p, dp, dp, C.c_int, dp, C.c_int, dp, dp, dp, dp, dp, dp, i32p]
+    lib.medgp_profile_num_kernels_ext3.restype = C.c_int
+    lib.medgp_profile_kernel_name_ext3.restype = C.c_char_p
+    lib.medgp_profile_kernel_name_ext3.argtypes = [C.c_int]
     lib.medgp_posterior_vjp_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, C.c_int, dp, dp, C.c_int, dp, dp, fp, fp, dp, dp, i32p]
     lib.medgp_forecast_grad.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, C.c_int, dp, dp, i32p]
     lib.medgp_forecast_batch.argtypes = [vp, C.c_int, i32p, dp, C.POINTER(C.c_int64), i32p, fp, i32p, fp, fp, fp, dp, i32p]
@@ -1043,6 +1054,91 @@ class Context:
                                                        _ptr(quant, C.c_double), _ptr(lpd, C.c_double), _ptr(p.st, C.c_int32)))
         return [dict(zmean=a, zvar=v, quant=q, lpd=l) for a, v, q, l in _split(p.offsets, zmean, zvar, quant, lpd)], p.st
 
+    # ---- per-observation noise scales and Student-t robust training (include/medgp_hip.h; helpers: medgp_amd.robust) ----
+    def _rows_of(self, slots):
+        """(n per entry, CSR offsets [nbatch + 1]) of the observations of the entries' patients"""
+        ns = np.array([self._slot_n[int(s)] for s in slots], dtype=np.int64)
+        off = np.zeros(ns.shape[0] + 1, dtype=np.int64)
+        off[1:] = np.cumsum(ns)
+        return ns, off
+
+    def _pack_rows(self, slots, rows, what):
+        """one array per entry, one value per observation in the order the patient was uploaded -> one packed float64 array"""
+        ns, off = self._rows_of(slots)
+        if len(rows) != ns.shape[0]:
+            raise ValueError(f"{len(rows)} {what} arrays for {ns.shape[0]} patients")
+        arrs = [np.asarray(r, dtype=np.float64).ravel() for r in rows]
+        for b, (a, n) in enumerate(zip(arrs, ns)):
+            if a.shape[0] != n:
+                raise ValueError(f"patient {b}: {a.shape[0]} {what} values for {int(n)} observations")
+        return off, np.ascontiguousarray(np.concatenate(arrs) if off[-1] else np.ones(1))
+
+    def set_noise_scale(self, slots, scales):
+        """medgp_set_noise_scale: resident per-observation noise scales s_i > 0 (the noise variance of row i is sigma^2_{m_i} s_i) for
+        hetero_nlml_grad and hetero_posterior; every other call ignores them.  scales: one array per slot, one value per observation
+        in the order the patient was uploaded (medgp_amd.robust.from_replicates / from_sd / flagged build them); None drops the
+        slots' tables.  A later set_patient[s] on a slot drops its table."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        if scales is None:
+            self._chk(self._lib.medgp_set_noise_scale(self._h, slots.shape[0], _ptr(slots, C.c_int32), None, None))
+            return
+        off, sc = self._pack_rows(slots, scales, "scale")
+        self._chk(self._lib.medgp_set_noise_scale(self._h, slots.shape[0], _ptr(slots, C.c_int32), _ptr(off, C.c_int64), _ptr(sc, C.c_double)))
+
+    def hetero_nlml_grad(self, slots, theta, flag_grad=True, rows=True):
+        """medgp_hetero_nlml_grad: nlml and gradient under the slots' resident noise scales, and (rows=True) per training row
+        resid = y - E f and fvar = var f.  Returns dict(nlml [nbatch], grad [nbatch, H] or None, resid, fvar: lists of one array [n]
+        per patient or None, status [nbatch]); a failed patient's rows are NaN."""
+        slots, theta = self._batch_args(slots, theta, check=True)
+        nb = slots.shape[0]
+        _, off = self._rows_of(slots)
+        nlml, grad, st = np.empty(nb), (np.empty((nb, self.H)) if flag_grad else None), np.empty(nb, dtype=np.int32)
+        resid = np.empty(max(int(off[-1]), 1)) if rows else None
+        fvar = np.empty(max(int(off[-1]), 1)) if rows else None
+        self._chk(self._lib.medgp_hetero_nlml_grad(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), int(bool(flag_grad)),
+                                                   _ptr(nlml, C.c_double), _ptr(grad, C.c_double), _ptr(resid, C.c_double), _ptr(fvar, C.c_double),
+                                                   _ptr(st, C.c_int32)))
+        sp = list(_split(off, resid, fvar))
+        return {"nlml": nlml, "grad": grad, "resid": [x[0] for x in sp] if rows else None, "fvar": [x[1] for x in sp] if rows else None, "status": st}
+
+    def hetero_posterior(self, slots, theta, meta2_list, t2_list, s2_list=None):
+        """medgp_hetero_posterior_batch: the posterior at test points under the slots' resident noise scales, float64.  slots, theta,
+        meta2_list, t2_list as posterior(); s2_list: the noise scale of every point (one array per patient; None: 1, a 0: the latent
+        f).  Returns ([(mean[m], var[m]) per patient], status)."""
+        p = self._point_args(slots, theta, meta2_list, t2_list)
+        s2 = self._per_point(p, s2_list, np.float64, "s2")
+        mean, var = np.empty(p.Mz), np.empty(p.Mz)
+        self._chk(self._lib.medgp_hetero_posterior_batch(*p.head, *p.pts, _ptr(s2, C.c_double), _ptr(mean, C.c_double), _ptr(var, C.c_double),
+                                                         _ptr(p.st, C.c_int32)))
+        return list(_split(p.offsets, mean, var)), p.st
+
+    def robust_nlml_grad(self, slots, theta, nu, sweeps=3, scale0=None, flag_grad=True, rows=True):
+        """medgp_robust_nlml_grad: Student-t noise by variational reweighting -- `sweeps` E-steps from scale0 (one array per patient
+        in the order it was uploaded; None: ones), then the bound J, its gradient and the row statistics at the last scales.
+        nu: the degrees of freedom, a scalar, [D] for every patient or [nbatch, D] (SE / SM: D = 1).  Returns dict(obj [nbatch],
+        grad [nbatch, H] or None, scale, resid, fvar: lists of one array [n] per patient (resid, fvar None without rows),
+        delta [nbatch], status [nbatch]); a failed patient's rows are NaN."""
+        slots, theta = self._batch_args(slots, theta, check=True)
+        nb = slots.shape[0]
+        D = self.D if self.kernel_index == KERNEL_LMC_SM else 1
+        nu = np.asarray(nu, dtype=np.float64)
+        if nu.size not in (1, D, nb * D):
+            raise ValueError(f"nu has {nu.size} values, expected 1, {D} or {nb} x {D}")
+        nu = np.ascontiguousarray(nu.reshape(nb, D) if nu.size == nb * D else np.broadcast_to(nu.reshape(1, -1), (nb, D)))
+        _, off = self._rows_of(slots)
+        s0 = None if scale0 is None else self._pack_rows(slots, scale0, "scale0")[1]
+        nrow = max(int(off[-1]), 1)
+        obj, grad, st = np.empty(nb), (np.empty((nb, self.H)) if flag_grad else None), np.empty(nb, dtype=np.int32)
+        scale, delta = np.empty(nrow), np.empty(nb)
+        resid, fvar = (np.empty(nrow), np.empty(nrow)) if rows else (None, None)
+        self._chk(self._lib.medgp_robust_nlml_grad(self._h, nb, _ptr(slots, C.c_int32), _ptr(theta, C.c_double), _ptr(nu, C.c_double), int(sweeps),
+                                                   _ptr(s0, C.c_double), int(bool(flag_grad)), _ptr(obj, C.c_double), _ptr(grad, C.c_double),
+                                                   _ptr(scale, C.c_double), _ptr(resid, C.c_double), _ptr(fvar, C.c_double), _ptr(delta, C.c_double),
+                                                   _ptr(st, C.c_int32)))
+        sp = list(_split(off, scale, resid, fvar))
+        return {"obj": obj, "grad": grad, "scale": [x[0] for x in sp], "resid": [x[1] for x in sp] if rows else None,
+                "fvar": [x[2] for x in sp] if rows else None, "delta": delta, "status": st}
+
     def forecast_grad(self, slots, theta, prefixes=None, flag_grad=1):
         """medgp_forecast_grad: the negative forecast score J = - sum_i lpd_i (plus the prior term, as nlml_grad) and its gradient in
         theta.  prefixes: one int array per patient, in the order the patient was uploaded: prefixes[b][i] = the number of leading
@@ -1078,7 +1174,7 @@ class Context:
         """on: bracket every launch with HIP events; only='k_cholinv': just the launches of that kernel."""
         mode = int(bool(on))
         if on and only is not None:
-            names = [self._lib.medgp_profile_kernel_name(k).decode() for k in range(self._lib.medgp_profile_num_kernels_ext2())]
+            names = [self._lib.medgp_profile_kernel_name_ext3(k).decode() for k in range(self._lib.medgp_profile_num_kernels_ext3())]
             mode = 2 + names.index(only)
         self._chk(self._lib.medgp_profile_enable(self._h, mode))
         self._profile_only = mode - 2 if mode >= 2 else None
@@ -1089,7 +1185,8 @@ class Context:
     def profile_read(self, all_entries=False):
         """{kernel name: (milliseconds, launches)} of the entries [0, medgp_profile_num_kernels_ext()), the table callers compare as a
         whole; all_entries=True: also the entries added since (the warp calls' four kernels), up to medgp_profile_num_kernels_ext2().
-        A kernel beyond the table that profile_enable(only=...) last named is returned as well: what was asked for is never left out."""
+        A kernel beyond the table that profile_enable(only=...) last named is returned as well: what was asked for is never left out
+        (the heteroscedastic calls' five kernels, ids up to medgp_profile_num_kernels_ext3(), are reached that way)."""
         out = {}
         ids = list(range(self._lib.medgp_profile_num_kernels_ext2() if all_entries else self._lib.medgp_profile_num_kernels_ext()))
         only = getattr(self, "_profile_only", None)
@@ -1098,5 +1195,5 @@ class Context:
         for k in ids:
             ms, cnt = C.c_double(), C.c_int64()
             self._chk(self._lib.medgp_profile_read(self._h, k, C.byref(ms), C.byref(cnt)))
-            out[self._lib.medgp_profile_kernel_name(k).decode()] = (ms.value, cnt.value)
+            out[self._lib.medgp_profile_kernel_name_ext3(k).decode()] = (ms.value, cnt.value)
         return out

@@ -71,7 +71,9 @@ __device__ __forceinline__ double lane_bcast(double v, int srclane) {
 // QT = mixture components this launch evaluates, Q0 = index of the first one.  Q <= 8: one launch <Q, 0>.  8 < Q <= 16 (Q is a free
 // configuration key of the reference, ref: kernel/c_kernel_LMC_SM.cpp:51-70): <8, 0> followed by <Q - 8, 8>, which ADDS its
 // components to the tile the first launch wrote (components in ascending order, as the reference sums them, :182-191).
-template <int QT, int Q0 = 0>
+// HET: the noise of row i is hyp[m_i] * L.nscale[b ld + i] (the heteroscedastic calls, kernels_hetero.h: L.nscale is set); a template flag
+// because as a run-time branch on the pointer it cost every instantiation two to 22 VGPRs and four of them a wave of occupancy.
+template <int QT, int Q0 = 0, bool HET = false>
 __global__ void __launch_bounds__(256) k_assemble_t(MedgpDev L) {
     const int b = blockIdx.y;
     if (L.status[b] < 0) return;
@@ -141,7 +143,11 @@ __global__ void __launch_bounds__(256) k_assemble_t(MedgpDev L) {
                 acc += bq[q] * (cd * exp2_nonpos(cq2n[q] * dd));
             }
             if constexpr (Q0 == 0) {
-                if (i == j) { const double lik = hyp[mj]; acc += lik; for (int r = 0; r < L.jit[b]; r++) acc += lik; }   // ref c_inference_exact.cpp:88-92, :101-104
+                if constexpr (HET) {
+                    if (i == j) { const double lik = hyp[mj] * L.nscale[(size_t)b * ld + i]; acc += lik; for (int r = 0; r < L.jit[b]; r++) acc += lik; }
+                } else {
+                    if (i == j) { const double lik = hyp[mj]; acc += lik; for (int r = 0; r < L.jit[b]; r++) acc += lik; }   // ref c_inference_exact.cpp:88-92, :101-104
+                }
             }
             v = jv ? acc : 0.0;
         } else v = (i == j) ? 1.0 : 0.0;

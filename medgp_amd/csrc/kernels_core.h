@@ -140,6 +140,7 @@ __device__ __attribute__((noinline)) void reassemble_wg(const MedgpDev &L, int b
             v = cov_elem(L, hyp, cs, sn, t, meta, i, j);
             if (i == j) {
                 double lik = hyp[meta[i]];
+                if (L.nscale) lik *= L.nscale[(size_t)b * ld + i];   // the SCALED noise vector is what a jitter round adds again
                 v += lik;
                 for (int r = 0; r < count; r++) v += lik;
             }

@@ -31,6 +31,7 @@
 #include "kernels_mean.h"
 #include "kernels_basis.h"
 #include "kernels_warp.h"
+#include "kernels_hetero.h"
 
 #include <algorithm>
 #include <chrono>
@@ -46,9 +47,10 @@
 
 namespace {
 
-enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_PJ_SOLVE, KID_PJ_U, KID_PJ_DIR, KID_PV_COT, KID_PV_WGRAD, KID_PV_CROSS, KID_PV_FINISH, KID_MN_G, KID_MN_SMALL, KID_MN_PANEL, KID_MN_WGRAD, KID_MN_POST, KID_BS_G, KID_BS_SMALL, KID_BS_POST, KID_WP_Z, KID_WP_SOLVE, KID_WP_SMALL, KID_WP_POST, KID_COUNT };
-constexpr int KID_EXT_COUNT = KID_BS_POST + 1;   // what medgp_profile_num_kernels_ext is pinned at; [KID_EXT_COUNT, KID_COUNT): the _ext2 entries
-const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue", "k_pjvp_solve", "k_pjvp_u", "k_pjvp_dir", "k_pvjp_cot", "k_pvjp_wgrad", "k_pvjp_cross", "k_pvjp_finish", "k_mean_g", "k_mean_small", "k_mean_panel", "k_mean_wgrad", "k_mean_post", "k_basis_g", "k_basis_small", "k_basis_post", "k_warp_z", "k_warp_solve", "k_warp_small", "k_warp_post"};
+enum KernelId { KID_PREP = 0, KID_ASSEMBLE, KID_CHOLINV, KID_LA_STEP, KID_LA_AUX, KID_LAUUM, KID_GRADBINS, KID_WGRAD, KID_EPILOGUE, KID_PREDICT, KID_ALPHA, KID_POSTERIOR, KID_POSTCOV, KID_POSTFACTOR, KID_POSTDRAW, KID_LOO_DIAG, KID_LOO_GRAM, KID_LOO_SOLVE, KID_LOO_KINV, KID_LOO_VEC, KID_LOO_WGRAD, KID_TREND, KID_FORECAST, KID_FC_VEC, KID_FC_T, KID_FC_SCAN, KID_FC_QM, KID_FC_TABLES, KID_FC_WGRAD, KID_LGO_VEC, KID_LGO_INV, KID_LGO_S, KID_LGO_T, KID_LGO_WGRAD, KID_FI_PREP, KID_FI_KDOT, KID_FI_T, KID_FI_WGRAD, KID_HE_MOMENTS, KID_HE_SLABSUM, KID_HE_BETA, KID_HE_WGRAD, KID_HE_EPILOGUE, KID_PJ_SOLVE, KID_PJ_U, KID_PJ_DIR, KID_PV_COT, KID_PV_WGRAD, KID_PV_CROSS, KID_PV_FINISH, KID_MN_G, KID_MN_SMALL, KID_MN_PANEL, KID_MN_WGRAD, KID_MN_POST, KID_BS_G, KID_BS_SMALL, KID_BS_POST, KID_WP_Z, KID_WP_SOLVE, KID_WP_SMALL, KID_WP_POST, KID_HT_LOAD, KID_HT_ROWS, KID_HT_ESTEP, KID_HT_OBJ, KID_HT_POST, KID_COUNT };
+constexpr int KID_EXT_COUNT = KID_BS_POST + 1;   // what medgp_profile_num_kernels_ext is pinned at; [KID_EXT_COUNT, KID_EXT2_COUNT): the _ext2 entries
+constexpr int KID_EXT2_COUNT = KID_WP_POST + 1;  // what medgp_profile_num_kernels_ext2 is pinned at; [KID_EXT2_COUNT, KID_COUNT): the _ext3 entries
+const char *const kKernelNames[KID_COUNT] = {"k_prep", "k_assemble", "k_cholinv", "k_la_step", "k_la_aux", "k_lauum", "k_gradbins", "k_wgrad", "k_epilogue", "k_predict", "k_alpha", "k_posterior", "k_postcov", "k_postfactor", "k_postdraw", "k_loo_diag", "k_loo_gram", "k_loo_solve", "k_loo_kinv", "k_loo_vec", "k_loo_wgrad", "k_trend", "k_forecast", "k_fc_vec", "k_fc_t", "k_fc_scan", "k_fc_qm", "k_fc_tables", "k_fc_wgrad", "k_lgo_vec", "k_lgo_inv", "k_lgo_s", "k_lgo_t", "k_lgo_wgrad", "k_fisher_prep", "k_fisher_kdot", "k_fisher_t", "k_fisher_wgrad", "k_hess_moments", "k_hess_slabsum", "k_hess_beta", "k_hess_wgrad", "k_hess_epilogue", "k_pjvp_solve", "k_pjvp_u", "k_pjvp_dir", "k_pvjp_cot", "k_pvjp_wgrad", "k_pvjp_cross", "k_pvjp_finish", "k_mean_g", "k_mean_small", "k_mean_panel", "k_mean_wgrad", "k_mean_post", "k_basis_g", "k_basis_small", "k_basis_post", "k_warp_z", "k_warp_solve", "k_warp_small", "k_warp_post", "k_het_load", "k_het_rows", "k_het_estep", "k_het_obj", "k_het_post"};
 
 thread_local std::string g_create_error;   // last medgp_create error of the calling thread
 
@@ -122,9 +124,13 @@ struct Arena {
 //   medgp_warp_nlml_grad / medgp_warp_posterior_batch (warp_tables.h): BUF_WP_VEC [z | log g' | w | alpha~], each laid out like alpha,
 //   BUF_WP_SMALL the per-entry blocks (logjac, 1/2 |w|^2, dpsi), BUF_WP_IN [psi | zq] (psi in the caller's order), BUF_WP_KIND kind[D],
 //   BUF_WP_Y2 the observed values at the call's points, BUF_WP_OUT the fp64 [zmean | zvar | lpd | quant] of the posterior call's points
+//   medgp_hetero_nlml_grad / medgp_hetero_posterior_batch / medgp_robust_nlml_grad (hetero_tables.h): BUF_HT_VEC [s | resid | fvar], each
+//   laid out like alpha (s is what MedgpDev::nscale points at during the call), BUF_HT_OUT the fp64 [mean | var | s2] of the posterior
+//   call's points, BUF_HT_TAB the robust call's table (robust_tables.h, the caller's order), BUF_HT_DELTA its per-entry delta,
+//   BUF_HT_HAS per internal entry whether its slot has resident scales
 struct DevBuf { void *p = nullptr; size_t cap = 0; };   // cap: bytes
 enum BufId { BUF_T2 = 0, BUF_META2, BUF_MEAN, BUF_VAR, BUF_PARTS, BUF_TILES, BUF_WORK, BUF_PREFIX, BUF_Y2, BUF_LPD,
-             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_PJ_U, BUF_PJ_OUT, BUF_PV_ENT, BUF_PV_SEG, BUF_PV_ORD, BUF_PV_IN, BUF_PV_PTS, BUF_PV_VEC, BUF_PV_SMALL, BUF_PV_OUT, BUF_MN_G, BUF_MN_PH, BUF_MN_PM, BUF_MN_VEC, BUF_MN_SMALL, BUF_MN_IN, BUF_MN_OUT, BUF_BS_OFF, BUF_BS_H2, BUF_WP_VEC, BUF_WP_SMALL, BUF_WP_IN, BUF_WP_KIND, BUF_WP_Y2, BUF_WP_OUT, BUF_COUNT };
+             BUF_PATS, BUF_PAIRS, BUF_BLKS, BUF_C, BUF_COV, BUF_EPS, BUF_SAMP, BUF_CSTAT, BUF_SINGLES, BUF_ROWS, BUF_GVEC, BUF_SLOPE, BUF_COMP, BUF_FUNC_D, BUF_FUNC_I, BUF_FC_T, BUF_FC_TAB, BUF_LGO_T, BUF_LGO_COLS, BUF_LGO_TROWS, BUF_LGO_SGL, BUF_LGO_ENT, BUF_LGO_GORD, BUF_FI_KDOT, BUF_FI_T, BUF_FI_COEF, BUF_FI_DIR, BUF_FI_OUT, BUF_HE_SLAB, BUF_HE_SUMS, BUF_HE_VEC, BUF_PJ_U, BUF_PJ_OUT, BUF_PV_ENT, BUF_PV_SEG, BUF_PV_ORD, BUF_PV_IN, BUF_PV_PTS, BUF_PV_VEC, BUF_PV_SMALL, BUF_PV_OUT, BUF_MN_G, BUF_MN_PH, BUF_MN_PM, BUF_MN_VEC, BUF_MN_SMALL, BUF_MN_IN, BUF_MN_OUT, BUF_BS_OFF, BUF_BS_H2, BUF_WP_VEC, BUF_WP_SMALL, BUF_WP_IN, BUF_WP_KIND, BUF_WP_Y2, BUF_WP_OUT, BUF_HT_VEC, BUF_HT_OUT, BUF_HT_TAB, BUF_HT_DELTA, BUF_HT_HAS, BUF_COUNT };
 constexpr size_t kArenaEager = (size_t)8 << 30;
 enum ArenaId { AR_K = 0, AR_U, AR_Z, AR_ALPHA, AR_WDIAG, AR_CS, AR_SN, AR_SLAB, AR_LA_PART, AR_LA_SMALL, AR_COUNT };
 
@@ -212,6 +218,10 @@ struct medgp_ctx {
     size_t basis_stage_cap = 0;
     hipEvent_t ev_basis = nullptr;
     bool basis_pending = false;
+    // the resident noise scales of medgp_set_noise_scale (kernels_hetero.h): [max_slots][ldn] in the grouped row order, allocated by the
+    // first call that sets any; h_has_scale: which slots hold some (a new patient in a slot drops them)
+    double *d_slot_scale = nullptr;
+    std::vector<uint8_t> h_has_scale;
     std::vector<int64_t> pv_src;    // medgp_posterior_vjp_batch: device point -> caller point of the last call (medgp_posterior_vjp_moments)
     bool pv_valid = false;          // ... and whether BUF_PV_PTS still holds that call's fp64 mean / var
     size_t posterior_budget = (size_t)2 << 30;   // MEDGP_POSTERIOR_BUDGET_GB
@@ -502,6 +512,7 @@ MedgpDev class_view(const medgp_ctx *c, const BatchPlan &P, const SizeClass &k) 
     V.cs = L.cs + P.tab0 + k.off_tab; V.sn = L.sn + P.tab0 + k.off_tab;
     V.Kmat = L.Kmat + P.mat0 + k.off_mat; V.Linv = L.Linv + (P.with_u ? P.mat0 + k.off_mat : 0);
     V.z = L.z + P.vec0 + k.off_vec; V.alpha = L.alpha + P.vec0 + k.off_vec; V.wdiag = L.wdiag + P.vec0 + k.off_vec;
+    if (L.nscale) V.nscale = L.nscale + P.vec0 + k.off_vec;   // (a heteroscedastic call is running: HeteroScope)
     V.epi_lp = L.epi_lp + b0 * MEDGP_EPI_PARTS; V.epi_ticket = L.epi_ticket + b0;
     V.scal = L.scal + b0 * 4; V.status = L.status + b0; V.jit = L.jit + b0; V.bn = L.bn + b0; V.xk = L.xk + b0 * 64 * 64;
     V.S = L.S + b0 * Q * D * D; V.SM = L.SM + b0 * Q * D * D; V.SV = L.SV + b0 * Q * D * D;
@@ -520,6 +531,7 @@ MedgpDev shifted_view(const MedgpDev &L, int b0) {
     V.cs = L.cs + (size_t)b0 * Q * ld; V.sn = L.sn + (size_t)b0 * Q * ld;
     V.Kmat = L.Kmat + (size_t)b0 * ld * ld; V.Linv = L.Linv + (size_t)b0 * ld * ld;
     V.z = L.z + (size_t)b0 * ld; V.alpha = L.alpha + (size_t)b0 * ld; V.wdiag = L.wdiag + (size_t)b0 * ld;
+    if (L.nscale) V.nscale = L.nscale + (size_t)b0 * ld;
     V.epi_lp = L.epi_lp + (size_t)b0 * MEDGP_EPI_PARTS; V.epi_ticket = L.epi_ticket + b0;
     V.scal = L.scal + (size_t)b0 * 4; V.status = L.status + b0; V.jit = L.jit + b0; V.bn = L.bn + b0; V.xk = L.xk + (size_t)b0 * 64 * 64;
     V.S = L.S + (size_t)b0 * Q * D * D; V.SM = L.SM + (size_t)b0 * Q * D * D; V.SV = L.SV + (size_t)b0 * Q * D * D;
@@ -680,6 +692,15 @@ int run_pipeline_one(medgp_ctx *c, hipStream_t stream, const MedgpDev &L, int nb
         Launcher l(c, KID_ASSEMBLE, stream);
         const dim3 tg(tri(nt64), nbatch), tb(256);
         // 9 .. 16 components: the first eight, then the rest added to the same tiles (kernels_assemble.h)
+        // (a heteroscedastic call -- L.nscale set, Q <= 16, never the generic route -- takes the instantiation that scales the noise: the
+        //  noise is added by the pass that starts at component 0)
+        if (L.nscale) {
+            with_q16(L.Q, [&](auto q, auto q0) {
+                constexpr int QQ = decltype(q)::value, Q0 = decltype(q0)::value;
+                hipLaunchKernelGGL((k_assemble_t<QQ, Q0, Q0 == 0>), tg, tb, 0, stream, L);
+            });
+            return;
+        }
         if (c->rules.use_v0 || !with_q16(L.Q, [&](auto q, auto q0) { hipLaunchKernelGGL((k_assemble_t<decltype(q)::value, decltype(q0)::value>), tg, tb, 0, stream, L); }))
             hipLaunchKernelGGL(k_assemble_v0, tg, tb, 0, stream, L);   // Q > 16 (or MEDGP_V0): generic kernel
     };
@@ -1065,7 +1086,7 @@ void transpose_directions(const std::vector<double> &out, int nbatch, int nvec, 
 
 extern "C" {
 
-int medgp_abi_version(void) { return 22; }
+int medgp_abi_version(void) { return 23; }
 
 int medgp_device_count(void) {
     int n = 0;
@@ -1275,6 +1296,9 @@ int medgp_reserve(medgp_ctx *c, int max_slots, int max_n, int max_batch) {
     c->basis.slot.assign(max_slots, BasisSlot{});
     c->d_basis = nullptr;   // freed by free_all above
     c->basis_pending = false;
+    c->d_slot_scale = nullptr;   // freed by free_all above
+    c->h_has_scale.assign(max_slots, 0);
+    L.nscale = nullptr;
     c->h_bslot.assign(max_batch, -1);
     c->last_nbatch = 0;
     c->plan = BatchPlan{};
@@ -1434,6 +1458,7 @@ int upload_patients(medgp_ctx *c, const std::vector<UpEntry> &ents) {
         c->h_perm[s] = std::move(perms[k]);
         c->h_perm_identity[s] = ident[k];
         c->basis.drop(s);   // its rows no longer belong to the data
+        c->h_has_scale[s] = 0;   // ... and neither do its noise scales
     }
     c->last_nbatch = 0;   // cached batch selection / factors no longer describe the resident patients
     c->last_has_inverse = false;
@@ -3380,9 +3405,306 @@ int warp_post_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double 
     return MEDGP_OK;
 }
 
+// ---- the heteroscedastic calls (kernels_hetero.h; geometry: hetero_tables.h; the Student-t constants: robust_tables.h) ---------------
+// MedgpDev::nscale is set for the length of ONE call: every way out of it clears the pointer, so no other call ever sees it.
+struct HeteroScope {
+    medgp_ctx *c;
+    explicit HeteroScope(medgp_ctx *c_) : c(c_) {}
+    ~HeteroScope() { c->dev.nscale = nullptr; }
+};
+struct HeteroCall {
+    HeteroBuffers hb;
+    size_t stride;   // doubles per role of BUF_HT_VEC
+    double *vec;
+    double *role(int r, const BatchPlan &P, const SizeClass &k) const { return vec + het_vec_offset(r, stride) + P.vec0 + k.off_vec; }
+};
+// What the three calls share: the argument checks, the plan, the capacity rule, the call's buffers, and the entry table of scales as the
+// pointer every class view of the call carries.  M: the posterior call's points; tab_per_entry: doubles of the robust call's table.
+int hetero_prepare(medgp_ctx *c, const char *who, int nbatch, const int32_t *slots, const double *theta, size_t M, size_t tab_per_entry, HeteroCall &hc) {
+    if (!slots || !theta) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    int rc;
+    if ((rc = check_q16(c, who, nullptr))) return rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = set_batch(c, nbatch, slots, false, true))) return rc;
+    const BatchPlan &P = c->plan;
+    if ((rc = check_one_wave(c, hetero_fits(P.need_mat, P.need_vec, c->rules.mem_budget), HET_MATS, " and vectors"))) return rc;
+    hc.stride = het_role_stride(P.vec0, P.need_vec);
+    hc.hb = hetero_buffers(P.vec0, P.need_vec, nbatch, M, tab_per_entry);
+    if ((rc = buf_ensure(c, BUF_HT_VEC, hc.hb.vec_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_HT_TAB, hc.hb.tab_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_HT_DELTA, hc.hb.delta_doubles * sizeof(double)))) return rc;
+    if ((rc = buf_ensure(c, BUF_HT_HAS, sizeof(int) * nbatch))) return rc;
+    hc.vec = buf<double>(c, BUF_HT_VEC);
+    c->dev.nscale = hc.vec + het_vec_offset(HET_VEC_SCALE, hc.stride);   // (class_view adds the class's offset, as for alpha)
+    return wait_lane0_staging(c);
+}
+// the entry table from the slots' resident scales (use_resident) or all ones
+int hetero_load(medgp_ctx *c, const int32_t *slots, int nbatch, bool use_resident, const HeteroCall &hc) {
+    const BatchPlan &P = c->plan;
+    const double *store = use_resident ? c->d_slot_scale : nullptr;
+    if (store) {
+        void *pin = nullptr;
+        int rc = pin_stage(c, sizeof(int) * nbatch, &pin);
+        if (rc) return rc;
+        for (int i = 0; i < nbatch; i++) ((int *)pin)[i] = c->h_has_scale[slots[P.order[i]]];
+        HIPCHK(c, hipMemcpyAsync(buf<int>(c, BUF_HT_HAS), pin, sizeof(int) * nbatch, hipMemcpyHostToDevice, c->stream));
+    }
+    for (const SizeClass &k : P.cls) {
+        const MedgpDev V = class_view(c, P, k);
+        Launcher l(c, KID_HT_LOAD);
+        hipLaunchKernelGGL(k_het_load, dim3((k.ld + 255) / 256, k.count), dim3(256), 0, c->stream, V, buf<int>(c, BUF_HT_HAS) + k.b0, store, hc.role(HET_VEC_SCALE, P, k));
+    }
+    return MEDGP_OK;
+}
+// k_wgrad (with_w) and k_het_rows on the entries of class k
+void hetero_rows(medgp_ctx *c, const BatchPlan &P, const SizeClass &k, const MedgpDev &V, bool with_w, const HeteroCall &hc) {
+    if (with_w) {
+        Launcher l(c, KID_WGRAD);   // (Q <= 16 was checked)
+        launch_wgrad(c, c->stream, V, k.count, wgrad_grid(P.en.data() + k.b0, k.count, k.nbmax));
+    }
+    Launcher l(c, KID_HT_ROWS);
+    hipLaunchKernelGGL(k_het_rows, dim3((k.ld + 255) / 256, k.count), dim3(256), 0, c->stream, V, hc.role(HET_VEC_SCALE, P, k), with_w ? 1 : 0,
+                       hc.role(HET_VEC_RESID, P, k), hc.role(HET_VEC_FVAR, P, k));
+}
+// the per-row outputs on their way home (queued; valid once the stream has been waited for), then het_rows_out lays them out
+int hetero_rows_download(medgp_ctx *c, const HeteroCall &hc, std::vector<double> &hv, bool want_scale, bool want_resid, bool want_fvar) {
+    hv.resize(hc.hb.vec_doubles);
+    const bool want[HET_VECS] = {want_scale, want_resid, want_fvar};
+    for (int r = 0; r < HET_VECS; r++)
+        if (want[r]) HIPCHK(c, hipMemcpyAsync(hv.data() + het_vec_offset(r, hc.stride), hc.vec + het_vec_offset(r, hc.stride), hc.stride * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return MEDGP_OK;
+}
+void hetero_rows_out(const medgp_ctx *c, const int32_t *slots, const int32_t *st, int nbatch, const HeteroCall &hc, const std::vector<double> &hv, int role, double *dst) {
+    if (!dst) return;
+    const BatchPlan &P = c->plan;
+    std::vector<int> en(nbatch);
+    for (int b = 0; b < nbatch; b++) en[b] = c->h_n[slots[b]];
+    const std::vector<int64_t> off = het_row_offsets(en.data(), nbatch);
+    for (const SizeClass &k : P.cls)
+        for (int j = 0; j < k.count; j++) {
+            const int b = P.order[k.b0 + j], s = slots[b];
+            het_rows_to_caller(hv.data() + het_vec_offset(role, hc.stride) + P.vec0 + k.off_vec + (size_t)j * k.ld, c->h_perm[s].data(), en[b], st[b] >= 0, dst + off[b]);
+        }
+}
+
+// The heteroscedastic nlml, its gradient and the row statistics.  hetero_prepare, the entry table from the resident scales, ONE pipeline
+// run whose assembly reads the table; then per size class in stream order: the unchanged k_wgrad (a gradient or fvar), k_het_rows,
+// k_slabsum and k_epilogue in its nlml mode.
+int hetero_grad_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int flag_grad, double *nlml, double *grad,
+                     double *resid, double *fvar, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
+    HeteroScope scope(c);
+    HeteroCall hc{};
+    int rc;
+    if ((rc = hetero_prepare(c, "medgp_hetero_nlml_grad", nbatch, slots, theta, 0, 0, hc))) return rc;
+    if ((rc = hetero_load(c, slots, nbatch, true, hc))) return rc;
+    if ((rc = factor_run_templated(c, nbatch, theta, 3))) return rc;
+    const BatchPlan &P = c->plan;
+    const bool with_w = flag_grad || fvar;
+    for (const SizeClass &k : P.cls) {
+        const MedgpDev V = class_view(c, P, k);
+        if (with_w || resid) hetero_rows(c, P, k, V, with_w, hc);
+        if (flag_grad) launch_slabsum(c, c->stream, V, k.count);
+        launch_epilogue(c, c->stream, V, k.count, c->d_theta, flag_grad, 1, c->d_nlml, c->d_grad, c->d_status_out, EPI_NLML);
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> hv;
+    std::vector<int32_t> st(nbatch);
+    if ((rc = hetero_rows_download(c, hc, hv, false, resid != nullptr, fvar != nullptr))) return rc;
+    if ((rc = download_objective(c, nbatch, flag_grad, nlml, grad, st.data()))) return rc;
+    hetero_rows_out(c, slots, st.data(), nbatch, hc, hv, HET_VEC_RESID, resid);
+    hetero_rows_out(c, slots, st.data(), nbatch, hc, hv, HET_VEC_FVAR, fvar);
+    if (status) std::memcpy(status, st.data(), sizeof(int32_t) * nbatch);
+    return MEDGP_OK;
+}
+
+// Student-t noise by variational reweighting.  `sweeps` times (pipeline run with the inverse, k_wgrad, k_het_rows, k_het_estep), all
+// queued on the stream with no host read-back in between; then the evaluation of J and its gradient at the last scales: pipeline run,
+// k_wgrad, k_het_rows, k_het_obj (J -> scal[2]) and finish_objective_class.  That is sweeps + 1 factorisations.
+int robust_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const double *nu, int sweeps, const double *scale0,
+                int flag_grad, double *obj, double *grad, double *scale, double *resid, double *fvar, double *delta, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (flag_grad & ~1) return fail(c, MEDGP_ERR_ARG, "unknown bits in flag_grad = %d", flag_grad);
+    if (!nu) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    if (sweeps < 0 || sweeps > ROBUST_MAX_SWEEPS) return fail(c, MEDGP_ERR_ARG, "sweeps = %d outside [0, %d]", sweeps, ROBUST_MAX_SWEEPS);
+    if (!slots || !theta) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    int rc;
+    if ((rc = check_call(c, nbatch, slots))) return rc;
+    const int D = c->rules.D;
+    {
+        const int64_t bad = robust_first_bad_nu(nu, (int64_t)nbatch * D);
+        if (bad >= 0) return fail(c, MEDGP_ERR_ARG, "nu[%lld] = %g is not finite and > 0", (long long)bad, nu[bad]);
+    }
+    std::vector<int> en(nbatch);
+    for (int b = 0; b < nbatch; b++) en[b] = c->h_n[slots[b]];
+    const std::vector<int64_t> off = het_row_offsets(en.data(), nbatch);
+    if (scale0) {
+        const int64_t bad = het_first_bad_scale(scale0, off[nbatch]);
+        if (bad >= 0) return fail(c, MEDGP_ERR_ARG, "scale0[%lld] = %g outside [2^-40, 2^40]", (long long)bad, scale0[bad]);
+    }
+    HeteroScope scope(c);
+    HeteroCall hc{};
+    if ((rc = hetero_prepare(c, "medgp_robust_nlml_grad", nbatch, slots, theta, 0, (size_t)D * ROBUST_TAB, hc))) return rc;
+    const BatchPlan &P = c->plan;
+    double *d_tab = buf<double>(c, BUF_HT_TAB), *d_delta = buf<double>(c, BUF_HT_DELTA);
+    {
+        void *pin = nullptr;
+        const size_t bytes = sizeof(double) * nbatch * D * ROBUST_TAB;
+        if ((rc = pin_stage(c, bytes, &pin))) return rc;
+        robust_fill_table(nu, (int64_t)nbatch * D, (double *)pin);
+        HIPCHK(c, hipMemcpyAsync(d_tab, pin, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    if (scale0) {   // the caller's rows to the grouped rows of every entry, ones in the padding: one transfer
+        void *pin = nullptr;
+        if ((rc = pin_stage(c, sizeof(double) * P.need_vec, &pin))) return rc;
+        double *img = (double *)pin;
+        std::fill_n(img, P.need_vec, 1.0);
+        for (const SizeClass &k : P.cls)
+            for (int j = 0; j < k.count; j++) {
+                const int b = P.order[k.b0 + j];
+                het_rows_to_grouped(scale0 + off[b], c->h_perm[slots[b]].data(), en[b], k.ld, img + k.off_vec + (size_t)j * k.ld);
+            }
+        HIPCHK(c, hipMemcpyAsync(hc.vec + het_vec_offset(HET_VEC_SCALE, hc.stride) + P.vec0, img, sizeof(double) * P.need_vec, hipMemcpyHostToDevice, c->stream));
+    } else if ((rc = hetero_load(c, slots, nbatch, false, hc))) return rc;
+    for (int it = 0; it < sweeps; it++) {
+        if ((rc = factor_run_templated(c, nbatch, theta, 3))) return rc;
+        for (const SizeClass &k : P.cls) {
+            const MedgpDev V = class_view(c, P, k);
+            hetero_rows(c, P, k, V, true, hc);
+            Launcher l(c, KID_HT_ESTEP);
+            hipLaunchKernelGGL(k_het_estep, dim3(k.count), dim3(256), 0, c->stream, V, d_tab, hc.role(HET_VEC_SCALE, P, k), hc.role(HET_VEC_RESID, P, k),
+                               hc.role(HET_VEC_FVAR, P, k), d_delta);
+        }
+    }
+    if ((rc = factor_run_templated(c, nbatch, theta, 3))) return rc;
+    const bool with_w = flag_grad || fvar;
+    for (const SizeClass &k : P.cls) {
+        const MedgpDev V = class_view(c, P, k);
+        if (with_w || resid) hetero_rows(c, P, k, V, with_w, hc);
+        {
+            Launcher l(c, KID_HT_OBJ);
+            hipLaunchKernelGGL(k_het_obj, dim3(k.count), dim3(256), 0, c->stream, V, d_tab, hc.role(HET_VEC_SCALE, P, k));
+        }
+        finish_objective_class(c, V, k.count, flag_grad);
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> hv, hd(nbatch, 0.0);
+    std::vector<int32_t> st(nbatch);
+    if ((rc = hetero_rows_download(c, hc, hv, scale != nullptr, resid != nullptr, fvar != nullptr))) return rc;
+    if ((rc = download_objective(c, nbatch, flag_grad, obj, grad, st.data(), hd.data(), d_delta, sweeps > 0 ? sizeof(double) * nbatch : 0))) return rc;
+    hetero_rows_out(c, slots, st.data(), nbatch, hc, hv, HET_VEC_SCALE, scale);
+    hetero_rows_out(c, slots, st.data(), nbatch, hc, hv, HET_VEC_RESID, resid);
+    hetero_rows_out(c, slots, st.data(), nbatch, hc, hv, HET_VEC_FVAR, fvar);
+    for (int b = 0; delta && b < nbatch; b++) delta[b] = st[b] >= 0 ? hd[b] : std::numeric_limits<double>::quiet_NaN();
+    if (status) std::memcpy(status, st.data(), sizeof(int32_t) * nbatch);
+    return MEDGP_OK;
+}
+
+// The heteroscedastic posterior at test points.  hetero_prepare (no n > 2 guard, as medgp_posterior_batch), the entry table from the
+// resident scales, one pipeline run; then per launch chunk of tiles of 64 points, in stream order: the unchanged k_pjvp_solve and
+// k_het_post (mean, var in fp64).  The points keep the caller's order.
+int hetero_post_impl(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets, const int32_t *meta2,
+                     const float *t2, const double *s2, double *mean, double *var, int32_t *status) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (!offsets) return fail(c, MEDGP_ERR_ARG, "NULL argument");
+    if (nbatch < 1) return fail(c, MEDGP_ERR_CAPACITY, "nbatch %d", nbatch);
+    int rc;
+    const int64_t M = check_points(c, nbatch, offsets, meta2, t2, false, nullptr);   // (mean / var are optional)
+    if (M < 0) return (int)M;
+    if ((mean == nullptr) != (var == nullptr)) return fail(c, MEDGP_ERR_ARG, "mean and var: both or neither");
+    for (int64_t j = 0; s2 && j < M; j++)
+        if (!(std::isfinite(s2[j]) && s2[j] >= 0.0 && s2[j] <= HET_SCALE_MAX)) return fail(c, MEDGP_ERR_ARG, "s2[%lld] = %g outside [0, 2^40]", (long long)j, s2[j]);
+    std::vector<double> ht2;
+    std::vector<int> hm2;
+    stage_points(c, M, meta2, t2, nullptr, ht2, hm2);
+    HeteroScope scope(c);
+    HeteroCall hc{};
+    if ((rc = hetero_prepare(c, "medgp_hetero_posterior_batch", nbatch, slots, theta, (size_t)M, 0, hc))) return rc;
+    if ((rc = hetero_load(c, slots, nbatch, true, hc))) return rc;
+    if ((rc = factor_run_templated(c, nbatch, theta, 1))) return rc;
+    const BatchPlan &P = c->plan;
+    PointTables<PostTile> T;
+    build_pjvp_tiles(table_classes(P), P.order.data(), offsets, c->posterior_budget, T);
+    const size_t Mz = (size_t)std::max<int64_t>(M, 1);
+    if ((rc = upload_point_call(c, M, ht2, hm2, T.tiles, T.work_need))) return rc;
+    if ((rc = buf_ensure(c, BUF_HT_OUT, hc.hb.out_doubles * sizeof(double)))) return rc;
+    double *d_out = buf<double>(c, BUF_HT_OUT);
+    double *d_mean = d_out + het_out_mean(Mz), *d_var = d_out + het_out_var(Mz), *d_s2 = d_out + 2 * Mz;
+    const bool with_s2 = s2 != nullptr && M > 0;
+    if (with_s2) {
+        void *pin = nullptr;
+        if ((rc = pin_stage(c, sizeof(double) * Mz, &pin))) return rc;
+        std::memcpy(pin, s2, sizeof(double) * M);
+        HIPCHK(c, hipMemcpyAsync(d_s2, pin, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+    }
+    for_solved_chunks(c, P, T, [&](const TileChunk &ch, const SizeClass &, const MedgpDev &V, const PostTile *tiles) {
+        Launcher l(c, KID_HT_POST);
+        hipLaunchKernelGGL(k_het_post, dim3(ch.nt), dim3(256), 0, c->stream, V, tiles, buf<int>(c, BUF_META2), buf<double>(c, BUF_WORK), ch.stride,
+                           with_s2 ? d_s2 : (const double *)nullptr, d_mean, d_var);
+    });
+    HIPCHK(c, hipGetLastError());
+    if ((rc = download_pair<double>(c, M, d_mean, d_var, mean, var))) return rc;
+    if ((rc = read_status(c, nbatch, status))) return rc;
+    free_retired(c);
+    return MEDGP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int medgp_set_noise_scale(medgp_ctx *c, int nslots, const int32_t *slots, const int64_t *offsets, const double *scale) {
+    if (!c) return MEDGP_ERR_ARG;
+    if (c->max_slots == 0) return fail(c, MEDGP_ERR_CAPACITY, "call medgp_reserve first");
+    if (nslots < 1 || !slots) return fail(c, MEDGP_ERR_ARG, "medgp_set_noise_scale: bad argument");
+    for (int k = 0; k < nslots; k++)
+        if (slots[k] < 0 || slots[k] >= c->max_slots || c->h_n[slots[k]] < 0) return fail(c, MEDGP_ERR_ARG, "slots[%d] = %d is not a resident patient", k, slots[k]);
+    if (!scale) {   // drop the tables
+        for (int k = 0; k < nslots; k++) c->h_has_scale[slots[k]] = 0;
+        return MEDGP_OK;
+    }
+    if (!offsets) return fail(c, MEDGP_ERR_ARG, "offsets is NULL");
+    if (offsets[0] != 0) return fail(c, MEDGP_ERR_ARG, "offsets[0] = %lld, expected 0", (long long)offsets[0]);
+    for (int k = 0; k < nslots; k++)
+        if (offsets[k + 1] - offsets[k] != c->h_n[slots[k]])
+            return fail(c, MEDGP_ERR_ARG, "offsets[%d..%d]: %lld scales for the %d observations of slot %d", k, k + 1, (long long)(offsets[k + 1] - offsets[k]), c->h_n[slots[k]], slots[k]);
+    {
+        const int64_t bad = het_first_bad_scale(scale, offsets[nslots]);
+        if (bad >= 0) return fail(c, MEDGP_ERR_ARG, "scale[%lld] = %g outside [2^-40, 2^40]", (long long)bad, scale[bad]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if (!c->d_slot_scale && (rc = dalloc(c, &c->d_slot_scale, (size_t)c->max_slots * c->ldn))) return rc;
+    for (int k = 0; k < nslots; k++) {
+        const int s = slots[k], n = c->h_n[s];
+        if (n > 0) {
+            void *pin = nullptr;
+            if ((rc = pin_stage(c, sizeof(double) * n, &pin))) return rc;
+            het_rows_to_grouped(scale + offsets[k], c->h_perm[s].data(), n, n, (double *)pin);
+            HIPCHK(c, hipMemcpyAsync(c->d_slot_scale + (size_t)s * c->ldn, pin, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    for (int k = 0; k < nslots; k++) c->h_has_scale[slots[k]] = 1;   // (only once every copy is queued: a failure above leaves the call without effect)
+    return MEDGP_OK;
+}
+
+int medgp_hetero_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, int flag_grad, double *nlml, double *grad,
+                           double *resid, double *fvar, int32_t *status) {
+    return hetero_grad_impl(c, nbatch, slots, theta, flag_grad, nlml, grad, resid, fvar, status);
+}
+
+int medgp_hetero_posterior_batch(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int64_t *offsets,
+                                 const int32_t *meta2, const float *t2, const double *s2, double *mean, double *var, int32_t *status) {
+    return hetero_post_impl(c, nbatch, slots, theta, offsets, meta2, t2, s2, mean, var, status);
+}
+
+int medgp_robust_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const double *nu, int sweeps,
+                           const double *scale0, int flag_grad, double *obj, double *grad, double *scale, double *resid, double *fvar,
+                           double *delta, int32_t *status) {
+    return robust_impl(c, nbatch, slots, theta, nu, sweeps, scale0, flag_grad, obj, grad, scale, resid, fvar, delta, status);
+}
 
 int medgp_warp_nlml_grad(medgp_ctx *c, int nbatch, const int32_t *slots, const double *theta, const int32_t *kind, const double *psi,
                          int flag_grad, double *nlml, double *grad, double *dpsi, double *logjac, int32_t *status) {
@@ -3626,8 +3948,11 @@ int medgp_profile_enable(medgp_ctx *c, int enable) {
 int medgp_profile_num_kernels(void) { return KID_FORECAST + 1; }
 int medgp_profile_num_kernels_all(void) { return KID_FC_WGRAD + 1; }
 int medgp_profile_num_kernels_ext(void) { return KID_EXT_COUNT; }
-int medgp_profile_num_kernels_ext2(void) { return KID_COUNT; }
-const char *medgp_profile_kernel_name(int k) { return (k >= 0 && k < KID_COUNT) ? kKernelNames[k] : ""; }
+int medgp_profile_num_kernels_ext2(void) { return KID_EXT2_COUNT; }
+int medgp_profile_num_kernels_ext3(void) { return KID_COUNT; }
+// (callers hold medgp_profile_kernel_name to "" from medgp_profile_num_kernels_ext2() on: the _ext3 entries have a name call of their own)
+const char *medgp_profile_kernel_name(int k) { return (k >= 0 && k < KID_EXT2_COUNT) ? kKernelNames[k] : ""; }
+const char *medgp_profile_kernel_name_ext3(int k) { return (k >= 0 && k < KID_COUNT) ? kKernelNames[k] : ""; }
 int medgp_profile_read(medgp_ctx *c, int k, double *ms_total, int64_t *launches) {
     if (!c || k < 0 || k >= KID_COUNT) return MEDGP_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));

@@ -35,9 +35,11 @@ struct MedgpDev {
     int ldn, max_slots, max_batch;   // ldn: leading dimension of THIS VIEW's batch buffers (a size class of the call: the class's largest n rounded up to 64)
     int pld;                 // row stride of the patient arrays pt / py / pmeta (the context's max_n rounded up to 64)
     int hyp_stride;          // doubles per batch entry in `hyp`
-    double pi;
     int dbg_fail;            // test hook (MEDGP_DEBUG_FAIL_ATTEMPTS=k): the first k factorisation attempts of every problem are
                              // treated as failed, which drives the reference's jitter loop deterministically (0 in production)
+                             // (it sits in what was padding in front of `pi`: with it there, `nscale` below leaves the size of the
+                             //  struct -- which k_cholinv keeps a copy of in scratch for reassemble_wg -- as it was)
+    double pi;
     // patients
     const int *pn;           // [slot] n
     const double *pt, *py;   // [slot][ldn]
@@ -70,6 +72,9 @@ struct MedgpDev {
     double *S, *SM, *SV;     // [batch][Q*D*D]
     double *slab;            // [batch][3][Q][slab_R][slab_C] piecewise block sums written by k_wgrad
     double *wdiag;           // [batch][ldn] diag(W)
+    const double *nscale;    // [batch][ldn] per-observation noise scales s_i > 0 in the grouped row order (the noise of row i is
+                             // sigma^2_{m_i} s_i), or null = all 1: set by the heteroscedastic calls alone (kernels_hetero.h), null in
+                             // every other call
     int slab_R, slab_C;
     size_t slab_stride;
 };
